@@ -12,6 +12,10 @@ ScanNet-shaped 150k-voxel scene per GPU: device collate (2 cm voxelisation, hash
 kernel maps -> Res16UNet34C -> 3x4 decoder passes -> 13 cost matrices -> Hungarian (device: usc_lsap_batch, scipy's
 algorithm and tie-breaking) -> 52 losses -> backward -> (N>1: gradient all-reduce) -> AdamW + OneCycleLR.  The raw scene arrays are resident in HBM before the
 timed region.  Rank 0 prints ONE JSON line (DESIGN.md §5 defines `roofline` and `cpu_baseline`).
+
+A plain run sets up, warms up, times the K steps and prints the line; `ms_per_step` is the wall time of one timed step.
+`--full` adds what the headline figure does not need (CPU baseline, the second row order, the roofline); `--dump-outputs
+DIR` writes what the last timed step computed as .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -100,7 +104,47 @@ def parse(argv=None):
                          "exchange costs when nothing hides it, to be read beside `ms_per_step` on an N-GPU node")
     ap.add_argument("--cpu-sample-voxels", type=int, default=10_000,
                     help="scene size of the cpu_baseline legs (3 warm-up + up to 10 timed passes of the CPU restatement each)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the second timed loop in "
+                         "the other row order (`value_zorder`), the dominant kernel's roofline (in-step launch marks + one "
+                         "instrumented step) and, with --mode ncut, the eigen-solve timing and its CPU baseline.  Without "
+                         "it the line holds `roofline: null` and `cpu_baseline: null`")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): "
+                         "mask3d / backbone: the total loss, every weighted loss, and a fixed seeded sample of the updated "
+                         "parameters and of their gradients; ncut: the masks of every scene of the last round")
     return ap.parse_args(argv)
+
+
+DUMP_SAMPLE = 1 << 20     # --dump-outputs: parameters / gradients sampled (4 MB each in float32)
+
+
+def dump_outputs(dirname, arrays):
+    """arrays: {name: tensor or array} -> DIR/<name>.npy, float32 (float64 kept)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if a.dtype != np.float64:
+            a = a.astype(np.float32)
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
+def step_outputs(loss, losses, params):
+    """What a caller of the training step holds after the last timed step: the total loss, the weighted losses by name,
+    and the parameters after the optimizer step with the gradients that moved them — the last two as the same fixed,
+    seeded sample of DUMP_SAMPLE positions in the concatenated parameter vector (all of it when it is smaller)."""
+    out = {"loss": loss.reshape(())}
+    out.update({k: v.reshape(()) for k, v in (losses or {}).items()})
+    with torch.no_grad():
+        p = torch.cat([q.detach().reshape(-1) for q in params])
+        g = torch.cat([q.grad.detach().reshape(-1) for q in params])
+        n = p.numel()
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_SAMPLE), replace=False))).to(p.device)
+        out["params_sample"] = p[idx]
+        out["grads_sample"] = g[idx]
+    return out
 
 
 def build_model(device):
@@ -282,7 +326,9 @@ def make_mask3d_step(args, dev, rank, world):
         if out is None:      # the trainer skips a batch without targets, like the reference (trainer/trainer.py:106-108)
             raise SystemExit("bench.py: training_step skipped the batch (no targets in the synthetic scene): "
                              "--voxels is too small for this benchmark")
-        total, _ = out
+        total, losses = out
+        if args.dump_outputs:          # kept for --dump-outputs only (detached: no graph node outlives its step)
+            state["losses"] = {k: v.detach() for k, v in losses.items()}
         opt.zero_grad(set_to_none=False)
         if reducer is not None:
             reducer.begin_step()
@@ -653,27 +699,42 @@ def run_ncut(args, dev):
     def run():
         for sc in scenes:
             sc["features"] = (dfe[0].clone(), dfe[1].clone())
-        return driver.run(scenes)[0]
+        return driver.run(scenes)
     for _ in range(args.warmup):
-        masks = run()
+        res = run()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        masks = run()
+        res = run()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps / K          # seconds per scene
-    # eigensolver alone (device time of one usc_ncut_fiedler call)
-    A, D = ncut.get_affinity_matrix((dfe[0].clone(), dfe[1].clone()), tau=0.6)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ncut.second_smallest_eigenvector(A, D)
-    e0.record()
-    for _ in range(5):
+    masks = res[0]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {f"masks_{i}": torch.as_tensor(m) for i, m in sorted(res.items())})
+    flops = 4.0 / 3.0 * S ** 3
+    roof = None
+    if args.full:
+        # eigensolver alone (device time of one usc_ncut_fiedler call)
+        A, D = ncut.get_affinity_matrix((dfe[0].clone(), dfe[1].clone()), tau=0.6)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ncut.second_smallest_eigenvector(A, D)
-    e1.record()
-    torch.cuda.synchronize()
-    eig_ms = e0.elapsed_time(e1) / 5
+        e0.record()
+        for _ in range(5):
+            ncut.second_smallest_eigenvector(A, D)
+        e1.record()
+        torch.cuda.synchronize()
+        eig_ms = e0.elapsed_time(e1) / 5
+        # a chain of S-1 dependent Householder steps, one grid-wide exchange each: neither HBM nor the matrix cores bound
+        # it.  What it is priced against is the exchange: the guide's ~4 us for one all-workgroup hand-over
+        # (MI355X_MICROARCH.md, grid barrier 4-7 us) — `frac` = that floor / the measured time per step of the solve
+        # (1 = nothing but exchanges)
+        roof = {"bound": "latency", "kernel": "usc_ncut_fiedler (tridiagonalisation + bisection + inverse iteration)",
+                "chain_steps": S - 1, "us_per_chain_step": 1e3 * eig_ms / max(1, S - 1), "exchange_floor_us": 4.0,
+                "achieved": 1e3 * eig_ms / max(1, S - 1), "peak": 4.0, "unit": "us per dependent step (lower is better)",
+                "frac": 4.0 / (1e3 * eig_ms / max(1, S - 1)), "traffic": None, "avg_call_ms": eig_ms,
+                "f64_gflop_per_call": flops / 1e9}
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import ncut_ref
         tf = tuple(torch.from_numpy(f) for f in feats)
         c0 = time.perf_counter()
@@ -683,7 +744,6 @@ def run_ncut(args, dev):
         cpu = {"value": 1.0 / cdt, "unit": "scenes/s", "cores": torch.get_num_threads(), "kind": "port",
                "sample": f"oracle/ncut_ref.unscene3d_ref (numpy + scipy.linalg.eigh subset) on the same {S}-segment "
                          f"scene, {cdt:.2f} s, {ref.shape[0]} masks"}
-    flops = 4.0 / 3.0 * S ** 3
     print(json.dumps({
         "metric": "pseudo-mask scenes/sec (masked NCut, 625 segments, 20 iterations)", "value": 1.0 / dt,
         "scenes_in_flight": K,
@@ -692,14 +752,7 @@ def run_ncut(args, dev):
         "config": {"workload": "BASELINE.json configs[4]: iterative masked NCut (affinity + generalized Fiedler vector, "
                                f"20 iterations) on one synthetic {S}-segment scene, DINO-like 384-d + CSC-like 96-d "
                                "segment features", "segments": S, "masks": int(masks.shape[0])},
-        # a chain of S-1 dependent Householder steps, one grid-wide exchange each: neither HBM nor the matrix cores bound it.
-        # What it is priced against is the exchange: the guide's ~4 us for one all-workgroup hand-over (MI355X_MICROARCH.md,
-        # grid barrier 4-7 us) — `frac` = that floor / the measured time per step of the solve (1 = nothing but exchanges)
-        "roofline": {"bound": "latency", "kernel": "usc_ncut_fiedler (tridiagonalisation + bisection + inverse iteration)",
-                     "chain_steps": S - 1, "us_per_chain_step": 1e3 * eig_ms / max(1, S - 1), "exchange_floor_us": 4.0,
-                     "achieved": 1e3 * eig_ms / max(1, S - 1), "peak": 4.0, "unit": "us per dependent step (lower is better)",
-                     "frac": 4.0 / (1e3 * eig_ms / max(1, S - 1)), "traffic": None, "avg_call_ms": eig_ms,
-                     "f64_gflop_per_call": flops / 1e9},
+        "roofline": roof,
         "cpu_baseline": cpu,
     }))
 
@@ -879,6 +932,7 @@ def main():
         xyz = torch.from_numpy(sc["xyz"]).to(dev)
         colors = torch.from_numpy(sc["colors"]).to(dev)
         step = lambda w: train_step(model, opt, xyz, colors, flat, w)
+        step.params = params
     else:
         step = make_mask3d_step(args, dev, rank, world)
 
@@ -906,7 +960,7 @@ def main():
     # (usc_launch_stats_begin: two atomics per workgroup) -> roofline.frac_in_step describes the configuration `value`
     # is measured in — lane, step program, captured decoder passes and all
     lstat_ring = None
-    if args.mode == "mask3d" and rank == 0:
+    if args.full and args.mode == "mask3d" and rank == 0:
         import ctypes as C
         from unscene3d_amd._lib import LaunchStat, check, lib
         lstat_slots = max(4096, 32 * args.steps)
@@ -949,6 +1003,8 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(loss, getattr(step, "state", {}).get("losses"), step.params))
 
     # The same K steps once more in the OTHER row order: `value` is measured in the reference's first-occurrence order
     # (ME.utils.sparse_quantize, datasets/utils.py:403-408 — FPS starts at row 0 and key sampling indexes rows, so this is
@@ -957,7 +1013,8 @@ def main():
     # --spatial-sort SHIFT makes z-order the measured order, the second loop is the reference order instead.
     ref_order = None
     other = 0 if args.spatial_sort else args.zorder_shift
-    if args.mode == "mask3d" and not args.no_second_order and hasattr(step, "set_spatial_sort") and (other or args.spatial_sort):
+    if (args.full and args.mode == "mask3d" and not args.no_second_order and hasattr(step, "set_spatial_sort")
+            and (other or args.spatial_sort)):
         step.set_spatial_sort(other)
         for _ in range(max(2, args.warmup)):
             step(world)
@@ -988,10 +1045,11 @@ def main():
     # Every rank runs it (the criterion's num_masks all-reduce and the gradient all-reduce are collectives); rank 0
     # reports.
     roof = None
-    with profiler.capture() as prof:
-        step(world)
-        torch.cuda.synchronize()
-    if rank == 0:
+    if args.full:
+        with profiler.capture() as prof:
+            step(world)
+            torch.cuda.synchronize()
+    if args.full and rank == 0:
         roof = prof.roofline(MFMA_F32_PEAK_TFLOPS)
         if roof is not None:
             # PMC counters cannot be read from inside the process; `traffic` is the per-launch HBM byte count
@@ -1058,7 +1116,8 @@ def main():
                                      if getattr(getattr(step, "opt", None), "_early_stream", None) is not None else "one launch after backward"),
                        **({} if ranks_seen is None else ranks_seen)},
             "roofline": roof,
-            "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else _unpinned(cpu_baseline, args.cpu_sample_voxels, args.mode),
+            "cpu_baseline": (_unpinned(cpu_baseline, args.cpu_sample_voxels, args.mode)
+                             if args.full and not args.no_cpu_baseline and world == 1 else None),
         }
         print(json.dumps(line))
     if hasattr(step, "close"):

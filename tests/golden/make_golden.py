@@ -9,6 +9,7 @@ not installed: SURVEY.md Appendix A), feeds them seeded inputs and stores inputs
     python tests/golden/make_golden.py decoder_pass   # one decoder pass, head-shared mask, forward + backward
     python tests/golden/make_golden.py aggregate  # N1 aggregate_features (mean / max, zero-segment fill)
     python tests/golden/make_golden.py felz       # Felzenszwalb over-segmentation (reference module built by oracle/Makefile)
+    python tests/golden/make_golden.py felz_build # the reference module's labels on the meshes of test_oracle_equals_reference_build
     python tests/golden/make_golden.py ncut       # NCut fixtures (separate interpreter: different stubs)
     python tests/golden/make_golden.py export     # eval/export post-processing fixtures (trainer.eval_instance_step)
     python tests/golden/make_golden.py dataset    # self-train mask merge + validation-mode scene reader fixtures
@@ -370,6 +371,29 @@ def make_felz():
         print("felz", name, "segments", int(labels.max()) + 1, "pairs", conn.shape, "distinct weights",
               len(np.unique(det["weights"])), "of", det["weights"].shape[0])
     np.savez_compressed(os.path.join(HERE, "felz.npz"), **out)
+
+
+FELZ_BUILD_CASES = ((11, 40, False), (12, 40, True), (13, 120, False), (14, 120, True))
+
+
+def make_felz_build():
+    """The reference's own felzenszwalb_cpp module (oracle/_ref/, see make_felz) on the seeded meshes of
+    tests/test_felzenszwalb.py::test_oracle_equals_reference_build — labels and connectivity for min_vertices 20 and 50.
+    Only the outputs are stored: the meshes are unscene3d_amd.synthetic.make_mesh(seed, side, quantise_colours)."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from oracle import felz_ref as FR
+    from unscene3d_amd.synthetic import make_mesh
+    ref = FR.reference_module()
+    assert ref is not None, "run `make -C oracle ref` first"
+    out = {}
+    for seed, side, q in FELZ_BUILD_CASES:
+        v, f, c = make_mesh(seed, side=side, quantise_colours=q)
+        for min_verts in (20, 50):
+            labels, conn = ref.segment_mesh(v, f, c, 0.005, min_verts)
+            out[f"{seed}/{min_verts}/labels"] = np.asarray(labels, np.int32)
+            out[f"{seed}/{min_verts}/connectivity"] = np.asarray(conn, np.int32).reshape(-1, 2)
+            print("felz_build", seed, min_verts, "segments", int(np.max(labels)) + 1, "pairs", len(conn))
+    np.savez_compressed(os.path.join(HERE, "felz_build.npz"), **out)
 
 
 def make_ncut_b(ref):
@@ -810,6 +834,8 @@ if __name__ == "__main__":
         make_export(import_reference_trainer())
     elif len(sys.argv) > 1 and sys.argv[1] == "felz":
         make_felz()
+    elif len(sys.argv) > 1 and sys.argv[1] == "felz_build":
+        make_felz_build()
     elif len(sys.argv) > 1 and sys.argv[1] == "decoder_pass":
         make_decoder_pass(import_reference_models())
     elif len(sys.argv) > 1 and sys.argv[1] == "aggregate":

@@ -43,3 +43,29 @@ def test_world_size_mismatch_is_refused():
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode != 0
     assert "--gpus 8 but WORLD_SIZE=1" in out.stderr
+
+
+def test_full_is_off_by_default_and_dumps_are_float_arrays(tmp_path):
+    """A plain run does only what the headline needs (--full opts in to the rest); --dump-outputs writes float arrays:
+    the losses by name and the same seeded sample of the parameters and of their gradients on every run."""
+    import numpy as np
+    import torch
+
+    bench = _load_bench()
+    assert bench.parse([]).full is False and bench.parse([]).dump_outputs is None
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full is True
+    torch.manual_seed(0)
+    lin = torch.nn.Linear(1500, 1000)
+    lin(torch.randn(4, 1500)).square().sum().backward()
+    params = list(lin.parameters())
+    a = bench.step_outputs(torch.tensor(2.5), {"loss_ce": torch.tensor(0.5)}, params)
+    b = bench.step_outputs(torch.tensor(2.5), {"loss_ce": torch.tensor(0.5)}, params)
+    assert a["params_sample"].shape == (bench.DUMP_SAMPLE,) and torch.equal(a["params_sample"], b["params_sample"])
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([p.grad.reshape(-1) for p in params])
+    idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(flat_p.numel(), bench.DUMP_SAMPLE, replace=False)))
+    assert torch.equal(a["params_sample"], flat_p[idx]) and torch.equal(a["grads_sample"], flat_g[idx])
+    bench.dump_outputs(str(tmp_path), a)
+    got = {f: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert set(got) == {"loss.npy", "loss_ce.npy", "params_sample.npy", "grads_sample.npy"}
+    assert all(v.dtype == np.float32 for v in got.values()) and float(got["loss.npy"]) == 2.5

@@ -3,7 +3,7 @@ USC3D_PROF_SHAPES=1 python tools/conv_report.py [--mode mask3d|backbone]"""
 import os, sys, json, subprocess
 os.environ["USC3D_PROF_SHAPES"] = "1"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline"] + sys.argv[1:],
+out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full"] + sys.argv[1:],
                      capture_output=True, text=True, env=os.environ)
 line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
 d = json.loads(line)

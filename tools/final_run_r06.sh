@@ -4,7 +4,7 @@ O=gpurun_out/r06g; mkdir -p $O
 s=$(date +%s)
 python -m pytest tests -m gpu -q --durations=30 -p no:cacheprovider > $O/tests.log 2>&1; tail -2 $O/tests.log
 echo "gpu suite: $(( $(date +%s) - s )) s" | tee $O/suite_seconds.txt
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-zorder 2>/dev/null | grep '^{' | tail -1 > $O/bench_steps20_warmup5.json
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-zorder --force-dist 2>/dev/null | grep '^{' | tail -1 > $O/bench_world1_rccl.json
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-zorder --scenes-per-gpu 8 2>/dev/null | grep '^{' | tail -1 > $O/bench_B8.json

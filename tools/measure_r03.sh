@@ -5,7 +5,7 @@ T=${1:-r03}
 O=gpurun_out/$T; mkdir -p $O
 line() { python -c "import sys,json; r=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); c=r['config']; print('$1', 'scenes/s', round(r['value'],2), 'ms/step', round(r['ms_per_step'],2), 'B', c.get('scenes_per_gpu'), 'voxels', c['voxels_per_scene'], {k:round(v,2) for k,v in c.items() if k.startswith('step_ms')})"; }
 # 1. default bench line (with cpu baseline)
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 # 2. step time vs scene size, scenes per GPU, rotation
 for v in 20000 80000 150000 300000; do python bench.py --no-cpu-baseline --voxels $v --steps 20 --warmup 5 2>/dev/null | line voxels=$v; done > $O/step_vs_scene_size.txt
 for B in 1 2 4 8; do python bench.py --no-cpu-baseline --steps 12 --warmup 4 --scenes-per-gpu $B 2>/dev/null | tee $O/bench_B$B.json | line B=$B; done > $O/scenes_per_gpu.txt
@@ -21,7 +21,7 @@ for k in gather_gemm wgrad; do python tools/pmc_summary.py $O/pmc_fetch $k; pyth
 rm -rf $O/pmc_fetch $O/pmc_write $O/prof
 # 5. HBM report, ncut bench, conv per shape
 python tools/hbm_report.py > $O/hbm_bound_kernels.txt 2>/dev/null
-python bench.py --mode ncut > $O/bench_ncut.json 2>/dev/null
+python bench.py --mode ncut --full > $O/bench_ncut.json 2>/dev/null
 for k in 1 2 4 8 16 24; do python bench.py --mode ncut --scenes $k --no-cpu-baseline --steps 2 --warmup 1 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.readline()); print('ncut scenes in flight', r['scenes_in_flight'], round(r['value'],2), 'scenes/s', round(r['ms_per_step'],1), 'ms/scene', r['config']['masks'], 'masks')"; done > $O/ncut_scenes_in_flight.txt
 USC3D_PROF_SHAPES=1 python tools/conv_report.py > $O/conv_per_shape.txt 2>/dev/null
 ls -la $O

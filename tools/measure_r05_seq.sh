@@ -3,7 +3,7 @@ set -x
 cd $GRAFT_REPO_ROOT
 T=${1:-r05a}
 O=gpurun_out/$T; mkdir -p $O
-python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 tail -n 1 $O/bench.json | cut -c 1-400
 for v in 150000 20000; do
   (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$O/trace$v -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-reference-order --steps 4 --warmup 3 --voxels $v > $GRAFT_REPO_ROOT/$O/trace$v.log 2>&1)
