@@ -327,12 +327,6 @@ typedef struct usc_bn {
   int32_t training;
 } usc_bn;
 
-/* Optional: a second stream of the CALLER (NULL switches it off again; per device).
- * usc_conv_backward / usc_conv_bn_act_backward then fork the weight gradient of
- * maps with <= 24 576 rows onto it and join before returning the stream to the
- * caller's order: on the coarse U-Net levels the input-gradient and weight-gradient
- * launches are latency-bound and run side by side.  Results are unchanged. */
-int usc_set_side_stream(usc_stream_t side);
 /* Optional: the weight-gradient LANE, a second stream of the caller with its own scratch (NULL lane: off; per device).
  * usc_conv_backward / usc_conv_bn_act_backward then queue the weight gradient of a map with <= max_rows rows (only
  * the accumulate-into-a-gradient-buffer form) on the lane behind one event of the caller's stream and return WITHOUT
@@ -515,7 +509,7 @@ int usc_bn_backward_dx(const float* x, const float* dy, const float* y_out,
  *             when it was formed from slices; a finished dout without dres is not written.
  * ws: usc_bn_tile_ws_bytes(c) bytes.  usc_bn_tile_ok(n, c): do the kernels cover this map (c a multiple of 32, <= 1024)?
  * usc_bn_tile_max_rows(): the map size up to which usc_conv_bn_act_forward / _backward and usc_program_run TAKE this form
- * (default 4 096 rows; USC3D_BN_TILE_ROWS, 0 = never). */
+ * (4 096 rows). */
 int64_t usc_bn_tile_max_rows(void);
 int usc_bn_tile_ok(int64_t n, int32_t c);
 int64_t usc_bn_tile_ws_bytes(int32_t c);

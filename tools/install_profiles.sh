@@ -1,4 +1,4 @@
-# copy one measurement set (tools/measure_r06.sh <tag>) from gpurun_out/<tag> into profiles/ as the round files (third argument: prefix, default r06)
+# copy one measurement set <tag> (written by tools/measure_r06.sh at a0f1986) into profiles/ as the round files (third argument: prefix, default r06)
 # usage: bash tools/install_profiles.sh <tag> "<comment for pmc_traffic.json>"
 T=${1:?tag}; C=${2:-"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over python bench.py (round 4)"}
 O=gpurun_out/$T

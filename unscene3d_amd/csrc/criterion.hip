@@ -362,8 +362,7 @@ int usc_lsap_batch(const float* cost, int32_t n_prob, int32_t nr, int32_t nc, in
   LsapLayout L = lsap_layout(r, c, true);
   if (L.total > kLsapLdsBudget) { stage = false; L = lsap_layout(r, c, false); }
   USC_REQUIRE(L.total <= kLsapLdsBudget, "usc_lsap_batch: %d x %d is too large for the one-wave solver (LDS)", nr, nc);
-  static const bool lds_form = getenv("USC3D_LSAP_LDS") != nullptr;      // A/B switch: the LDS-resident form
-  if (c <= 128 && stage && !lds_form)
+  if (c <= 128 && stage)
     hipLaunchKernelGGL(lsap_reg_kernel, dim3(n_prob), dim3(64), (size_t)L.total, as_stream(s), cost, (int)nr, (int)nc,
                        row_ind, col_ind, status);
   else

@@ -425,12 +425,6 @@ __global__ __launch_bounds__(256) void tri_persistent_kernel(TriPersist a) {
   if (tid == 0) s_abort = 0;
   __syncthreads();
 
-#ifdef USC_TRI_TIMING   // developer build (-DUSC_TRI_TIMING): cycles per phase of workgroups 0 and G-1, printed at the end
-  long long tA = 0, tB = 0, tC = 0, tD = 0, t0 = clock64(), t1;
-#define TRI_MARK(acc) do { t1 = clock64(); acc += t1 - t0; t0 = t1; } while (0)
-#else
-#define TRI_MARK(acc) do {} while (0)
-#endif
   for (int64_t i = 0; i + 1 < n; ++i) {
     // ---- reflector i from piv (x = piv[i+2..], alpha = piv[i+1]); every thread ends up with tau and scale ----
     {
@@ -469,7 +463,6 @@ __global__ __launch_bounds__(256) void tri_persistent_kernel(TriPersist a) {
       if (g == 0) t.Vt[i * n + r] = val;
     }
     __syncthreads();
-    TRI_MARK(tA);
     if (i + 2 >= n) break;   // last step: tau = 0 (empty x), nothing to update
     // ---- own rows of p = C22 v; the owner of row i+1 publishes it ----
     // slots of step i: p in [par*n, par*n + n), the published row in [(2 + par)*n, ...), par = i & 1
@@ -545,7 +538,6 @@ __global__ __launch_bounds__(256) void tri_persistent_kernel(TriPersist a) {
     // ---- exchange: every thread waits for the tagged slots it needs (this is the grid barrier: nobody gets past
     // step i without everybody's p of step i).  No counter, no drain, no atomic; a slot is rewritten at step i+2, by
     // which time every workgroup has produced step i+1 and therefore finished reading step i ----
-    TRI_MARK(tB);
     constexpr int K = 4;   // slots per thread and buffer in flight together
     for (int64_t c0 = i + 1 + tid; c0 < n; c0 += 256 * K) {
       u32x4 qp[K], qr[K];
@@ -579,7 +571,6 @@ __global__ __launch_bounds__(256) void tri_persistent_kernel(TriPersist a) {
       }
     }
     __syncthreads();
-    TRI_MARK(tC);
     if (s_abort) {
       if (g == 0 && tid == 0) t.d[0] = __builtin_nan("");
       return;
@@ -642,13 +633,7 @@ __global__ __launch_bounds__(256) void tri_persistent_kernel(TriPersist a) {
       }
     }
     __syncthreads();
-    TRI_MARK(tD);
   }
-#ifdef USC_TRI_TIMING
-  if ((g == 0 || g == G - 1) && tid == 0)
-    printf("tri timing wg %d: reflector %lld  symv+publish %lld  exchange %lld  update %lld cycles (n=%d)\n", g, tA, tB, tC, tD, (int)n);
-#endif
-#undef TRI_MARK
   // d[n-1]: bottom-right entry after the last update; its owner holds it
   if ((n - 1) % G == g) {
     const int qo = (int)((n - 1) / G);
@@ -769,12 +754,6 @@ __global__ __launch_bounds__(128) void tri_eig_kernel(const double* __restrict__
     for (int64_t j = threadIdx.x; j < n; j += 128) { const double ej = j < n - 1 ? e_g[j] : 0.0; e2[j] = ej * ej; }
     __syncthreads();
   }
-#ifdef USC_EIG_TIMING   // developer build: cycles per phase of wave 0, printed at the end
-  long long tph[6] = {0, 0, 0, 0, 0, 0}, tq0 = clock64(), tq1;
-#define EIG_MARK(i) do { tq1 = clock64(); tph[i] += tq1 - tq0; tq0 = tq1; } while (0)
-#else
-#define EIG_MARK(i) do {} while (0)
-#endif
   // Gershgorin interval
   double lo = 1e300, hi = -1e300;
   for (int64_t j = lane; j < n; j += 64) {
@@ -802,7 +781,6 @@ __global__ __launch_bounds__(128) void tri_eig_kernel(const double* __restrict__
   }
   if (lane == 0) eval_out[which] = lam;
   if (which != 0) return;
-  EIG_MARK(0);
   // ---- inverse iteration on wave 0.  The LU sweep and the two substitutions are recurrences (lane 0); everything
   // element-wise (set-up, reciprocals, norm, the 1/norm scaling, arg-max, sign, copy-out) is spread over the 64 lanes.
   // Lane 0's LDS/global writes are ordered against the other lanes' later reads by program order within the wave plus
@@ -835,7 +813,6 @@ __global__ __launch_bounds__(128) void tri_eig_kernel(const double* __restrict__
     }
   }
   USC_WAVE_SYNC();
-  EIG_MARK(1);
   if (lane == 0) {
     // state carried down the rows: U diagonal and first super-diagonal of the row being eliminated
     double ddj = dd[0], duj = n > 1 ? e[0] : 0.0;
@@ -869,7 +846,6 @@ __global__ __launch_bounds__(128) void tri_eig_kernel(const double* __restrict__
   USC_WAVE_SYNC();
   for (int64_t j = lane; j < n; j += 64) dd[j] = 1.0 / dd[j];
   USC_WAVE_SYNC();
-  EIG_MARK(2);
   double prev_change = 0.0;
   for (int it = 0; it < 6; ++it) {
     if (lane == 0) {
@@ -920,7 +896,6 @@ __global__ __launch_bounds__(128) void tri_eig_kernel(const double* __restrict__
       }
     }
     USC_WAVE_SYNC();
-    EIG_MARK(3);
     double nrm = 0.0;
     for (int64_t j = lane; j < n; j += 64) nrm += z[j] * z[j];
     for (int o = 32; o > 0; o >>= 1) nrm += __shfl_xor(nrm, o, 64);
@@ -942,7 +917,6 @@ __global__ __launch_bounds__(128) void tri_eig_kernel(const double* __restrict__
       zmax = fmax(zmax, __shfl_xor(zmax, o, 64));
     }
     USC_WAVE_SYNC();
-    EIG_MARK(4);
     // (wave-uniform)  The shift is an eigenvalue to an ulp, so one sweep suppresses every other component by
     // ~1e-16 / gap: a change <= 1e-11 means the iterate BEFORE this sweep was already that close, and this sweep took it
     // to the noise floor (measured: 2.5e-13 after sweep 1, 9.4e-14 from then on — the old 1e-14 bar was never met
@@ -968,13 +942,6 @@ __global__ __launch_bounds__(128) void tri_eig_kernel(const double* __restrict__
     const double zj = flip ? -z[j] : z[j];
     if (LDS) z_g[j] = zj; else z[j] = zj;
   }
-  EIG_MARK(5);
-#ifdef USC_EIG_TIMING
-  if (lane == 0)
-    printf("eig timing: bisection %lld  setup %lld  lu %lld  sweeps %lld  normalise %lld  sign+copy %lld cycles (n=%d)\n", tph[0],
-           tph[1], tph[2], tph[3], tph[4], tph[5], (int)n);
-#endif
-#undef EIG_MARK
 #undef USC_WAVE_SYNC
 }
 
@@ -1177,8 +1144,7 @@ static bool launch_persistent(const TriState& t, double* tail, hipStream_t st) {
   TriPersist a;
   a.t = t;
   // few workgroups: every arrival is an atomic on one word, and a step's work is tiny (n = 625: 2.4 kFLOP per row)
-  static const int g_env = [] { const char* e = getenv("USC3D_TRI_G"); return e ? atoi(e) : 0; }();
-  a.G = g_env > 0 ? g_env : 64;
+  a.G = 64;
   if (a.G > cus) a.G = cus;
   if ((int64_t)a.G > n / 2) a.G = (int)(n / 2);
   a.R = (int)ceil_div(n, a.G);

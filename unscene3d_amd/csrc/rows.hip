@@ -203,13 +203,7 @@ __global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(const double* __res
 // launches this replaces cost 9.4 us at 507 rows against ~5 us for the one; the statistics are the same f64 sums.
 // measured (profiles/r03_hbm_bound_kernels.txt): statistics 9.4 -> 4.2 us at 507 rows, 9.8 -> 8.0 at 2 222, slower from
 // 9 402; the backward reduce (three inputs) 11.6 -> 5.3 us at 507 rows but 11.9 -> 13.4 at 2 222
-static int64_t bn_small_rows(bool backward) {
-  static const int64_t knob = [] {
-    const char* e = getenv("USC3D_BN_SMALL_ROWS");   // measurement knob; 0 = always the two-launch form
-    return e ? (int64_t)atoll(e) : (int64_t)-1;
-  }();
-  return knob >= 0 ? knob : (backward ? 1024 : 4096);
-}
+static int64_t bn_small_rows(bool backward) { return backward ? 1024 : 4096; }
 template <int MODE, typename OUT>
 __global__ __launch_bounds__(256) void bn_small_kernel(StatArgs a, OUT o) {
   __shared__ double sh[8][256 + 2];
@@ -1234,11 +1228,10 @@ int usc_bn_backward_dx(const float* x, const float* dy, const float* y_out, cons
 }
 
 int64_t usc_bn_tile_max_rows(void) {
-  static const int64_t knob = getenv("USC3D_BN_TILE_ROWS") ? (int64_t)atoll(getenv("USC3D_BN_TILE_ROWS")) : (int64_t)4096;
-  // 0: the tile form is off (A/B switch).  4 096: the two coarsest levels of a 150 k-voxel scene; measured per unit
-  // (tools/bn_tile_bench.py) 17.3 -> 11.5 / 20.9 -> 9.5 us forward / backward at 507 rows, 18.5 -> 15.4 / 24.9 -> 17.9 at
-  // 2 222 x 128; at 9 402 rows the old launches are as fast (21.1 vs 22.3 / 24.3 vs 25.9): left as they were
-  return knob;
+  // 4 096: the two coarsest levels of a 150 k-voxel scene; measured per unit (tools/bn_tile_bench.py) 17.3 -> 11.5 /
+  // 20.9 -> 9.5 us forward / backward at 507 rows, 18.5 -> 15.4 / 24.9 -> 17.9 at 2 222 x 128; at 9 402 rows the old
+  // launches are as fast (21.1 vs 22.3 / 24.3 vs 25.9): left as they were
+  return 4096;
 }
 
 // what the kernels cover (any number of rows: <= 64 row tiles of whatever height); usc_bn_tile_max_rows() is the POLICY

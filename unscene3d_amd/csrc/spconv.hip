@@ -225,14 +225,7 @@ constexpr int kZeroRowFloats = 4096;
 // (a select on a loaded register makes the compiler wait for the load — and everything older — first)
 __device__ float g_zero_row[kZeroRowFloats + 8];
 
-#ifdef USC_PHASE_STATS   /* developer build (tools/build_ablate.sh phase "-DUSC_PHASE_STATS"): where a tile's cycles go */
-__device__ unsigned long long g_phase[16];
-#define USC_PH(idx, val) atomicAdd(&g_phase[idx], (unsigned long long)(val))
-#endif
-#ifndef USC_COMPACT_WAVES
-#define USC_COMPACT_WAVES 8          /* developer builds: 16 = one 1024-thread workgroup per CU (tools/build_ablate.sh) */
-#endif
-constexpr int kCompactWaves = USC_COMPACT_WAVES;   // 8: 512-thread workgroups, two resident per CU when their LDS fits
+constexpr int kCompactWaves = 8;   // 512-thread workgroups, two resident per CU when their LDS fits
 
 template <int NB>
 __global__ __launch_bounds__(64 * kCompactWaves, 4) void gather_gemm_compact_kernel(GemmParams p) {
@@ -265,10 +258,6 @@ __global__ __launch_bounds__(64 * kCompactWaves, 4) void gather_gemm_compact_ker
   }
   const int64_t r0 = tile * TM;
   if (p.stats && threadIdx.x == 0) atomicMin(p.stats, (unsigned long long)wall_clock64());
-#ifdef USC_PHASE_STATS
-  const long long ph_t0 = clock64();
-  long long ph_wait = 0, ph_flush = 0;
-#endif
 
   // ---- prologue: zero accumulators, compact the neighbour table of this tile per offset
   for (int e = threadIdx.x; e < (TM + 1) * BN / 4; e += NT) reinterpret_cast<float4*>(accT)[e] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -276,7 +265,7 @@ __global__ __launch_bounds__(64 * kCompactWaves, 4) void gather_gemm_compact_ker
   {
     // every neighbour-table word this wave compacts (<= 4 offsets x 4 chunks of 64 rows) is requested before the first one
     // is used: the ballot passes below depend on each other only through `base`, but one load per pass, each waited
-    // for, put ~10 dependent HBM round trips in front of every tile (round 6: tools/compact_phase.py, 6 % of a tile)
+    // for, put ~10 dependent HBM round trips in front of every tile (round 6: tools/compact_phase.py at a0f1986, 6 % of a tile)
     constexpr int kOffPerWave = (kMaxK + kCompactWaves - 1) / kCompactWaves;
     int nv[kOffPerWave][4];
 #pragma unroll
@@ -325,9 +314,6 @@ __global__ __launch_bounds__(64 * kCompactWaves, 4) void gather_gemm_compact_ker
   }
   __syncthreads();
   const int total_items = item_start[K < 32 ? K : 31] + (K >= 32 ? 0 : 0);
-#ifdef USC_PHASE_STATS
-  const long long ph_t1 = clock64();
-#endif
 
   // ---- main loop.  A wave walks its items (item = wave, wave + 8, ...); one item = 32 real pairs of one
   // offset k, reduced over Cin in "quads" of 8 input channels (one 16-byte load of the gathered row per lane
@@ -368,17 +354,8 @@ __global__ __launch_bounds__(64 * kCompactWaves, 4) void gather_gemm_compact_ker
     st.wk = wp_cb + (int64_t)k * cin * BN;
     return st;
   };
-#ifndef USC_KDB
-#define USC_KDB 1
-#endif
-#ifndef USC_KRB
-#define USC_KRB 2
-#endif
-#ifndef USC_KDA
-#define USC_KDA 3
-#endif
-  constexpr int kDA = USC_KDA, kDB = USC_KDB;  // prefetch distances in quads
-  constexpr int kRA = 4, kRB = USC_KRB;  // ring sizes (the quad loop is unrolled by 4: static slots)
+  constexpr int kDA = 3, kDB = 1;  // prefetch distances in quads
+  constexpr int kRA = 4, kRB = 2;  // ring sizes (the quad loop is unrolled by 4: static slots)
   float4 ra[kRA];
   float4 rb[kRB][NB];   // [slot][accumulator] -> the 4 k-steps of the quad
   f32x16 acc[NB];
@@ -389,91 +366,47 @@ __global__ __launch_bounds__(64 * kCompactWaves, 4) void gather_gemm_compact_ker
       for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
   };
   auto load_a = [&](float4& dst, const float* src) {
-#ifdef USC_ABLATE_A
-    dst = make_float4(1.f, 2.f, 3.f, 4.f);
-#else
     dst = *reinterpret_cast<const float4*>(src);
-#endif
   };
   auto load_bq = [&](float4 (&dst)[NB], const float* wq) {   // wq: uniform address of the quad's packed weights
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-#ifdef USC_ABLATE_B
-      dst[nb] = make_float4(1.f + nb, 2.f + nb, 3.f + nb, 4.f + nb);
-#else
       dst[nb] = *reinterpret_cast<const float4*>(wq + nb * 256 + lane * 4);
-#endif
     }
   };
   auto flush = [&](const Item& st) {
-#ifdef USC_ABLATE_FLUSH
-    float sink = 0.f;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sink += acc[nb][r];
-    if (sink == 1.2345e-30f) accT[lane] = sink;
-    zero_acc();
-    return;
-#endif
     // ordered flush into the LDS accumulators (ticket == item index).  The ticket lives in LDS and is polled
     // with ds_read (an address_space(3) pointer: the generic `volatile int*` compiled to flat_load sc0 sc1 +
     // s_waitcnt vmcnt(0), draining the prefetch rings at every poll).  LDS executes one wave's instructions in
     // issue order, so the hand-off needs no memory fence — which would also wait for vmcnt(0) — only the
     // compiler barriers and lgkmcnt waits below.
-#ifdef USC_PHASE_STATS
-    const long long ph_f0 = clock64();
-#endif
     // The local output rows of this lane's 16 accumulator rows, read BEFORE the ticket (the pair lists do not change after
     // the prologue): accumulator row r = 4g + q belongs to pair 8g + q + 4h of the item, so a lane's rows are four runs of
     // four consecutive bytes — four aligned word reads, all in flight while lane 0 polls.  (Round 6: the first version read
     // one byte per row inside the ordered section, each behind an `s_waitcnt lgkmcnt(0)` — sixteen dependent LDS round
-    // trips under the ticket; tools/compact_phase.py put the section at a fifth of a wave's time.)
+    // trips under the ticket; tools/compact_phase.py at a0f1986 put the section at a fifth of a wave's time.)
     uint32_t loc4[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) loc4[g] = *reinterpret_cast<const uint32_t*>(pl_loc + st.pbase + 8 * g);
-#ifndef USC_ABLATE_TICKET
     if (lane == 0) {
-#ifndef USC_POLL_SLEEP
-#define USC_POLL_SLEEP 1
-#endif
       // The ticket counts FLUSHED items.  Items are numbered offset-major and the items of one offset touch disjoint
       // output rows (a row has at most one neighbour per offset), so an item only has to wait for the offsets before
       // its own — st.first = index of the first item of its offset — not for its siblings: the ~2 items per offset of a
       // 148-row tile flush side by side, and every output element is still summed over k ascending (bit-identical).
-      while (*ticket3 < st.first) __builtin_amdgcn_s_sleep(USC_POLL_SLEEP);
+      while (*ticket3 < st.first) __builtin_amdgcn_s_sleep(1);
     }
     __builtin_amdgcn_wave_barrier();
-#endif
-#ifdef USC_PHASE_STATS
-    const long long ph_f1 = clock64();
-#endif
-#ifndef USC_NO_SETPRIO
     // the ticket holder is the workgroup's critical path: without priority its LDS/VALU instructions queue
     // behind the other waves' MFMAs (issue is arbitrated by priority, then age) and the serialised section
     // stretched to ~10k cycles per item — measured: ticket alone +3 %, RMW alone +8 %, both together +77 %.
     __builtin_amdgcn_s_setprio(3);
-#endif
     asm volatile("" ::: "memory");
     // Plain LDS read-add-write; the ticket gives this wave exclusive, ordered access (ds_add_f32
     // atomics measured 2x slower for the whole kernel).  No branches: a padding pair's rows go to the dummy row
     // accT[TM] (its accumulators are exact zeros — the pair gathered the all-zero row — but -0 + 0 would flip a sign
     // bit in a real row).  The reads of a batch of rows are issued before the first dependent add so the row updates
     // pipeline instead of paying one LDS round trip each.
-#ifndef USC_KFB
-#define USC_KFB 4
-#endif
-    constexpr int kFB = USC_KFB;   // rows per batch (register budget: the load rings stay live across the flush)
-#ifdef USC_ABLATE_RMW
-    {
-      float sink = 0.f;
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sink += acc[nb][r];
-      if (sink == 1.2345e-30f + (float)loc4[0]) accT[lane] = sink;
-    }
-#else
+    constexpr int kFB = 4;   // rows per batch (register budget: the load rings stay live across the flush)
 #pragma unroll
     for (int part = 0; part < 16 / kFB; ++part) {
       float* dsts[kFB];
@@ -494,19 +427,11 @@ __global__ __launch_bounds__(64 * kCompactWaves, 4) void gather_gemm_compact_ker
         for (int nb = 0; nb < NB; ++nb) dsts[q][nb] = old[q][nb] + acc[nb][r];
       }
     }
-#endif
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's LDS updates are done before the ticket moves
-#ifndef USC_ABLATE_TICKET
     __builtin_amdgcn_wave_barrier();
     if (lane == 0)   // ds_add on the LDS address (a generic pointer would compile to a flat atomic and drain the load rings)
       __hip_atomic_fetch_add((__attribute__((address_space(3))) int32_t*)ticket3, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
-#ifndef USC_NO_SETPRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
-#ifdef USC_PHASE_STATS
-    { const long long ph_f2 = clock64(); ph_wait += ph_f1 - ph_f0; ph_flush += ph_f2 - ph_f1; }
-#endif
     zero_acc();
   };
 
@@ -537,19 +462,10 @@ __global__ __launch_bounds__(64 * kCompactWaves, 4) void gather_gemm_compact_ker
     while (true) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-#ifndef USC_LOAD_B_FIRST
+        // (Round 6, measured and not kept: the weights loaded in front of the gathered row — 24.1 against 23.9 ms
+        // per step; vector loads return in order, and what this loop waits for is not the gathered rows' latency.)
         load_a(ra[(u + kDA) % kRA], pa); advance_a();
         load_bq(rb[(u + kDB) % kRB], pb); advance_b();
-#else
-        // Developer switch, measured in round 6 and NOT kept: vector loads return in order, and the next quad's first MFMA
-        // waits for this quad's weight loads — with the gather issued in front of them it also waits for a row requested
-        // only one quad earlier, whatever the ring's nominal distance of kDA quads.  Weights first doubles that distance
-        // (the ISA shows vmcnt(7) instead of vmcnt(6)): 0.511 / 0.478 ms against 0.509 / 0.466 (96 -> 96, 148 564 rows,
-        // forward / input gradient), 24.1 against 23.9 ms per step, and kDA = 2 is as fast as 3 — the gathered rows'
-        // latency is not what this loop waits for.
-        load_bq(rb[(u + kDB) % kRB], pb); advance_b();
-        load_a(ra[(u + kDA) % kRA], pa); advance_a();
-#endif
         __builtin_amdgcn_sched_barrier(0);
         const float4 a4 = ra[u % kRA];
         const float av[4] = {a4.x, a4.y, a4.z, a4.w};
@@ -573,14 +489,7 @@ __global__ __launch_bounds__(64 * kCompactWaves, 4) void gather_gemm_compact_ker
       }
     }
   }
-#ifdef USC_PHASE_STATS
-  const long long ph_tw = clock64();
-#endif
   __syncthreads();
-#ifdef USC_PHASE_STATS
-  const long long ph_t3 = clock64();
-  if (lane == 0) { USC_PH(3, ph_t3 - ph_tw); USC_PH(4, ph_wait); USC_PH(5, ph_flush); USC_PH(8, ph_tw - ph_t1); }
-#endif
 
   // ---- epilogue: coalesced copy of the tile to HBM
   // (Round 6, measured and not kept: in this loop the compiler waits for `vmcnt(0)` at the join of the bias / accumulate
@@ -606,12 +515,6 @@ __global__ __launch_bounds__(64 * kCompactWaves, 4) void gather_gemm_compact_ker
     }
     *reinterpret_cast<float4*>(dst) = v;
   }
-#ifdef USC_PHASE_STATS
-  if (threadIdx.x == 0) {
-    const long long ph_t4 = clock64();
-    USC_PH(0, ph_t1 - ph_t0); USC_PH(1, ph_t3 - ph_t1); USC_PH(2, ph_t4 - ph_t3); USC_PH(6, 1); USC_PH(7, total_items);
-  }
-#endif
   if (p.stats && threadIdx.x == 0) {
     if (blockIdx.y == 0) {
       int pairs = 0;
@@ -997,9 +900,6 @@ __global__ __launch_bounds__(256, (CT * NB > 9) ? 1 : 2) void wgrad_full_kernel(
   float aX[4][CT], aY[4][CT], bX[4][NB], bY[4][NB];
   int id1 = load_idx(cb), id2 = load_idx(cb + 8);
   load_rows(id1, aX, bX);
-#ifdef USC_ABLATE_WG_LOOP
-  if (p.cin < 0)
-#endif
   for (int64_t q = cb; q < ce; q += 16) {
     const int id3 = load_idx(q + 16);
     load_rows(id2, aY, bY);
@@ -1012,12 +912,6 @@ __global__ __launch_bounds__(256, (CT * NB > 9) ? 1 : 2) void wgrad_full_kernel(
   //  two resident workgroups share — 1.8 GFLOP = 11 us at peak for the 507-row 256->256 layer, 15 us measured — not by
   //  its loads)
 
-#ifdef USC_ABLATE_WG_EPI
-  if (p.cin > 0) {
-    if (wave == 0 && lane == 0) p.partial[((int64_t)s * p.K + k) * cin * cout + ci0 * cout + co0] = acc[0][0] + acc[NA - 1][15];
-    return;
-  }
-#endif
   // Reduction over the four waves, in the fixed order w0 + ((w3 + w2) + w1) per element, one input-channel tile (ct)
   // at a time: every wave parks the tile's NB*16 accumulators in LDS, then wave w sums accumulator rows 4w .. 4w+3
   // over the four waves and writes them — all four waves add and store (the first version let wave 3, 2, 1 add in
@@ -1212,8 +1106,7 @@ static int wgrad_splits(int K, int cin, int cout, int NB, int64_t n_rows) {
   const int64_t tiles = (int64_t)K * ceil_div(cin, 32) * ceil_div(cout, NB * 32);
   // measured on the 128->96 layers (tools/scratch/r03/wg_target2.sh): 4.0 M pairs 902 / 776 / 730 / 745 us at 1 024 /
   // 2 048 / 4 096 / 6 912 workgroups, 1.1 M pairs 286 / 266 / 276 / 303 us
-  static const int knob = getenv("USC3D_WGRAD_TILE_TARGET") ? atoi(getenv("USC3D_WGRAD_TILE_TARGET")) : 0;
-  const int target = knob > 0 ? knob : ((K > 1 && n_rows >= (int64_t)2 << 20) ? 4096 : 2048);
+  const int target = (K > 1 && n_rows >= (int64_t)2 << 20) ? 4096 : 2048;
   int64_t S = ceil_div(target, tiles);
   const int64_t by_rows = n_rows / 2048 + 1;
   if (S > by_rows) S = by_rows;
@@ -1222,33 +1115,21 @@ static int wgrad_splits(int K, int cin, int cout, int NB, int64_t n_rows) {
   return (int)S;
 }
 static int wgrad_full_nb(int cb) { return (cb % 3 == 0) ? 3 : (cb % 4 == 0 ? 4 : (cb % 2 == 0 ? 2 : 1)); }
-static bool wgrad_big_tiles() {      // USC3D_WGRAD_BIG=0: without the 12-tile forms (A/B switch)
-  static const bool on = !getenv("USC3D_WGRAD_BIG") || atoi(getenv("USC3D_WGRAD_BIG")) != 0;
-  return on;
-}
 static int wgrad_full_ct(int ctiles, int NBf) {
-  if (wgrad_big_tiles()) {
-    if (NBf == 3 && ctiles % 3 != 0 && ctiles % 4 == 0) return 4;     // e.g. 128 -> 96: 148 -> 134 us per launch on average
-    // (the mirror form <3,4> for 96 -> 128 measured SLOWER than one input tile per workgroup, 167 vs 75 us on the K = 1
-    //  layer of the finest level: not used)
-  }
+  if (NBf == 3 && ctiles % 3 != 0 && ctiles % 4 == 0) return 4;     // e.g. 128 -> 96: 148 -> 134 us per launch on average
+  // (the mirror form <3,4> for 96 -> 128 measured SLOWER than one input tile per workgroup, 167 vs 75 us on the K = 1
+  //  layer of the finest level: not used)
   return (ctiles % 3 == 0 && NBf * 3 <= 9) ? 3 : ((ctiles % 4 == 0 && NBf * 4 <= 9) ? 4 : ((ctiles % 2 == 0 && NBf * 2 <= 9) ? 2 : 1));
 }
 static int64_t wgrad_full_splits(int K, int ctiles, int cb, int CT, int NBf, int64_t n_rows) {
   const int64_t blocks_per_split = (int64_t)K * (ctiles / CT) * (cb / NBf);
-  static const int target = getenv("USC3D_WGRAD_TARGET_BLOCKS") ? atoi(getenv("USC3D_WGRAD_TARGET_BLOCKS")) : 512;
-  static const int rows_per = getenv("USC3D_WGRAD_ROWS_PER_SPLIT") ? atoi(getenv("USC3D_WGRAD_ROWS_PER_SPLIT")) : 4096;
   // 512: one round of 2 workgroups per CU.  The finest level (4.0 M pairs at 150 k voxels) is the exception: 64 slices
   // of its 27 x 1 x 1 workgroups (1 728, ~0.9 MB each) measured 417 us against 451 us with 18 (86.5 vs 80 TFLOP/s) — the
   // long pair lists leave a tail of half-empty CUs that more, shorter workgroups fill; from 1.1 M pairs down the extra
   // slices cost more than they return (158 -> 164 us, 33 -> 38 us on the coarse levels).
-  const int64_t tgt = (K > 1 && n_rows >= (int64_t)2 << 20 && target < 2048) ? 2048 : target;
+  const int64_t tgt = (K > 1 && n_rows >= (int64_t)2 << 20) ? 2048 : 512;
   int64_t S = tgt / blocks_per_split;
-  // USC3D_WGRAD_ONE_SLICE_FROM=<blocks>: no pair split (and no reduction launch) once a single slice already has that
-  // many workgroups (experiment knob)
-  static const int one_from = getenv("USC3D_WGRAD_ONE_SLICE_FROM") ? atoi(getenv("USC3D_WGRAD_ONE_SLICE_FROM")) : 0;
-  if (one_from > 0 && blocks_per_split >= one_from) S = 1;
-  const int64_t by_rows = n_rows / (K > 1 ? rows_per : 256) + 1;   // identity pairs (dense layers): 64 rows per wave suffice
+  const int64_t by_rows = n_rows / (K > 1 ? 4096 : 256) + 1;   // identity pairs (dense layers): 64 rows per wave suffice
   if (S > by_rows) S = by_rows;
   if (S > 64) S = 64;
   if (S < 1) S = 1;
@@ -1271,8 +1152,7 @@ constexpr int64_t kTargetWaves = 3072;
 
 // few input channels, 32 output channels, a neighbour table: stem_conv_kernel
 static bool stem_form(bool has_table, int cin, int cout, int K) {
-  static const bool on = !getenv("USC3D_STEM_KERNEL") || atoi(getenv("USC3D_STEM_KERNEL")) != 0;
-  return on && has_table && cin >= 1 && cin <= 4 && cout == 32 && K >= 1 && K <= 32;
+  return has_table && cin >= 1 && cin <= 4 && cout == 32 && K >= 1 && K <= 32;
 }
 
 static GemmPlan plan_table(int64_t n_out, int cin, int cout, int K) {
@@ -1285,16 +1165,14 @@ static GemmPlan plan_table(int64_t n_out, int cin, int cout, int K) {
     // per CU; the tile height is chosen so that the tiles fill an integer number of 256-CU rounds.
     const int cb = cout / 32;
     const int nb = (cb % 3 == 0) ? 3 : (cb % 2 == 0 ? 2 : 1);
-#ifndef USC_TM_MAX3
-#define USC_TM_MAX3 192
-#endif
-    const int tm_max = nb == 3 ? USC_TM_MAX3 : 256;
-#ifndef USC_TILE_SLOTS
-#define USC_TILE_SLOTS 256   /* whole rounds of 256 CUs; 512 (both resident workgroups of a CU) measured 5 % slower on the 40 k-row map: smaller tiles pad more */
-#endif
+    constexpr int kTmMax3 = 192;
+    // whole rounds of 256 CUs; 512 (both resident workgroups of a CU) measured 5 % slower on the 40 k-row map: smaller
+    // tiles pad more
+    constexpr int64_t kTileSlots = 256;
+    const int tm_max = nb == 3 ? kTmMax3 : 256;
     int64_t R = 1;
-    int64_t tm = ceil_div(n_out, (int64_t)USC_TILE_SLOTS * R);
-    while (tm > tm_max) { ++R; tm = ceil_div(n_out, (int64_t)USC_TILE_SLOTS * R); }
+    int64_t tm = ceil_div(n_out, kTileSlots * R);
+    while (tm > tm_max) { ++R; tm = ceil_div(n_out, kTileSlots * R); }
     tm = (tm + 3) & ~3ll;
     pl.NB = nb;
     pl.TM = (int)tm;
@@ -1379,7 +1257,7 @@ int usc_spconv_plan(int32_t kind, int64_t n, int32_t cin, int32_t cout, int32_t 
     // wgrad: mirror usc_spconv_wgrad's choice (full kernel: NB | 1<<8 | 1<<13 | CT<<16)
     const int ctiles = cin / 32, cb = cout / 32;
     const int NBf = (cb % 3 == 0) ? 3 : (cb % 4 == 0 ? 4 : (cb % 2 == 0 ? 2 : 1));
-    if (cin % 32 == 0 && cout % 32 == 0 && (!(NBf == 3 && ctiles % 3 != 0) || (wgrad_big_tiles() && ctiles % 4 == 0))) {
+    if (cin % 32 == 0 && cout % 32 == 0 && (!(NBf == 3 && ctiles % 3 != 0) || ctiles % 4 == 0)) {
       const int CT = wgrad_full_ct(ctiles, NBf);
       return NBf | (1 << 8) | (1 << 13) | (CT << 16);
     }
@@ -1427,15 +1305,6 @@ int64_t usc_launch_stats_end(usc_launch_stat* host_out, int64_t max_out) {
   g_lstats.meta.clear();
   return n;
 }
-
-#ifdef USC_PHASE_STATS
-// developer build only: read (and clear) the phase counters of gather_gemm_compact_kernel
-extern "C" int usc_phase_stats_read(unsigned long long* out16) {
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_phase), sizeof(unsigned long long) * 16) != hipSuccess) return USC_ERR_LAUNCH;
-  unsigned long long z[16] = {0};
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof(z)) == hipSuccess ? USC_OK : USC_ERR_LAUNCH;
-}
-#endif
 
 int64_t usc_wall_clock_khz(void) {
   int dev = 0, khz = 0;
@@ -1534,14 +1403,12 @@ int64_t usc_spconv_wgrad_ws_bytes(int32_t K, int32_t cin, int32_t cout) {
 int64_t usc_spconv_wgrad_ws_bytes_rows(int32_t K, int32_t cin, int32_t cout, int64_t n_rows) {
   // the split count usc_spconv_wgrad will choose for this pair-list capacity (same arithmetic)
   const int64_t numel = (int64_t)K * cin * cout;
-#ifndef USC_WGRAD_LEGACY
   const int ctiles = cin / 32, cb = cout / 32;
   if (cin % 32 == 0 && cout % 32 == 0 && cb > 0) {
     const int NBf = wgrad_full_nb(cb);
-    if (!(NBf == 3 && ctiles % 3 != 0) || (wgrad_big_tiles() && ctiles % 4 == 0))
+    if (!(NBf == 3 && ctiles % 3 != 0) || ctiles % 4 == 0)
       return wgrad_full_splits(K, ctiles, cb, wgrad_full_ct(ctiles, NBf), NBf, n_rows) * numel * 4;
   }
-#endif
   return (int64_t)wgrad_splits(K, cin, cout, pick_nb(cout), n_rows) * numel * 4;
 }
 
@@ -1569,7 +1436,7 @@ int usc_spconv_wgrad_table(const float* in, int32_t cin, const float* dy, int32_
 // > 0: usc_spconv_wgrad launches its all-input-tiles kernel with at most this many workgroups along x, each walking
 // several (offset, split) work items — set around the launches of the weight-gradient lane (units.hip), which run
 // BESIDE the backward pass's own chain and must leave it wave slots on every CU
-static int g_wgrad_grid_limit = getenv("USC3D_WGRAD_GRID_LIMIT") ? atoi(getenv("USC3D_WGRAD_GRID_LIMIT")) : 0;
+static int g_wgrad_grid_limit = 0;
 void usc_spconv_wgrad_grid_limit(int32_t max_workgroups) { g_wgrad_grid_limit = max_workgroups; }
 
 int usc_spconv_wgrad(const float* a, int32_t cin, const float* b, int32_t cout, int32_t K, const int32_t* a_idx,
@@ -1583,12 +1450,11 @@ int usc_spconv_wgrad(const float* a, int32_t cin, const float* b, int32_t cout, 
   WgradParams p{};
   p.a = a; p.b = b; p.a_idx = a_idx; p.b_idx = b_idx; p.koff = koff; p.n_rows = n_rows;
   p.partial = (float*)ws; p.cin = cin; p.cout = cout; p.K = K;
-#ifndef USC_WGRAD_LEGACY
   const int ctiles = cin / 32, cb = cout / 32;
   const int NBf = wgrad_full_nb(cb);
   // (128 -> 96 channels would need 4x3 tiles = 256 VGPRs + scratch, or 2x3 twice: both measured slower than the
   //  per-input-tile kernel below, 0.78 / 0.82 vs 0.73 ms)
-  if (cin % 32 == 0 && cout % 32 == 0 && (!(NBf == 3 && ctiles % 3 != 0) || (wgrad_big_tiles() && ctiles % 4 == 0))) {
+  if (cin % 32 == 0 && cout % 32 == 0 && (!(NBf == 3 && ctiles % 3 != 0) || ctiles % 4 == 0)) {
     // CT input tiles x NB column tiles per wave, CT*NB <= 9 accumulator tiles
     const int CT = wgrad_full_ct(ctiles, NBf);
     const int64_t S = wgrad_full_splits(K, ctiles, cb, CT, NBf, n_rows);
@@ -1614,7 +1480,6 @@ int usc_spconv_wgrad(const float* a, int32_t cin, const float* b, int32_t cout, 
     USC_CHECK_LAUNCH("usc_spconv_wgrad");
     return USC_OK;
   }
-#endif
   const int NB = pick_nb(cout);
   const bool aligned = (cin % 32 == 0) && (cout % (NB * 32) == 0);
   const int S = wgrad_splits(K, cin, cout, NB, n_rows);

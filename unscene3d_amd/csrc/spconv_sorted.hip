@@ -27,10 +27,7 @@ void launch_group_reduce(const float* partial, int G, int64_t numel4, int cout, 
 namespace {
 
 constexpr int kKeyBits = 12;
-#ifndef USC_SORT_ROWS
-#define USC_SORT_ROWS 2   /* rows per thread in the bucket-sort kernels (workgroup = 256 * USC_SORT_ROWS rows) */
-#endif
-constexpr int kSortRows = USC_SORT_ROWS;
+constexpr int kSortRows = 2;   // rows per thread in the bucket-sort kernels (workgroup = 256 * kSortRows rows)
 constexpr int kBins = 1 << kKeyBits;
 constexpr int kZeroFloats = 4096;
 __device__ float s_zero_row[kZeroFloats + 8];
@@ -269,9 +266,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) void gather_gemm_so
     stage_store(0);
   }
   __syncthreads();
-#ifdef USC_ABLATE_SORTED_LOOP   /* developer switch (tools/build_ablate.sh): prologue + epilogue only */
-  if (p.cin < 0)
-#endif
   while (k < 32) {
     // next step's coordinates
     int k2 = k, ch2 = ch + 1;
@@ -333,9 +327,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) void gather_gemm_so
 
   // ---- write the tile (rows scattered back through perm)
   if (tile >= ntiles) return;
-#ifdef USC_ABLATE_SORTED_STORE  /* developer switch: no tile write-back (one word, so that the accumulators stay live) */
-  if (p.cin > 0) { if (lane == 0 && acc[0][0] == 123.456f) p.out[0] = acc[NB - 1][15]; return; }
-#endif
   float* outp = p.out;
   if (p.G > 1) outp += (int64_t)blockIdx.z * p.n_out * cout;
   const bool direct = p.G == 1;
@@ -365,7 +356,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) void gather_gemm_so
 struct SortedPlan { int NB, WAVES, G; };
 
 // Tile width (NB blocks of 32 output columns per wave) and offset split (G partial-sum slices) of one launch.
-// Measured on the bench scene's 507 ... 40 421-row levels (tools/sorted_plan_sweep.py -> profiles/r02_sorted_plan.txt):
+// Measured on the bench scene's 507 ... 40 421-row levels (tools/sorted_plan_sweep.py at a0f1986 -> profiles/r02_sorted_plan.txt):
 // the tile width hardly matters at a given G; what matters is (a) enough waves that every SIMD holds two or three
 // (a lone wave runs its chain of matrix-core steps at ~60 %: nothing overlaps its barriers and LDS reads) against
 // (b) one more [n_out, cout] slice written and read back per extra G.  (a) wins up to ~2 waves per SIMD on the
@@ -376,17 +367,6 @@ SortedPlan plan_sorted(int64_t n_out, int cin, int cout, int K) {
   if (cb % 4 == 0) nb = 4;
   else if (cb % 3 == 0) nb = 3;
   else if (cb % 2 == 0) nb = 2;
-  // USC3D_SORTED_TUNE=1: tools/sorted_plan_sweep.py forces (NB, G) per launch through the environment
-  static const bool tune = getenv("USC3D_SORTED_TUNE") != nullptr;
-  if (tune) {
-    const char* e_nb = getenv("USC3D_SORTED_NB");
-    const char* e_g = getenv("USC3D_SORTED_G");
-    const int f_nb = e_nb ? atoi(e_nb) : 0, f_g = e_g ? atoi(e_g) : 0;
-    if (f_nb >= 1 && f_nb <= 4 && cb % f_nb == 0 && f_g >= 1) {
-      const int64_t Kg = ceil_div((int64_t)K, (int64_t)(f_g < K ? f_g : K));
-      return SortedPlan{f_nb, f_nb == 4 ? 4 : 8, (int)ceil_div((int64_t)K, Kg)};
-    }
-  }
   SortedPlan pl{nb, nb == 4 ? 4 : 8, 1};
   const int64_t ntiles = ceil_div(n_out, 32);
   const int64_t waves = ntiles * (cb / nb);

@@ -85,20 +85,12 @@ int table_gemm(const usc_kmap* m, const int32_t* nbr, const float* in, int64_t n
   return usc_spconv_gather_gemm(in, n_in, cin, W, K, cout, nbr, n_out, bias, out, accumulate, wt, w, b, s);
 }
 
-// ---- fork/join of the weight gradient onto a side stream --------------------------------------------------------
+// ---- the weight-gradient lane -----------------------------------------------------------------------------------
 // The input-gradient and the weight-gradient kernels of one convolution are independent.  On the coarse levels of
 // the U-Net (hundreds to a few thousand rows) both are latency-bound launches that occupy a fraction of the 256 CUs,
-// so running them side by side costs about as much as the longer of the two.  The side stream is the CALLER's
-// (usc_set_side_stream); the fork and the join are events inside the one call, so nothing outlives it: when the
-// call returns, everything it queued is ordered before whatever the caller queues next on its stream.
-struct SideStream { hipStream_t st = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
-SideStream g_side[16];
-constexpr int64_t kForkMaxRows = 24576;   // larger maps fill the chip on their own (and the tile-compacted kernel
-                                          // sizes its tiles for whole rounds of 256 CUs)
-
-// ---- the weight-gradient lane -----------------------------------------------------------------------------------
-// The join of the fork above put the caller's stream behind the side stream once per convolution, and that cost more
-// than the overlap returned.  The lane never joins inside a call: the weight gradient of a small map is queued on the
+// so running them side by side costs about as much as the longer of the two.  A fork onto a side stream joined inside
+// each call (measured and removed) put the caller's stream behind the side stream once per convolution, and that cost
+// more than the overlap returned.  The lane never joins inside a call: the weight gradient of a small map is queued on the
 // lane stream behind ONE event of the caller's stream (everything it reads is ready at that point) and the call
 // returns; the input-gradient chain — the critical path of the backward pass — carries on, and the latency-bound
 // weight-gradient launches of the coarse levels fill the CUs it leaves idle.  The caller joins once, when the
@@ -136,12 +128,6 @@ int lane_release(Lane* lane, usc_stream_t s) {
   }
   lane->held.clear();
   return rc;
-}
-
-SideStream* side_for_current_device() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  return g_side[dev].st ? &g_side[dev] : nullptr;
 }
 
 struct ConvShape { int64_t n_in, n_out; };   // rows of the convolution's input / output feature matrices
@@ -228,28 +214,6 @@ int flush_deferred(DeferredWgrads& q, void* ws, int64_t ws_bytes, usc_stream_t s
 }  // namespace
 
 extern "C" {
-
-int usc_set_side_stream(usc_stream_t side) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) {
-    set_error("usc_set_side_stream: unsupported device index");
-    return USC_ERR_ARG;
-  }
-  SideStream& e = g_side[dev];
-  if (!side) {
-    e.st = nullptr;
-    return USC_OK;
-  }
-  if (!e.fork) {
-    if (hipEventCreateWithFlags(&e.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&e.join, hipEventDisableTiming) != hipSuccess) {
-      set_error("usc_set_side_stream: hipEventCreate failed");
-      return USC_ERR_LAUNCH;
-    }
-  }
-  e.st = as_stream(side);
-  return USC_OK;
-}
 
 int usc_set_wgrad_lane(usc_stream_t lane, void* lane_ws, int64_t lane_ws_bytes, int64_t max_rows) {
   int dev = 0;
@@ -417,10 +381,7 @@ static int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, i
     Lane* lane = lane_for_current_device();
     const int64_t rows = m->nbr ? m->pair_capacity : sh.n_in;
     const int64_t b = usc_spconv_wgrad_ws_bytes_rows(K, cin, cout, rows);
-    // USC3D_WGRAD_LANE_MIN_ROWS (experiment knob): only maps with at least that many rows go to the lane — the
-    // throughput-bound weight gradients of the fine levels, queued to run beside the latency-bound coarse-level chain
-    static const int64_t lane_min_rows = getenv("USC3D_WGRAD_LANE_MIN_ROWS") ? atoll(getenv("USC3D_WGRAD_LANE_MIN_ROWS")) : 0;
-    const bool lane_ok = lane && sh.n_in > 0 && sh.n_in >= lane_min_rows && sh.n_in <= lane->max_rows && sh.n_out <= lane->max_rows &&
+    const bool lane_ok = lane && sh.n_in > 0 && sh.n_in <= lane->max_rows && sh.n_out <= lane->max_rows &&
                          b <= lane->ws_bytes && (!m->nbr || (m->pair_in && m->pair_out && m->koff));
     const int64_t big = sh.n_in > sh.n_out ? sh.n_in : sh.n_out;
     // the chain has reached a map too small to fill the chip: what was held runs beside it from here on
@@ -441,9 +402,8 @@ static int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, i
       // the stem (3 -> 32 channels) keeps its table-form kernel on the lane too: it is the LAST weight gradient of the
       // backward pass — the lane's tail, which the step waits for — and the pair-list kernel needs 110 us for it, the table
       // form 57 (round 6: the lane branch used to send everything through usc_spconv_wgrad)
-      static const bool stem_table = !getenv("USC3D_STEM_KERNEL") || atoi(getenv("USC3D_STEM_KERNEL")) != 0;
       const int64_t bt = usc_spconv_wgrad_table_ws_bytes(K, cin, cout);
-      if (stem_table && kind == USC_CONV_SAME && m->nbr && cin <= 4 && cout == 32 && K <= 32 && bt <= lane->ws_bytes)
+      if (kind == USC_CONV_SAME && m->nbr && cin <= 4 && cout == 32 && K <= 32 && bt <= lane->ws_bytes)
         rc = usc_spconv_wgrad_table(x, cin, dy, cout, m->nbr, K, sh.n_out, dW, 1, lane->ws, bt, ls);
       else if (!m->nbr)
         rc = usc_spconv_wgrad(x, cin, dy, cout, 1, nullptr, nullptr, nullptr, sh.n_in, dW, 1, lane->ws, b, ls);
@@ -455,32 +415,17 @@ static int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, i
       dW = nullptr;          // done (queued); the rest of this call is the input gradient on the caller's stream
     }
   }
-  // fork: the weight gradient on the side stream while this stream runs the input gradient
-  SideStream* side = (dx && dW && sh.n_in > 0 && sh.n_in <= kForkMaxRows && sh.n_out <= kForkMaxRows) ? side_for_current_device() : nullptr;
-  hipStream_t wst = as_stream(s);
   int64_t dgrad_bytes = 0;
   // slices may stay behind only when the consumer can take them (tile-form batch norm on the input map) and nothing in
   // this call overwrites them: the weight gradient then takes its scratch behind the input gradient's region
   Slices left;
-  const bool may_defer = out && dx && !side && tile_rows_ok(sh.n_in, cin);
+  const bool may_defer = out && dx && tile_rows_ok(sh.n_in, cin);
   if (may_defer) {
     int64_t f_, w_;
     conv_ws_parts(m, kind, cin, cout, &f_, &dgrad_bytes, &w_);
     if (dgrad_bytes + w_ > cur.bytes) dgrad_bytes = 0;
   }
   Slices* want = (may_defer && dgrad_bytes > 0) ? &left : nullptr;
-  if (side) {
-    // disjoint scratch: [0, dgrad_bytes) for this stream, the rest for the side stream
-    int64_t f_, w_;
-    conv_ws_parts(m, kind, cin, cout, &f_, &dgrad_bytes, &w_);
-    if (dgrad_bytes + w_ > cur.bytes || hipEventRecord(side->fork, as_stream(s)) != hipSuccess ||
-        hipStreamWaitEvent(side->st, side->fork, 0) != hipSuccess) {
-      side = nullptr;
-      dgrad_bytes = 0;
-    } else {
-      wst = side->st;
-    }
-  }
   if (dx && sh.n_in > 0) {
     if (kind == USC_CONV_SAME) {
       // stride-1 map: the mirrored offset reaches the rows that read row i; transpose folded where the kernel can
@@ -502,33 +447,25 @@ static int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, i
     if (!rc && left.G > 0) {
       out->dx = dx; out->partial = left.partial; out->G = left.G; out->n = sh.n_in; out->c = cin; out->accumulate = dx_accumulate;
     }
-    if (rc) dW = nullptr;   // skip the weight gradient, still join below
+    if (rc) dW = nullptr;   // skip the weight gradient
   }
   if (dW) {
-    // same stream: the weight gradient reuses the scratch from the start (stream order); forked: its own region
-    WsCursor wc{(char*)ws, ws ? ws_bytes : 0, (side || left.G > 0) ? dgrad_bytes : 0};
+    // the weight gradient reuses the scratch from the start (stream order), or takes it behind the slices left above
+    WsCursor wc{(char*)ws, ws ? ws_bytes : 0, left.G > 0 ? dgrad_bytes : 0};
     const int64_t rows = m->nbr ? m->pair_capacity : sh.n_in;
     const int64_t b = usc_spconv_wgrad_ws_bytes_rows(K, cin, cout, rows);
     void* w = wc.take(b);
     if (!w) set_error("usc_conv_backward: workspace too small (weight gradient)");
-    usc_stream_t ws_stream = (usc_stream_t)wst;
-    static const bool stem_table = !getenv("USC3D_STEM_KERNEL") || atoi(getenv("USC3D_STEM_KERNEL")) != 0;
     const int64_t bt = usc_spconv_wgrad_table_ws_bytes(K, cin, cout);
     if (!w) rc = USC_ERR_ARG;
-    else if (stem_table && kind == USC_CONV_SAME && m->nbr && cin <= 4 && cout == 32 && K <= 32 && (char*)w + bt <= (char*)ws + ws_bytes)
-      rc = usc_spconv_wgrad_table(x, cin, dy, cout, m->nbr, K, sh.n_out, dW, dW_accumulate, w, bt, ws_stream);
+    else if (kind == USC_CONV_SAME && m->nbr && cin <= 4 && cout == 32 && K <= 32 && (char*)w + bt <= (char*)ws + ws_bytes)
+      rc = usc_spconv_wgrad_table(x, cin, dy, cout, m->nbr, K, sh.n_out, dW, dW_accumulate, w, bt, s);
     else if (!m->nbr)
-      rc = usc_spconv_wgrad(x, cin, dy, cout, 1, nullptr, nullptr, nullptr, sh.n_in, dW, dW_accumulate, w, b, ws_stream);
+      rc = usc_spconv_wgrad(x, cin, dy, cout, 1, nullptr, nullptr, nullptr, sh.n_in, dW, dW_accumulate, w, b, s);
     else if (kind == USC_CONV_UP)
-      rc = usc_spconv_wgrad(x, cin, dy, cout, K, m->pair_out, m->pair_in, m->koff, rows, dW, dW_accumulate, w, b, ws_stream);
+      rc = usc_spconv_wgrad(x, cin, dy, cout, K, m->pair_out, m->pair_in, m->koff, rows, dW, dW_accumulate, w, b, s);
     else
-      rc = usc_spconv_wgrad(x, cin, dy, cout, K, m->pair_in, m->pair_out, m->koff, rows, dW, dW_accumulate, w, b, ws_stream);
-  }
-  if (side) {   // join (also on an error above: the caller's stream must not run ahead of the side stream)
-    if (hipEventRecord(side->join, side->st) != hipSuccess || hipStreamWaitEvent(as_stream(s), side->join, 0) != hipSuccess) {
-      set_error("usc_conv_backward: joining the side stream failed");
-      return USC_ERR_LAUNCH;
-    }
+      rc = usc_spconv_wgrad(x, cin, dy, cout, K, m->pair_in, m->pair_out, m->koff, rows, dW, dW_accumulate, w, b, s);
   }
   return rc;
 }

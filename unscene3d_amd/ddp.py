@@ -7,8 +7,6 @@ while the backbone's backward is still running (`BucketedGradReducer`).  xGMI ri
 per-link bound: few, large collectives."""
 from __future__ import annotations
 
-import os
-
 import torch
 
 
@@ -34,19 +32,13 @@ def all_reduce_mean_(flat, world_size: int):
     return flat
 
 
-# USC3D_LANE_ORDERED_COLLECTIVES=0: the round-5 behaviour (the compute stream waits for the lane before every bucket)
-LANE_ORDERED_COLLECTIVES = os.environ.get("USC3D_LANE_ORDERED_COLLECTIVES", "1") == "1"
-# USC3D_EARLY_BUCKETS=0 (diagnostic): the reducer counts the reports but starts every bucket in finish()
-_EARLY_BUCKETS = os.environ.get("USC3D_EARLY_BUCKETS", "1") == "1"
-
-
 class BucketedGradReducer:
     """Overlaps the gradient all-reduce with backward.
 
     The flat buffer is cut into contiguous buckets of ~`bucket_bytes` (24 MB: large enough for the xGMI rings, small
     enough that the bucket mixing backbone and decoder parameters — reduced after backward — stays small) in parameter
     order.  The backward kernels of this
-    package write parameter gradients straight into `p.grad` (ops.GRAD_IN_PLACE) and report each write through
+    package write parameter gradients straight into `p.grad` (ops._grad_target) and report each write through
     `ops.GRAD_WRITTEN_HOOK`; parameters that still go through autograd report through a post-accumulate hook.  The
     first step only LEARNS how many reports each parameter produces per step (shared decoder weights are written by
     twelve passes — eager kernels and graph replays (graphs.py) both report); from the second step on a bucket whose parameters all
@@ -111,7 +103,7 @@ class BucketedGradReducer:
             if self.launched and self.launched[self.bucket_of[id(param)]]:
                 self._late = True        # the kernels of this write race with the bucket's collective already in flight
             from . import ops
-            if _EARLY_BUCKETS and not (self.flat.is_cuda and ops.on_side_stream()):
+            if not (self.flat.is_cuda and ops.on_side_stream()):
                 # (a report from the decoder's key-preparation stream only counts: a collective started here would be
                 # ordered behind THAT stream alone; the next report on the compute stream, or finish(), starts it)
                 self._advance()
@@ -147,7 +139,7 @@ class BucketedGradReducer:
             # until finish().
             from . import ops, units
             ops.join_side_streams()          # (the decoder's key-preparation stream writes lin_squeeze / in_proj gradients)
-            cs = self._collective_stream() if LANE_ORDERED_COLLECTIVES else None
+            cs = self._collective_stream()
             if cs is not None:
                 cur = torch.cuda.current_stream()
                 lane_ev = units.lane_event(self.flat.device)          # (releases weight gradients the lane still holds)

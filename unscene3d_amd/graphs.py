@@ -13,8 +13,6 @@ does not change after capture — use `optimizer.zero_grad(set_to_none=False)` (
 """
 from __future__ import annotations
 
-import os
-
 import torch
 
 # "thread_local": other threads of the process (the RCCL watchdog polls events while a multi-GPU job captures) may
@@ -68,7 +66,6 @@ class _Runner:
 # here and writes straight into the buffer: no copy in front of the backward replay (12 per training step).
 _GRAD_OUT_BUFFERS = {}
 STATS = {"grad_buffer_hits": 0, "grad_out_copies": 0}      # counted per backward replay (tests; tools)
-_GRAD_BUFFER_PASSTHROUGH = os.environ.get("USC3D_GRAD_BUFFER_PASSTHROUGH", "1") == "1"
 
 
 def grad_buffer_for(t):
@@ -76,8 +73,6 @@ def grad_buffer_for(t):
     order as the pass output), or None.  `t` may be any contiguous VIEW of the output (the LayerNorm works on
     [rows, d]): what has to agree is the element count, the dtype and that both are dense in the same order — a
     buffer with permuted strides (several scenes per batch) is not handed out."""
-    if not _GRAD_BUFFER_PASSTHROUGH:
-        return None
     hit = _GRAD_OUT_BUFFERS.get((t.device.index, t.data_ptr()))
     if (hit is None or hit.numel() != t.numel() or hit.dtype != t.dtype or not hit.is_contiguous()
             or not t.is_contiguous()):

@@ -26,15 +26,6 @@ from .modules.helpers_3detr import GenericMLP
 from .position_embedding import PositionEmbeddingCoordsSine
 
 SINGLE_POINT_ERROR = "only a single point gives nans in cross-attention"   # trainer.py:125 string-matches this
-# the residual connection of a decoder block routed through the block's first projection node (one autograd add per
-# block and pass less: 36 launches per step)
-_RESIDUAL_IN_PROJECTION = os.environ.get("USC3D_RESIDUAL_IN_PROJECTION", "1") == "1"
-_PADDED_MASK_EMBED = os.environ.get("USC3D_PADDED_MASK_EMBED", "1") == "1"
-_LAZY_HOST_COPIES = os.environ.get("USC3D_LAZY_HOST_COPIES", "1") == "1"
-_FUSED_KEY_SAMPLING = os.environ.get("USC3D_FUSED_KEY_SAMPLING", "1") == "1"
-_GATHER_INTO_GRAPH_INPUTS = os.environ.get("USC3D_GATHER_INTO_GRAPH_INPUTS", "1") == "1"
-_GRAD_SINKS = os.environ.get("USC3D_GRAD_SINKS", "1") == "1"
-_LN_PASSTHROUGH = os.environ.get("USC3D_LN_PASSTHROUGH", "1") == "1"
 
 
 class Mask3D(nn.Module):
@@ -410,10 +401,10 @@ class Mask3D(nn.Module):
                             (curr_sample_size, n_scenes, d_model), (n_scenes, curr_sample_size, self.num_queries))
                     if tuple(tuple(h) for h in have) != tuple(tuple(w) for w in graph_shapes):
                         step_fn = self._eager_pass(dec, i)
-                    elif _GATHER_INTO_GRAPH_INPUTS and plan["gidx"] is not None:
+                    elif plan["gidx"] is not None:
                         bufs = step_fn.input_buffers    # keys / values / mask written straight into the captured pass's inputs
                 feats_l = aux[hlevel].F
-                fused = (_FUSED_KEY_SAMPLING and plan["gidx"] is not None and feats_l.is_cuda
+                fused = (plan["gidx"] is not None and feats_l.is_cuda
                          and feats_l.dtype == torch.float32 and n_scenes <= 16 and feats_l.shape[1] % 4 == 0
                          and self.num_queries <= 128)
 
@@ -434,7 +425,7 @@ class Mask3D(nn.Module):
                         batched_aux = ops.sample_keys(
                             feats_l.contiguous(), None, None, plan["gidx"], n_scenes, curr_sample_size, n_valid,
                             unique=plan["all_sampled"], valid_unique=True,       # (the plan's keys: distinct rows, then masked padding)
-                            sink=sinks.setdefault((hlevel, bool(plan["all_sampled"])), ops.GradSink()) if _GRAD_SINKS else None)
+                            sink=sinks.setdefault((hlevel, bool(plan["all_sampled"])), ops.GradSink()))
                     else:
                         batched_aux = _stack([ops.gather_rows(decomposed_aux[k].contiguous(), rand_idx[k],
                                                               unique=sizes[k] > curr_sample_size) for k in range(n_scenes)])
@@ -498,7 +489,7 @@ class Mask3D(nn.Module):
         node: the gradient that comes back from the layer is then summed inside the norm's backward launch
         (ops.layer_norm(passthrough=True)) instead of by an autograd add per pass -> (normed, queries)."""
         norm = self.decoder_norm
-        if (_LN_PASSTHROUGH and queries.is_cuda and queries.dtype == torch.float32 and queries.requires_grad
+        if (queries.is_cuda and queries.dtype == torch.float32 and queries.requires_grad
                 and isinstance(norm, LayerNorm) and norm.elementwise_affine and norm.bias is not None
                 and len(norm.normalized_shape) == 1 and norm.normalized_shape[0] in ops._LN_DIMS):
             return ops.layer_norm(queries, norm.weight, norm.bias, norm.eps, passthrough=True)
@@ -511,13 +502,13 @@ class Mask3D(nn.Module):
         Q = query_feat.shape[-2]
         q_pad = (-Q) % 32
         if query_feat.is_cuda and query_feat.dtype == torch.float32:      # Linear + ReLU in one launch
-            if defer_class and _RESIDUAL_IN_PROJECTION and query_feat.requires_grad:
+            if defer_class and query_feat.requires_grad:
                 # the normalised queries feed the mask head AND the class head: routed through the first projection's
                 # node, the class head's gradient is summed inside that projection's input-gradient launch
                 hidden, query_feat = ops.linear(query_feat, head[0].weight, head[0].bias, relu=True, passthrough=True)
             else:
                 hidden = ops.linear(query_feat, head[0].weight, head[0].bias, relu=True)
-            if (q_pad and _PADDED_MASK_EMBED and query_feat.dim() == 3 and query_feat.shape[0] == 1
+            if (q_pad and query_feat.dim() == 3 and query_feat.shape[0] == 1
                     and isinstance(head[2], Linear) and head[2].out_features % 32 == 0):
                 # one scene: the embeddings come out zero-extended to a multiple of 32 rows (what the logits product
                 # below wants) from the launch that computes them
@@ -539,10 +530,7 @@ class Mask3D(nn.Module):
             # one applies sigmoid < 0.5 (reference :418-436).  Several scenes: the segment tables are stacked and the
             # row index carries each scene's segment offset (the voxel rows of a batch are one table already).
             for i, seg_feat in enumerate(mask_segments):
-                if _CHAIN_SEGMENT_GRADS:
-                    logits, mask_segments[i] = _mask_logits(seg_feat, mask_embed[i], chain=True)   # (the caller's list)
-                else:
-                    logits = _mask_logits(seg_feat, mask_embed[i])
+                logits, mask_segments[i] = _mask_logits(seg_feat, mask_embed[i], chain=True)   # (the caller's list)
                 output_segments.append(logits)
             cm, ts = mask_features.coordinate_manager, mask_features._ts()
             if len(output_segments) == 1:
@@ -637,7 +625,7 @@ class HostArrayLater:
 
 
 def _host_array(t):
-    if t.is_cuda and _LAZY_HOST_COPIES:
+    if t.is_cuda:
         return HostArrayLater(t)
     return t.detach().cpu().numpy()
 
@@ -809,7 +797,6 @@ def set_kv_side_stream(on: bool):
         torch.cuda.synchronize()
     _KV_SIDE_STREAM = bool(on)
 _FUSED_ATTN_MASK = os.environ.get("USC3D_FUSED_ATTN_MASK", "1") != "0"
-_CHAIN_SEGMENT_GRADS = os.environ.get("USC3D_CHAIN_SEGMENT_GRADS", "1") != "0"
 
 
 _PAD_CACHE = {}
@@ -904,7 +891,7 @@ class SelfAttentionLayer(nn.Module):
         # need_weights=False: same output; skips materialising/averaging the [B,Q,K] attention weights the
         # reference computes and discards (`[0]`), and lets PyTorch take its fused SDPA path
         if tgt_key_padding_mask is None and self.self_attn.dropout == 0.0 and src.is_cuda:
-            if not self.normalize_before and _RESIDUAL_IN_PROJECTION:
+            if not self.normalize_before:
                 upd, tgt = multihead_attention(self.self_attn, src, src, src, attn_mask=tgt_mask, pos_q=query_pos,
                                                pos_k=query_pos, residual=True)
             else:
@@ -937,7 +924,7 @@ class CrossAttentionLayer(nn.Module):
         if memory_mask is None and memory_mask_bsl is not None and not src.is_cuda:
             memory_mask = memory_mask_bsl.repeat_interleave(self.multihead_attn.num_heads, dim=0).permute(0, 2, 1)
         if memory_key_padding_mask is None and self.multihead_attn.dropout == 0.0 and src.is_cuda:
-            if not self.normalize_before and _RESIDUAL_IN_PROJECTION:
+            if not self.normalize_before:
                 upd, tgt = multihead_attention(self.multihead_attn, src, memory, memory, attn_mask=memory_mask,
                                                mask_bsl=memory_mask_bsl, pos_q=query_pos, pos_k=pos, residual=True)
             else:
@@ -976,7 +963,7 @@ def _cross_forward_kv(self, tgt, k, v, mask_bsl, query_pos):
     W, b = mha.in_proj_weight, mha.in_proj_bias
     E = src.shape[-1]
     if src.is_cuda and src.dtype == torch.float32:
-        if not self.normalize_before and _RESIDUAL_IN_PROJECTION and (mha.dropout == 0.0 or not self.training):
+        if not self.normalize_before and (mha.dropout == 0.0 or not self.training):
             q, tgt = ops.in_proj_q(src, W, b, pos=query_pos, residual=True)
         else:
             q = ops.in_proj_q(src, W, b, pos=query_pos)
@@ -1006,7 +993,7 @@ class FFNLayer(nn.Module):
         src = self.norm(tgt) if self.normalize_before else tgt
         if src.is_cuda and src.dtype == torch.float32 and self.activation is F.relu and (self.dropout.p == 0.0
                                                                                           or not self.training):
-            if not self.normalize_before and _RESIDUAL_IN_PROJECTION:
+            if not self.normalize_before:
                 # ReLU in the same launch; `tgt` comes back through the layer's node: the residual's gradient is summed
                 # inside linear1's input-gradient launch
                 hidden, tgt = ops.linear(src, self.linear1.weight, self.linear1.bias, relu=True, passthrough=True)

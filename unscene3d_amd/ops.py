@@ -315,8 +315,7 @@ def pairs_gemm(feats, W, rows_in, rows_out, koff, P, n_out):
 # Parameter gradients straight into `p.grad`: when a leaf parameter already has a gradient buffer (the trainer
 # keeps them allocated: zero_grad(set_to_none=False), one flat buffer for the all-reduce), the backward kernels add
 # into it and the Function returns None, instead of returning a fresh tensor that autograd's AccumulateGrad then
-# adds with one more small kernel per parameter (~250 launches per step for the backbone).
-GRAD_IN_PLACE = os.environ.get("USC3D_GRAD_IN_PLACE", "1") == "1"
+# adds with one more small kernel per parameter (~250 launches per step for the backbone).  See _grad_target.
 
 
 # streams other than the compute stream that backward kernels of this package write parameter gradients on (the decoder's
@@ -347,7 +346,7 @@ def _grad_target(param):
     autograd).  Never when somebody else listens for the gradient through autograd: tensor hooks, or
     post-accumulate hooks (torch DDP, FSDP, user hooks) unless they belong to this package's own reducer, which is
     told about in-place writes through GRAD_WRITTEN_HOOK."""
-    if GRAD_IN_PLACE and isinstance(param, torch.nn.Parameter) and param.is_leaf and param.grad is not None \
+    if isinstance(param, torch.nn.Parameter) and param.is_leaf and param.grad is not None \
             and param.grad.is_contiguous() and not param._backward_hooks \
             and (GRAD_WRITTEN_HOOK is not None or not getattr(param, "_post_accumulate_grad_hooks", None)):
         return param.grad
@@ -403,9 +402,6 @@ def _grad_written(*params):
                 GRAD_WRITTEN_HOOK(p)
 
 
-STEM_KERNEL = os.environ.get("USC3D_STEM_KERNEL", "1") != "0"
-
-
 def wgrad(a, b, K, a_idx=None, b_idx=None, koff=None, into=None, out=None, nbr=None):
     """dW[k] = sum_{p in list k} a[a_idx[p]]^T b[b_idx[p]] -> f32[K,cin,cout]; ADDED into `into`, or WRITTEN to `out`
     (a contiguous buffer of K*cin*cout floats), when given.
@@ -416,7 +412,7 @@ def wgrad(a, b, K, a_idx=None, b_idx=None, koff=None, into=None, out=None, nbr=N
     cin, cout = a.shape[1], b.shape[1]
     dW = into if into is not None else (out if out is not None else
                                         torch.empty((K, cin, cout), dtype=torch.float32, device=a.device))
-    if STEM_KERNEL and nbr is not None and cin <= 4 and cout == 32 and K <= 32 and nbr.shape == (K, b.shape[0]):
+    if nbr is not None and cin <= 4 and cout == 32 and K <= 32 and nbr.shape == (K, b.shape[0]):
         wsb = lib.usc_spconv_wgrad_table_ws_bytes(K, cin, cout)
         ws = _ws(wsb, a.device)
         with _prof.maybe(lambda: "usc::stem_wgrad_kernel" + (f" [n={b.shape[0]} cin={cin} cout={cout} K={K}]" if _prof.SHAPES else ""),
@@ -1262,9 +1258,6 @@ def linear(x, W, b=None, relu=False, passthrough=False, pad_rows_to=None):
     return _LinearRows.apply(x, W, b, relu, passthrough, pad_rows_to)
 
 
-FUSED_QKV = os.environ.get("USC3D_FUSED_QKV", "1") == "1"
-
-
 class _InProj(torch.autograd.Function):
     """q, k, v = the three input projections of nn.MultiheadAttention from its packed in_proj_weight [3E,E] /
     in_proj_bias [3E] (reference: nn.MultiheadAttention inside models/mask3d.py:491-605).  One Function so that the
@@ -1284,7 +1277,7 @@ class _InProj(torch.autograd.Function):
                 xs[j], ps[j] = xs[j] + ps[j], None
         def same_t(a, c):
             return a.data_ptr() == c.data_ptr() and a.shape == c.shape
-        if (FUSED_QKV and same_t(xs[0], xs[1]) and same_t(xs[1], xs[2]) and _small_linear_ok(xs[0].shape[0], E, 3 * E)
+        if (same_t(xs[0], xs[1]) and same_t(xs[1], xs[2]) and _small_linear_ok(xs[0].shape[0], E, 3 * E)
                 and W.is_contiguous() and (ps[0] is None) == (ps[1] is None)
                 and (ps[0] is None or same_t(ps[0], ps[1]))):
             # self attention: one launch for the three projections of the one input ([3, M, E], each its own matrix)
@@ -1334,7 +1327,7 @@ class _InProj(torch.autograd.Function):
         M = x0.shape[0]
         adjacent = (dq.is_contiguous() and dk.is_contiguous() and dv.is_contiguous()
                     and dk.data_ptr() == dq.data_ptr() + 4 * M * E and dv.data_ptr() == dk.data_ptr() + 4 * M * E)
-        if (FUSED_QKV and ctx.same_qk and ctx.same_kv and ctx.same_pos and need[0] and adjacent and W.is_contiguous()
+        if (ctx.same_qk and ctx.same_kv and ctx.same_pos and need[0] and adjacent and W.is_contiguous()
                 and _small_linear_ok(M, 3 * E, E) and dW.is_contiguous() and db.is_contiguous()):
             # self attention: the three projections backwards in one launch (usc_qkv_proj_bwd)
             gx = torch.empty((M, E), dtype=torch.float32, device=W.device)

@@ -15,8 +15,8 @@ SURVEY.md §8e: scenes are independent, so the path scales by REPLICAS — no co
   rebuild of the neighbour sets, and the scenes share one thread.)  Measured on the 625-segment bench scene
   (`bench.py --mode ncut --scenes K`): 8.1 scenes/s with one scene in flight (eigen-solve bound: 5.6 ms x 20
   iterations), 11.1 / 14.5 / 16.1 / 21.0 / 23.5 / 25.0 / 26.7 with 2 / 3 / 4 / 6 / 12 / 16 / 24.  A solve's 64 workgroups hold
-  only 20 KB of LDS each, so the solves of many scenes share the CUs; smaller grids per solve (USC3D_TRI_G = 48, 32)
-  were measured slower at every K.  Default: 16 in flight.
+  only 20 KB of LDS each, so the solves of many scenes share the CUs; smaller grids per solve (48 or 32
+  workgroups) were measured slower at every K.  Default: 16 in flight.
 """
 from __future__ import annotations
 

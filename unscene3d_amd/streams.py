@@ -21,7 +21,6 @@ No reference counterpart (the reference is single-stream PyTorch); used by datas
 """
 from __future__ import annotations
 
-import os
 import time
 
 import torch
@@ -72,7 +71,7 @@ def pick(device, role: str, beside=(), max_candidates: int = 8) -> torch.cuda.St
     key = (idx, role)
     if key in _PICKED:
         return _PICKED[key]
-    if os.environ.get("USC3D_STREAM_PROBE", "1") == "0" or torch.cuda.is_current_stream_capturing():
+    if torch.cuda.is_current_stream_capturing():
         st = torch.cuda.Stream(device=device)
         _PICKED[key] = st
         return st

@@ -24,10 +24,6 @@ from . import profiler as _prof
 from ._lib import BNDesc, KMap, check, lib
 
 ENABLED = os.environ.get("USC3D_NATIVE_UNITS", "1") == "1"
-# Weight gradients of the small maps forked onto a side stream (usc_set_side_stream).  Measured on the bench scene:
-# 37.3 ms per step without, 39.0 ms with (20 k voxels: 33.2 vs 35.8) — two event records and two stream waits per
-# unit cost the host and the device more than the overlap of two ~30 us launches returns.  Off by default.
-FORK_WGRAD = os.environ.get("USC3D_FORK_WGRAD", "0") == "1"
 # The weight-gradient lane (usc_set_wgrad_lane): weight gradients of maps up to LANE_MAX_ROWS rows are queued on a second
 # stream and joined ONCE, at the end of the backward pass (and before a gradient bucket goes to a collective) — the
 # input-gradient chain is not held up by them.  On for every map since round 5 (USC3D_WGRAD_LANE_MAX_ROWS=0 switches it
@@ -42,9 +38,9 @@ LANE_WS_BYTES = 192 << 20
 # The lane's schedule inside the step program's backward pass (usc_wgrad_lane_hold, round 6): weight gradients of maps
 # with >= LANE_HOLD_MIN_ROWS rows (the levels whose input gradients run on the tile-compacted kernel) are noted until
 # the walk reaches a map with <= LANE_RELEASE_ROWS rows and run beside the coarse levels' latency-bound chain instead
-# of beside the fine levels' input gradients.  USC3D_LANE_RELEASE_ROWS=0 switches the schedule off.
-LANE_HOLD_MIN_ROWS = int(os.environ.get("USC3D_LANE_HOLD_MIN_ROWS", "24576"))
-LANE_RELEASE_ROWS = int(os.environ.get("USC3D_LANE_RELEASE_ROWS", "3000"))
+# of beside the fine levels' input gradients.  LANE_RELEASE_ROWS = 0 switches the schedule off.
+LANE_HOLD_MIN_ROWS = 24576
+LANE_RELEASE_ROWS = 3000
 SAME, DOWN, UP = 0, 1, 2
 # Grouped weight gradients (usc_spconv_wgrad_group): the stride-1 convolutions of one level's residual blocks have the
 # same shape on the same kernel map; their weight gradients are off the backward pass's critical chain (nothing reads
@@ -54,47 +50,17 @@ SAME, DOWN, UP = 0, 1, 2
 # launch; eleven of them in one grid need neither (round-3 probe: 378 -> 197 us for the eleven 256 -> 256 problems of the
 # stride-16 level).  USC3D_GROUP_WGRAD=0 switches it off (A/B, and the bit-equality tests against the per-operator path).
 GROUP_WGRAD = os.environ.get("USC3D_GROUP_WGRAD", "1") == "1"
-_SIDE = {}     # device index -> torch.cuda.Stream handed to usc_set_side_stream
 _LANE = {}     # device index -> (stream, scratch tensor) handed to usc_set_wgrad_lane, or None
 _LANE_JOIN_QUEUED = {}     # device index -> id of the graph task whose end-of-backward lane join has been queued
-
-
-def _lane_stream(device):
-    """The lane's stream: plain, with a priority (USC3D_LANE_PRIORITY: torch's convention, lower = more urgent), or
-    restricted to a subset of the CUs (USC3D_LANE_CU_PATTERN=<hex word repeated over the 256-CU mask>, e.g. 55555555 =
-    every second CU) so that the main stream's latency-bound launches always find free CUs — experiment knobs."""
-    pat = os.environ.get("USC3D_LANE_CU_PATTERN")
-    if pat:
-        hip = C.CDLL("libamdhip64.so")
-        words = (C.c_uint32 * 8)(*([int(pat, 16) & 0xffffffff] * 8))
-        raw = C.c_void_p()
-        rc = hip.hipExtStreamCreateWithCUMask(C.byref(raw), 8, words)
-        if rc != 0 or not raw.value:
-            raise RuntimeError(f"hipExtStreamCreateWithCUMask failed ({rc})")
-        return torch.cuda.ExternalStream(raw.value, device=device)
-    pr = os.environ.get("USC3D_LANE_PRIORITY")
-    if pr == "low":
-        # HIP's lowest priority (torch offers normal and high only): the chain's kernels win every race for a free CU
-        hip = C.CDLL("libamdhip64.so")
-        lo, hi = C.c_int(), C.c_int()
-        hip.hipDeviceGetStreamPriorityRange(C.byref(lo), C.byref(hi))
-        raw = C.c_void_p()
-        rc = hip.hipStreamCreateWithPriority(C.byref(raw), 1, lo.value)          # 1 = hipStreamNonBlocking
-        if rc != 0 or not raw.value:
-            raise RuntimeError(f"hipStreamCreateWithPriority failed ({rc})")
-        return torch.cuda.ExternalStream(raw.value, device=device)
-    if pr is not None:
-        return torch.cuda.Stream(device=device, priority=int(pr))
-    from . import streams           # a stream measured to run beside the compute stream (streams.py)
-    return streams.pick(device, "wgrad-lane")
 
 
 def _lane(device):
     """(stream, scratch) of the device's weight-gradient lane, or None when it is switched off."""
     key = device.index if device.index is not None else torch.cuda.current_device()
     if key not in _LANE:
-        if LANE_MAX_ROWS > 0 and not FORK_WGRAD:
-            st = _lane_stream(device)
+        if LANE_MAX_ROWS > 0:
+            from . import streams           # a stream measured to run beside the compute stream (streams.py)
+            st = streams.pick(device, "wgrad-lane")
             ws = torch.empty(LANE_WS_BYTES, dtype=torch.uint8, device=device)
             check(lib.usc_set_wgrad_lane(st.cuda_stream, ws.data_ptr(), ws.numel(), LANE_MAX_ROWS), "usc_set_wgrad_lane")
             _LANE[key] = (st, ws)
@@ -187,19 +153,6 @@ def _lane_hold(device, n_in, n_out, in_place_dW, *tensors):
     key = device.index if device.index is not None else torch.cuda.current_device()
     queue_lane_join(key)
     return True
-
-
-def _ensure_side_stream(device):
-    """One side stream per device for the weight gradients of the small maps (csrc/units.hip: forked and joined inside
-    each backward call, so the caller's stream order — allocator, collectives, graph capture — is untouched)."""
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    if key not in _SIDE:
-        if FORK_WGRAD:
-            st = torch.cuda.Stream(device=device)
-            check(lib.usc_set_side_stream(st.cuda_stream), "usc_set_side_stream")
-            _SIDE[key] = st
-        else:
-            _SIDE[key] = None
 
 
 class KMapRef:
@@ -311,9 +264,8 @@ def flush_deferred_wgrads(device=None):
 
 def _defer_wgrad(kmap, kind, cin, cout, in_place):
     """May this unit's weight gradient go to the queue?  Stride-1 table convolutions on the coarse levels whose
-    gradient is added into p.grad in place, outside graph capture, lane and fork modes off."""
-    if not (GROUP_WGRAD and in_place and kind == SAME and kmap.K > 1 and kmap.struct.pair_in and not FORK_WGRAD
-            and LANE_MAX_ROWS == 0):
+    gradient is added into p.grad in place, outside graph capture, lane off."""
+    if not (GROUP_WGRAD and in_place and kind == SAME and kmap.K > 1 and kmap.struct.pair_in and LANE_MAX_ROWS == 0):
         return False
     return bool(lib.usc_spconv_wgrad_group_ok(2, cin, cout, kmap.K, kmap.struct.pair_capacity) or
                 lib.usc_spconv_wgrad_group_ok(_group_max(), cin, cout, kmap.K, kmap.struct.pair_capacity))
@@ -408,7 +360,6 @@ def unit_backward(x, W3, bn, kmap, kind, y, stats, out_relu, dout, dy_buf, want_
     if need_dx and dx is None:
         dx = torch.empty((n_in, cin), dtype=torch.float32, device=dev)
         dx_accumulate = False
-    _ensure_side_stream(dev)
     tW = ops._grad_target(W_param)
     _lane_hold(dev, n_in, n_out, tW is not None, x, dy_buf)
     tg, tb = ops._grad_target(g_param), ops._grad_target(b_param)
