@@ -1052,6 +1052,21 @@ int usc_felz_merge_host(const int32_t* edge_a, const int32_t* edge_b,
                         const float* weights, int64_t n_edges, int32_t n_vertices,
                         float kthr, int32_t seg_min_verts, int32_t* comps);
 
+/* ------------------------------------------------------------------------
+ * Validation AP — the mask / GT-instance overlap counts of the ScanNet instance
+ * evaluator (benchmark/evaluate_semantic_instance.py, assign_instances_for_scan*).
+ * masks u8[n, ld] row-major, nonzero = point in mask (np.not_equal(mask, 0));
+ * slot i32[n], each in [0, nslots): the GT instance slot of every point (the
+ * caller's last slot = void); counts i32[(k + 1) * nslots], written in full:
+ *   counts[j * nslots + s] = #points with masks[p, j] != 0 and slot[p] == s  (j < k)
+ *   counts[k * nslots + s] = #points with slot[p] == s                      (GT sizes)
+ * k in 1..4096, ld >= k, nslots in 1..65536, n in 0..2^31-1.  Exact integers:
+ * bit-identical from run to run.  One call per scene, no synchronisation.
+ * ---------------------------------------------------------------------- */
+int usc_mask_gt_overlap(const uint8_t* masks, int64_t n, int32_t k, int64_t ld,
+                        const int32_t* slot, int32_t nslots, int32_t* counts,
+                        usc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -973,6 +973,30 @@ def knn1(query: torch.Tensor, ref: torch.Tensor):
     return d2.sqrt(), idx
 
 
+def mask_gt_overlap(masks: torch.Tensor, slot: torch.Tensor, nslots: int) -> torch.Tensor:
+    """Point overlap of every mask column with every GT slot (the ScanNet instance evaluator's intersections):
+    masks bool/u8 [N,K] (rows may be strided: stride(0) >= K, stride(1) == 1), slot i32 [N] in [0, nslots)
+    -> i32 [K+1, nslots]: row j < K = #points of column j in each slot, row K = #points in each slot."""
+    require_device()
+    if not isinstance(masks, torch.Tensor) or masks.dim() != 2 or not masks.is_cuda:
+        raise RuntimeError("masks must be a 2-D HIP (cuda) tensor")
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    if masks.dtype != torch.uint8:
+        raise RuntimeError(f"masks must be bool or uint8, got {masks.dtype}")
+    n, k = masks.shape
+    if n > 0 and (masks.stride(1) != 1 or masks.stride(0) < k):
+        masks = masks.contiguous()
+    ld = masks.stride(0) if n > 0 else k
+    _chk(slot, torch.int32, "slot")
+    if slot.shape != (n,):
+        raise RuntimeError(f"slot must be [{n}], got {list(slot.shape)}")
+    counts = torch.empty((k + 1, int(nslots)), dtype=torch.int32, device=masks.device)
+    check(lib.usc_mask_gt_overlap(_ptr(masks), n, k, ld, _ptr(slot), int(nslots), _ptr(counts), _stream()),
+          "usc_mask_gt_overlap")
+    return counts
+
+
 def cc_eps(xyz: torch.Tensor, eps: float, max_rounds: int = 256) -> torch.Tensor:
     """Connected components of the eps-ball graph == DBSCAN(eps, min_samples=1).labels_ (first-seen order)."""
     require_device()

@@ -6,12 +6,16 @@ PyTorch-Lightning / hydra (neither is part of the accelerated path).  Difference
 on the device and synchronised once per step (the reference does 52 `.cpu().item()` calls, :149)."""
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import MinkowskiEngine as ME
 from ..config import instantiate_model
+from ..evaluation import (FREEMASK, InstanceAPEvaluator, gt_boxes, load_gt_ids, pred_box_list,
+                          validation_results)
 from ..models.criterion import SetCriterion
 from ..models.mask3d import SINGLE_POINT_ERROR
 from ..models.matcher import HungarianMatcher
@@ -233,6 +237,51 @@ class InstanceSegmentation(nn.Module):
         if sc is not None and not isinstance(sc, np.ndarray):       # the reference hands back a numpy array (mask3d.py:467)
             output["sampled_coords"] = np.asarray(sc)
         return {"losses": val, "instances": instances, "output": output}
+
+    # ---------------------------------------------------------------- validation metrics (reference :785-931)
+    def begin_validation(self, class_set=FREEMASK, gt_dir=None, gt_ids=None):
+        """Start a validation pass.  class_set: evaluation.ClassSet (default FREEMASK, `dataset="freemask"`).  GT ids
+        of a scene (label * 1000 + instance per full-resolution point) come from gt_ids[name] or from
+        `<gt_dir>/<name>.txt` (the reference's instance_gt/<split>/ files); either is read once per scene name."""
+        old = getattr(self, "_val", None)
+        cs = class_set
+        ev = old["evaluator"] if old is not None and old["evaluator"].class_set == cs else InstanceAPEvaluator(cs)
+        ev.reset()
+        self._val = {"evaluator": ev, "gt_dir": gt_dir, "gt_ids": dict(gt_ids or {}), "bbox_preds": {}, "bbox_gt": {}}
+
+    def validation_step(self, batch, batch_idx=0, label_offset=0):
+        """eval_step, then every scene's predictions go to the mask AP (one device histogram per scene) and box AP
+        evaluators.  -> eval_step's result, unchanged."""
+        if getattr(self, "_val", None) is None:
+            self.begin_validation()
+        res = self.eval_step(batch, batch_idx, label_offset)
+        if res is None:
+            return None
+        v = self._val
+        data, _, names = batch
+        labelled = getattr(self.config.data, "test_mode", "validation") != "test" and len(data.target_full) != 0
+        for b, (name, inst) in enumerate(zip(names, res["instances"])):
+            ids = v["gt_ids"].get(name)
+            if ids is None and not v["evaluator"].has_gt(name):
+                if v["gt_dir"] is None:
+                    raise KeyError(f"validation_step: no GT ids for scene {name!r} (begin_validation(gt_dir=|gt_ids=))")
+                ids = load_gt_ids(os.path.join(v["gt_dir"], f"{name}.txt"))
+            v["evaluator"].add_scene(name, inst, gt_ids=ids)
+            if labelled:
+                v["bbox_preds"][name] = pred_box_list(inst["pred_boxes"])
+                v["bbox_gt"][name] = gt_boxes(data.target_full[b], data.full_res_coords[b], label_offset)
+        return res
+
+    def validation_epoch_end(self, prefix="val") -> dict:
+        """-> the dict the reference's eval_instance_epoch_end logs ({} when the box evaluation has no class), and
+        clears the pass's predictions (cached GT stays)."""
+        v = getattr(self, "_val", None)
+        if v is None:
+            return {}
+        out = validation_results(v["evaluator"], v["bbox_preds"], v["bbox_gt"], prefix=prefix)
+        v["evaluator"].reset()
+        v["bbox_preds"], v["bbox_gt"] = {}, {}
+        return out
 
     def configure_optimizers(self, steps_per_epoch: int, epochs: int = None):
         o = self.config.optimizer
