@@ -237,6 +237,43 @@ int usc_spconv_pairs_gemm(const float* in, int32_t cin, const float* W,
                           const int32_t* rows_out, const int64_t* koff,
                           int64_t P_capacity, float* out, usc_stream_t s);
 
+/* ------------------------------------------------------------------------
+ * bf16 matrix-core forward convolution (opt-in inference precision,
+ * unscene3d_amd.inference_precision("bf16")): bf16 operands on
+ * v_mfma_f32_32x32x16_bf16, f32 accumulation, f32 output.  Replaces the
+ * forward of MinkowskiConvolution / MinkowskiConvolutionTranspose
+ * (ME 0.5.4 src/convolution_kernel.cu; models/res16unet.py:224-297) only
+ * under that opt-in; training always runs the f32 kernels above.
+ * ---------------------------------------------------------------------- */
+/* out[i] = bf16(in[i]), round to nearest even (NaN stays NaN); in 16-byte,
+ * out 8-byte aligned.  The activation copy the bf16 conv gathers from
+ * (replaces the input read of the ME forward conv). */
+int usc_cast_bf16(const float* in, int64_t n, uint16_t* out, usc_stream_t s);
+/* Weights f32[K,cin,cout] -> bf16 in B-fragment order,
+ * Wp[k][cin/16][cout/32][64][8] with Wp[k][s][t][l][j] = W[k][16s + 8(l>>5) + j][32t + (l&31)]
+ * (K*cin*cout bf16 values; cin a multiple of 16, cout of 32).  Replaces ME's
+ * kernel parameter as the forward conv reads it. */
+int usc_spconv_pack_w_bf16(const float* W, int32_t K, int32_t cin, int32_t cout,
+                           uint16_t* Wp, usc_stream_t s);
+/* Scratch bytes usc_spconv_gather_gemm_bf16 needs for a shape (0: none), or
+ * -1 when the shape is not covered (cin % 16, cout % 32, K > 64, ...): the
+ * caller then takes the f32 path. */
+int64_t usc_spconv_gather_gemm_bf16_ws_bytes(int64_t n_out, int32_t cin,
+                                             int32_t cout, int32_t K);
+/* out[o,:] (= or += when accumulate) sum_k in[nbr[k*n_out+o],:] @ W[k] (+ bias)
+ * with in bf16[n_in,cin] (usc_cast_bf16), Wp packed (usc_spconv_pack_w_bf16);
+ * nbr -1 = no neighbour (contributes zero), nbr NULL = K==1 identity rows.
+ * Each output element is summed by one lane over k and channel ascending: no
+ * atomics, no split-K, bit-identical from run to run.  Covers the forward of
+ * k3/s1 (K=27), k2/s2 (K=8, nbr = child table) and, on the inverted child
+ * table, the k2 transposed conv.  Replaces the same ME calls as
+ * usc_spconv_gather_gemm, forward only. */
+int usc_spconv_gather_gemm_bf16(const uint16_t* in, int64_t n_in, int32_t cin,
+                                const uint16_t* Wp, int32_t K, int32_t cout,
+                                const int32_t* nbr, int64_t n_out,
+                                const float* bias, float* out, int32_t accumulate,
+                                void* ws, int64_t ws_bytes, usc_stream_t s);
+
 /* Scratch bytes for usc_spconv_wgrad. */
 int64_t usc_spconv_wgrad_ws_bytes(int32_t K, int32_t cin, int32_t cout);
 /* Weight gradient:  dW[k] = sum_{p in list k}  a[a_idx[p],:]^T  b[b_idx[p],:]
@@ -404,6 +441,22 @@ int usc_conv_bn_act_backward(const usc_kmap* m, int32_t kind, const float* x,
                              int32_t dW_accumulate, float* dgamma,
                              float* dbeta, int32_t dbn_accumulate, void* ws,
                              int64_t ws_bytes, usc_stream_t s);
+/* usc_conv_bn_act_forward with the convolution in bf16 (usc_spconv_gather_gemm_bf16):
+ * Wp = the conv's weights packed by usc_spconv_pack_w_bf16; x is f32 and is
+ * cast to bf16 in the scratch; batch norm, residual and ReLU are the f32 ones of
+ * usc_conv_bn_act_forward (no tile form).  Inference only: y / stats / out are
+ * as there, but nothing here is meant for a backward pass.  Returns an error
+ * for shapes usc_spconv_gather_gemm_bf16_ws_bytes does not cover.  Replaces ME's
+ * conv forward + MinkowskiBatchNorm under the bf16 inference precision. */
+int64_t usc_unit_bf16_ws_bytes(const usc_kmap* m, int32_t kind, int32_t cin,
+                               int32_t cout);
+int usc_conv_bn_act_forward_bf16(const usc_kmap* m, int32_t kind,
+                                 const float* x, int32_t cin,
+                                 const uint16_t* Wp, int32_t cout,
+                                 const usc_bn* bn, const float* residual,
+                                 int32_t relu, float* y, float* stats,
+                                 float* out, void* ws, int64_t ws_bytes,
+                                 usc_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Step programs: the issue loop of a whole network stage behind ONE call.
@@ -421,8 +474,11 @@ int usc_conv_bn_act_backward(const usc_kmap* m, int32_t kind, const float* x,
  *   USC_STEP_CAT      : dst[n, ca + cb] = [a[n, ca] | b[n, cb]]
  *   USC_STEP_SPLIT    : dst[n, ca] = a[:, :ca];  dst2[n, cb] (+= when accumulate) a[:, ca:ca + cb]   (a is [n, ca + cb])
  *   USC_STEP_ADD      : dst[0 .. n) += a[0 .. n)   (n counts floats)
+ *   USC_STEP_UNIT_FWD_BF16 : usc_conv_bn_act_forward_bf16(map, kind, x, cin, W (read as the packed bf16 weights),
+ *                       cout, bn, residual, relu, y, stats, out)
  * ---------------------------------------------------------------------- */
-enum usc_step_op { USC_STEP_UNIT_FWD = 0, USC_STEP_UNIT_BWD = 1, USC_STEP_CAT = 2, USC_STEP_SPLIT = 3, USC_STEP_ADD = 4 };
+enum usc_step_op { USC_STEP_UNIT_FWD = 0, USC_STEP_UNIT_BWD = 1, USC_STEP_CAT = 2, USC_STEP_SPLIT = 3, USC_STEP_ADD = 4,
+                   USC_STEP_UNIT_FWD_BF16 = 5 };
 typedef struct usc_step {
   int32_t op, kind, cin, cout, relu;
   int32_t dx_accumulate, dW_accumulate, dbn_accumulate, defer_wgrad, accumulate;

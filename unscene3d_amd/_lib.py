@@ -53,7 +53,7 @@ class Step(C.Structure):
 
 
 _sp = C.POINTER(Step)
-STEP_UNIT_FWD, STEP_UNIT_BWD, STEP_CAT, STEP_SPLIT, STEP_ADD = 0, 1, 2, 3, 4
+STEP_UNIT_FWD, STEP_UNIT_BWD, STEP_CAT, STEP_SPLIT, STEP_ADD, STEP_UNIT_FWD_BF16 = 0, 1, 2, 3, 4, 5
 
 # name -> (restype, [argtypes])   — mirrors include/usc3d.h one to one
 SIGNATURES = {
@@ -90,6 +90,10 @@ SIGNATURES = {
     "usc_bn_tile_backward": (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p,
                                        _i64, _p]),
     "usc_spconv_pairs_gemm": (C.c_int, [_p, _i32, _p, _i32, _i32, _p, _p, _p, _i64, _p, _p]),
+    "usc_cast_bf16": (C.c_int, [_p, _i64, _p, _p]),
+    "usc_spconv_pack_w_bf16": (C.c_int, [_p, _i32, _i32, _i32, _p, _p]),
+    "usc_spconv_gather_gemm_bf16_ws_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "usc_spconv_gather_gemm_bf16": (C.c_int, [_p, _i64, _i32, _p, _i32, _i32, _p, _i64, _p, _p, _i32, _p, _i64, _p]),
     "usc_spconv_wgrad_ws_bytes": (_i64, [_i32, _i32, _i32]),
     "usc_spconv_wgrad": (C.c_int, [_p, _i32, _p, _i32, _i32, _p, _p, _p, _i64, _p, _i32, _p, _i64, _p]),
     "usc_spconv_wgrad_ws_bytes_rows": (_i64, [_i32, _i32, _i32, _i64]),
@@ -115,6 +119,8 @@ SIGNATURES = {
     "usc_conv_backward": (C.c_int, [_kp, _i32, _p, _i32, _p, _i32, _p, _p, _i32, _p, _i32, _p, _i64, _p]),
     "usc_bn_eval_stats": (C.c_int, [_p, _p, _p, _p, _f32, _i32, _p, _p, _p, _p, _p]),
     "usc_conv_bn_act_forward": (C.c_int, [_kp, _i32, _p, _i32, _p, _i32, _bp, _p, _i32, _p, _p, _p, _p, _i64, _p]),
+    "usc_unit_bf16_ws_bytes": (_i64, [_kp, _i32, _i32, _i32]),
+    "usc_conv_bn_act_forward_bf16": (C.c_int, [_kp, _i32, _p, _i32, _p, _i32, _bp, _p, _i32, _p, _p, _p, _p, _i64, _p]),
     "usc_conv_bn_act_backward": (C.c_int, [_kp, _i32, _p, _i32, _p, _i32, _bp, _p, _p, _p, _p, _p, _p, _p, _i32, _p,
                                            _i32, _p, _p, _i32, _p, _i64, _p]),
     "usc_colstats_ws_bytes": (_i64, [_i64, _i32]),

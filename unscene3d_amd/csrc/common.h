@@ -122,4 +122,8 @@ __device__ inline int wave_inclusive_scan(int v) {
 }
 #endif
 
+// bf16 forward conv (spconv_bf16.hip): inv[k][f] = c where nbr2[k][c] = f, else -1 (K x n_fine) — the gather table of
+// the k2 transposed conv from the child table of its stride-2 map
+int spconv_up_table(const int32_t* nbr2, int32_t K, int64_t n_coarse, int64_t n_fine, int32_t* inv, hipStream_t st);
+
 }  // namespace usc

@@ -508,6 +508,63 @@ int usc_conv_bn_act_forward(const usc_kmap* m, int32_t kind, const float* x, int
   return usc_bn_apply(y, scale, shift, residual, relu, out, sh.n_out, cout, s);
 }
 
+
+int64_t usc_unit_bf16_ws_bytes(const usc_kmap* m, int32_t kind, int32_t cin, int32_t cout) {
+  if (!m) return 0;
+  const ConvShape sh = conv_shape(m, kind);
+  const int64_t g = usc_spconv_gather_gemm_bf16_ws_bytes(sh.n_out, cin, cout, m->K);
+  if (g < 0) return -1;
+  int64_t b = align_up(usc_colstats_ws_bytes(sh.n_out, cout), 256) + align_up(sh.n_in * cin * 2, 256) + align_up(g, 256);
+  if (kind == USC_CONV_UP) b += align_up((int64_t)m->K * sh.n_out * 4, 256);
+  return b + 256;
+}
+
+int usc_conv_bn_act_forward_bf16(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const uint16_t* Wp,
+                                 int32_t cout, const usc_bn* bn, const float* residual, int32_t relu, float* y,
+                                 float* stats, float* out, void* ws, int64_t ws_bytes, usc_stream_t s) {
+  int rc = check_map(m, kind, cin, cout, "usc_conv_bn_act_forward_bf16");
+  if (rc) return rc;
+  USC_REQUIRE(bn && bn->c == cout, "usc_conv_bn_act_forward_bf16: batch-norm width must equal the conv's output width");
+  USC_REQUIRE(y && stats && out && bn->gamma && bn->beta, "usc_conv_bn_act_forward_bf16: null pointer");
+  const ConvShape sh = conv_shape(m, kind);
+  const int64_t gb = usc_spconv_gather_gemm_bf16_ws_bytes(sh.n_out, cin, cout, m->K);
+  USC_REQUIRE(gb >= 0, "usc_conv_bn_act_forward_bf16: shape not covered (K=%d, %d -> %d channels)", m->K, cin, cout);
+  if (sh.n_out == 0) return USC_OK;
+  USC_REQUIRE(x && Wp, "usc_conv_bn_act_forward_bf16: null pointer");
+  USC_REQUIRE(m->nbr || kind == USC_CONV_SAME, "usc_conv_bn_act_forward_bf16: strided maps need the child table");
+  hipStream_t st = as_stream(s);
+  WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
+  const int64_t sb = usc_colstats_ws_bytes(sh.n_out, cout);
+  void* sws = cur.take(sb);
+  uint16_t* xb = (uint16_t*)cur.take(sh.n_in * cin * 2);
+  void* gws = gb > 0 ? cur.take(gb) : nullptr;
+  int32_t* table = kind == USC_CONV_UP ? (int32_t*)cur.take((int64_t)m->K * sh.n_out * 4) : nullptr;
+  USC_REQUIRE(sws && xb && (gb == 0 || gws) && (kind != USC_CONV_UP || table),
+              "usc_conv_bn_act_forward_bf16: workspace too small (usc_unit_bf16_ws_bytes)");
+  rc = usc_cast_bf16(x, sh.n_in * cin, xb, s);
+  if (rc) return rc;
+  const int32_t* nbr = m->nbr;
+  if (kind == USC_CONV_UP) {
+    // every fine row has one parent: the child table read backwards is the gather table over the fine rows
+    rc = spconv_up_table(m->nbr, m->K, m->n_out, sh.n_out, table, st);
+    if (rc) return rc;
+    nbr = table;
+  }
+  rc = usc_spconv_gather_gemm_bf16(xb, sh.n_in, cin, Wp, m->K, cout, nbr, sh.n_out, nullptr, y, 0, gws, gb, s);
+  if (rc) return rc;
+  float* mean = stats, *invstd = stats + cout, *scale = stats + 2 * cout, *shift = stats + 3 * cout;
+  if (bn->training) {
+    rc = usc_bn_forward_stats(y, sh.n_out, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean,
+                              bn->running_var, bn->num_batches_tracked, mean, invstd, scale, shift, sws, sb, s);
+  } else {
+    USC_REQUIRE(bn->running_mean && bn->running_var, "usc_conv_bn_act_forward_bf16: eval mode needs running statistics");
+    rc = usc_bn_eval_stats(bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->eps, cout, mean, invstd, scale,
+                           shift, s);
+  }
+  if (rc) return rc;
+  return usc_bn_apply(y, scale, shift, residual, relu, out, sh.n_out, cout, s);
+}
+
 static int unit_backward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
                               const usc_bn* bn, const float* y, const float* stats, const float* out_relu,
                               const float* dout, float* dy, float* dres, float* dx, int32_t dx_accumulate, float* dW,
@@ -571,6 +628,9 @@ static int64_t program_half_bytes(const usc_step* steps, int32_t n_steps) {
     if ((t.op == USC_STEP_UNIT_FWD || t.op == USC_STEP_UNIT_BWD) && t.map) {
       const int64_t b = usc_unit_ws_bytes(t.map, t.kind, t.cin, t.cout);
       if (b > need) need = b;
+    } else if (t.op == USC_STEP_UNIT_FWD_BF16 && t.map) {
+      const int64_t b = usc_unit_bf16_ws_bytes(t.map, t.kind, t.cin, t.cout);
+      if (b > need) need = b;
     }
   }
   return align_up(need, 256);
@@ -602,6 +662,10 @@ int usc_program_run(const usc_step* steps, int32_t begin, int32_t end, void* ws_
       case USC_STEP_UNIT_FWD:
         rc = usc_conv_bn_act_forward(t.map, t.kind, t.x, t.cin, t.W, t.cout, t.bn, t.residual, t.relu, t.y, t.stats, t.out,
                                      ws, ws_bytes, s);
+        break;
+      case USC_STEP_UNIT_FWD_BF16:
+        rc = usc_conv_bn_act_forward_bf16(t.map, t.kind, t.x, t.cin, (const uint16_t*)t.W, t.cout, t.bn, t.residual, t.relu,
+                                          t.y, t.stats, t.out, ws, ws_bytes, s);
         break;
       case USC_STEP_UNIT_BWD: {
         USC_REQUIRE(t.map, "usc_program_run: step %d has no kernel map", i);

@@ -297,6 +297,42 @@ def gather_gemm(feats, W, nbr, n_out, bias=None, out=None, accumulate=False, w_t
     return out
 
 
+def cast_bf16(x: torch.Tensor) -> torch.Tensor:
+    """f32 -> bf16 copy, round to nearest even (usc_cast_bf16)."""
+    _chk(x, torch.float32, "x")
+    out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    check(lib.usc_cast_bf16(_ptr(x), x.numel(), _ptr(out), _stream()), "usc_cast_bf16")
+    return out
+
+
+def gather_gemm_bf16(feats, Wp, K, cout, nbr, n_out, bias=None, out=None, accumulate=False):
+    """out[o] (+)= sum_k bf16(feats[nbr[k,o]]) @ bf16(W[k]) (+bias), f32 accumulate (csrc/spconv_bf16.hip).
+    feats bf16[n_in, cin] (cast_bf16) or f32 (cast here); Wp: precision.pack_weights(W f32[K, cin, cout]);
+    nbr i32[K, n_out] (-1 = no neighbour) or None (identity, K = 1).  Raises for shapes the kernel does not cover
+    (precision.shape_ok)."""
+    if feats.dtype == torch.float32:
+        feats = cast_bf16(feats.contiguous())
+    _chk(feats, torch.bfloat16, "feats")
+    _chk(Wp, torch.bfloat16, "Wp")
+    cin = feats.shape[1]
+    if Wp.numel() != K * cin * cout:
+        raise RuntimeError("gather_gemm_bf16: packed weights do not match K, cin, cout")
+    if nbr is not None:
+        _chk(nbr, torch.int32, "nbr")
+        if nbr.shape[0] != K or nbr.shape[1] != n_out:
+            raise RuntimeError("gather_gemm_bf16: neighbour table shape mismatch")
+    if out is None:
+        out = torch.empty((n_out, cout), dtype=torch.float32, device=feats.device)
+    if bias is not None:
+        _chk(bias, torch.float32, "bias")
+    wsb = lib.usc_spconv_gather_gemm_bf16_ws_bytes(n_out, cin, cout, K)
+    ws = _ws(wsb, feats.device) if wsb > 0 else None
+    check(lib.usc_spconv_gather_gemm_bf16(_ptr(feats), feats.shape[0], cin, _ptr(Wp), K, cout, _ptr(nbr), n_out,
+                                          _ptr(bias), _ptr(out), int(accumulate), _ptr(ws), max(wsb, 0), _stream()),
+          "usc_spconv_gather_gemm_bf16")
+    return out
+
+
 def pairs_gemm(feats, W, rows_in, rows_out, koff, P, n_out):
     """out[rows_out[p]] = feats[rows_in[p]] @ W[k(p)] — every out row written exactly once."""
     _chk(feats, torch.float32, "feats")

@@ -29,8 +29,8 @@ import os
 
 import torch
 
-from . import ops, units
-from ._lib import STEP_ADD, STEP_CAT, STEP_SPLIT, STEP_UNIT_BWD, STEP_UNIT_FWD, Step, check, lib
+from . import ops, precision, units
+from ._lib import STEP_ADD, STEP_CAT, STEP_SPLIT, STEP_UNIT_BWD, STEP_UNIT_FWD, STEP_UNIT_FWD_BF16, Step, check, lib
 
 ENABLED = os.environ.get("USC3D_BACKBONE_PROGRAM", "1") == "1"
 SAME, DOWN, UP = units.SAME, units.DOWN, units.UP
@@ -230,7 +230,7 @@ def usable(model, x):
 
 class _Trunk(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, pl, cm, ts, feats, *params):
+    def forward(ctx, model, pl, cm, ts, bf16, feats, *params):
         dev = feats.device
         rows = [cm.coord_map(ts << l).n for l in range(pl.n_levels)]
         floats = sum(r * f for r, f in zip(rows, pl.act_floats)) + pl.stat_floats + (pl.n_act + 8) * _ALIGN
@@ -268,6 +268,9 @@ class _Trunk(torch.autograd.Function):
                 st.op, st.kind, st.cin, st.cout, st.relu = STEP_UNIT_FWD, op["kind"], op["cin"], cout, int(op["relu"])
                 st.map, st.bn = C.addressof(km.struct), bref
                 st.x, st.W = ptr[op["x"]], op["conv"].kernel.data_ptr()
+                wp = bf16.get(id(op["conv"].kernel)) if bf16 else None
+                if wp is not None:                           # inference in bf16: packed weights (kept by `bf16`)
+                    st.op, st.W = STEP_UNIT_FWD_BF16, wp.data_ptr()
                 st.residual = ptr[op["res"]] if op["res"] is not None else None
                 st.y, st.stats, st.out = py, ps, po
                 stats_ptr.append(ps)
@@ -446,7 +449,7 @@ class _Trunk(torch.autograd.Function):
             key = dev.index if dev.index is not None else torch.cuda.current_device()
             units.queue_lane_join(key)
         ctx.state = None
-        return (None, None, None, None, None) + (None,) * len(pl.params)
+        return (None, None, None, None, None, None) + (None,) * len(pl.params)
 
 
 def trunk(model, x):
@@ -457,4 +460,14 @@ def trunk(model, x):
         return None
     cm, ts = x.coordinate_manager, x._ts()
     feats = x.F.contiguous()
-    return list(_Trunk.apply(model, pl, cm, ts, feats, *pl.params))
+    # bf16 inference (precision.py): id(conv weight) -> packed bf16 weights, decided here (outside the Function, whose
+    # forward always runs with gradients off); None when every unit runs in f32
+    bf16 = None
+    if precision.bf16_active():
+        bf16 = {}
+        for op in pl.ops:
+            if op["t"] == "unit":
+                wp = precision.unit_weights(op["conv"].kernel, op["kind"] == SAME, cm.coord_map(ts << op["lout"]).n)
+                if wp is not None:
+                    bf16[id(op["conv"].kernel)] = wp
+    return list(_Trunk.apply(model, pl, cm, ts, bf16, feats, *pl.params))

@@ -9,11 +9,13 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..precision import inference_precision
 
 
-def encode_scene_feats_3d(model, sinput, resolution_scale=2):
-    """Res16UNet34CMultiRes features of level `res_{resolution_scale}` for every input voxel."""
-    with torch.no_grad():
+def encode_scene_feats_3d(model, sinput, resolution_scale=2, precision="f32"):
+    """Res16UNet34CMultiRes features of level `res_{resolution_scale}` for every input voxel.  precision: the trunk's
+    convolutions in "f32" or "bf16" (unscene3d_amd.inference_precision)."""
+    with torch.no_grad(), inference_precision(precision):
         _, feature_maps = model(sinput)
         enc = feature_maps[f"res_{resolution_scale}"]
         lr_coords = enc.C[:, 1:].float().contiguous()

@@ -19,7 +19,7 @@ import weakref
 
 import torch
 
-from . import ops
+from . import ops, precision
 from . import profiler as _prof
 from ._lib import BNDesc, KMap, check, lib
 
@@ -330,8 +330,9 @@ def usable(x, conv, *more_convs):
 
 # --------------------------------------------------------------------------------------------------------------
 # one unit each way (plain functions: the autograd nodes below compose them)
-def unit_forward(x, W3, bn, kmap: KMapRef, kind, residual, relu):
-    """-> (y conv output, stats f32[4,c], out).  W3 f32[K,cin,cout]."""
+def unit_forward(x, W3, bn, kmap: KMapRef, kind, residual, relu, wp=None):
+    """-> (y conv output, stats f32[4,c], out).  W3 f32[K,cin,cout].  wp: the packed bf16 weights
+    (precision.unit_weights) -> the conv runs in bf16 (inference only), else f32."""
     dev = x.device
     K, cin, cout = W3.shape
     n_out = kmap.n_in if kind == UP else kmap.n_out
@@ -339,6 +340,13 @@ def unit_forward(x, W3, bn, kmap: KMapRef, kind, residual, relu):
     out = torch.empty((n_out, cout), dtype=torch.float32, device=dev)
     stats = torch.empty((4, cout), dtype=torch.float32, device=dev)
     _, bref = _bn_desc(bn, _training(bn))
+    if wp is not None:
+        ws = workspace(lib.usc_unit_bf16_ws_bytes(kmap.ref, kind, cin, cout), dev)
+        check(lib.usc_conv_bn_act_forward_bf16(kmap.ref, kind, x.data_ptr(), cin, wp.data_ptr(), cout, bref,
+                                               None if residual is None else residual.data_ptr(), int(relu),
+                                               y.data_ptr(), stats.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), ops._stream()), "usc_conv_bn_act_forward_bf16")
+        return y, stats, out
     wsb = lib.usc_unit_ws_bytes(kmap.ref, kind, cin, cout)
     ws = workspace(wsb, dev)
     check(lib.usc_conv_bn_act_forward(kmap.ref, kind, x.data_ptr(), cin, W3.data_ptr(), cout, bref,
@@ -399,11 +407,11 @@ class _Unit(torch.autograd.Function):
     """out = [relu](BN(conv(x)) [+ residual]) as one autograd node."""
 
     @staticmethod
-    def forward(ctx, x, W, gamma, beta, residual, bn, kmap, kind, relu):
+    def forward(ctx, x, W, gamma, beta, residual, bn, kmap, kind, relu, wp):
         x = x.contiguous()
         res = None if residual is None else residual.contiguous()
         W3 = _w3(W).contiguous()
-        y, stats, out = unit_forward(x, W3, bn, kmap, kind, res, relu)
+        y, stats, out = unit_forward(x, W3, bn, kmap, kind, res, relu, wp)
         ctx.save_for_backward(x, W3, y, stats, out if relu else None)
         ctx.bn, ctx.kmap, ctx.kind, ctx.has_res = bn, kmap, kind, residual is not None
         ctx.params = (W, gamma, beta)
@@ -420,11 +428,14 @@ class _Unit(torch.autograd.Function):
                                              defer_ok=True)
         if dW is not None and W.dim() == 2:
             dW = dW.view(W.shape)
-        return dx, dW, dg, db, dres, None, None, None, None
+        return dx, dW, dg, db, dres, None, None, None, None, None
 
 
 def conv_bn_act(x, conv_weight, bn, kmap, kind, residual=None, relu=True):
-    return _Unit.apply(x, conv_weight, bn.weight, bn.bias, residual, bn, kmap, kind, relu)
+    # bf16 only without autograd (precision.unit_weights returns None otherwise): decided here, outside the Function,
+    # whose forward always runs with gradients off
+    return _Unit.apply(x, conv_weight, bn.weight, bn.bias, residual, bn, kmap, kind, relu,
+                       precision.unit_weights(conv_weight, kind == SAME, kmap.n_in if kind == UP else kmap.n_out))
 
 
 class _BasicBlock(torch.autograd.Function):
@@ -432,19 +443,19 @@ class _BasicBlock(torch.autograd.Function):
     (reference models/modules/resnet_block.py:48-64, models/resnet.py:124-146) as one autograd node."""
 
     @staticmethod
-    def forward(ctx, x, W1, g1, b1, W2, g2, b2, Wd, gd, bd, bns, kmap, kmap_id):
+    def forward(ctx, x, W1, g1, b1, W2, g2, b2, Wd, gd, bd, bns, kmap, kmap_id, wps):
         x = x.contiguous()
         bn1, bn2, bnd = bns
         W1c, W2c = W1.contiguous(), W2.contiguous()
-        y1, st1, a1 = unit_forward(x, W1c, bn1, kmap, SAME, None, True)
+        y1, st1, a1 = unit_forward(x, W1c, bn1, kmap, SAME, None, True, wps[0])
         saved_d = (None, None, None)
         if Wd is not None:
             Wdc = _w3(Wd).contiguous()
-            yd, std, r = unit_forward(x, Wdc, bnd, kmap_id, SAME, None, False)
+            yd, std, r = unit_forward(x, Wdc, bnd, kmap_id, SAME, None, False, wps[2])
             saved_d = (Wdc, yd, std)
         else:
             r = x
-        y2, st2, out = unit_forward(a1, W2c, bn2, kmap, SAME, r, True)
+        y2, st2, out = unit_forward(a1, W2c, bn2, kmap, SAME, r, True, wps[1])
         ctx.save_for_backward(x, W1c, W2c, y1, st1, a1, y2, st2, out, *saved_d)
         ctx.bns, ctx.kmap, ctx.kmap_id = bns, kmap, kmap_id
         ctx.params = (W1, g1, b1, W2, g2, b2, Wd, gd, bd)
@@ -480,7 +491,7 @@ class _BasicBlock(torch.autograd.Function):
                                                  True, need_dx, Wd, gd, bd)
             if dWd is not None and Wd.dim() == 2:
                 dWd = dWd.view(Wd.shape)
-        return dx, dW1, dg1, db1, dW2, dg2, db2, dWd, dgd, dbd, None, None, None
+        return dx, dW1, dg1, db1, dW2, dg2, db2, dWd, dgd, dbd, None, None, None, None
 
 
 def basic_block(x, block, kmap, kmap_id):
@@ -491,5 +502,8 @@ def basic_block(x, block, kmap, kmap_id):
     else:
         Wd = gd = bd = bnd = None
     bn1, bn2 = block.norm1.bn, block.norm2.bn
+    n = kmap.n_out
+    wps = (precision.unit_weights(block.conv1.kernel, True, n), precision.unit_weights(block.conv2.kernel, True, n),
+           None if Wd is None else precision.unit_weights(Wd, True, n))
     return _BasicBlock.apply(x, block.conv1.kernel, bn1.weight, bn1.bias, block.conv2.kernel, bn2.weight, bn2.bias,
-                             Wd, gd, bd, (bn1, bn2, bnd), kmap, kmap_id)
+                             Wd, gd, bd, (bn1, bn2, bnd), kmap, kmap_id, wps)
