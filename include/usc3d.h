@@ -921,6 +921,22 @@ int64_t usc_ncut_fiedler_ws_bytes(int64_t S);
 int usc_ncut_fiedler(const uint8_t* Abin, const double* deg, int64_t S, double eps,
                      double* evec, double* eval, void* ws, int64_t ws_bytes,
                      usc_stream_t s);
+/* The same; flags bit 0 forces the stepwise tridiagonalisation (as USC3D_TRI_STEPWISE=1 does). */
+int usc_ncut_fiedler_ex(const uint8_t* Abin, const double* deg, int64_t S, double eps,
+                        double* evec, double* eval, void* ws, int64_t ws_bytes,
+                        usc_stream_t s, int32_t flags);
+/* The kernels usc_ncut_fiedler_ex launches for S segments on a device with `cus`
+ * compute units (host only, no HIP call; -1 unless 3 <= S <= 8000):
+ *   bits 0-3   tridiagonalisation: 0 stepwise (tri_reflect_symv + tri_update per
+ *              step), one launch with the rows in 1 registers <10,3>, 2 registers
+ *              <16,4>, 3 LDS, 4 global memory
+ *   bit  4     tri_eig_kernel works in LDS (else in global memory)
+ *   bits 8-11  back-transformation: 0 tri_backtransform_kernel (1024 threads),
+ *              1-3 tri_backtransform_quad_kernel<2,3,4>, 4-7 the one-wave
+ *              tri_backtransform_wave_kernel<4,8,11,16> (USC3D_BACKTRANSFORM_QUAD=0)
+ * USC3D_TRI_STEPWISE and USC3D_BACKTRANSFORM_{QUAD,WAVE} are honoured as in the launch.
+ * The launch still falls back to stepwise if the kernel cannot get its LDS. */
+int32_t usc_ncut_fiedler_plan(int64_t S, int32_t cus, int32_t flags);
 
 /* ------------------------------------------------------------------------
  * N6  exact 1-nearest-neighbour — replaces scipy.spatial.KDTree.query(k=1)

@@ -82,3 +82,34 @@ def test_steady_state_preparation_on_a_host_device_only_freezes_the_heap():
         assert prepare_steady_state(torch.device("cpu"), freeze_heap=False) == {}
     finally:
         gc.unfreeze()
+
+
+def _fiedler_plan(S, cus=256, flags=0):
+    code = lib.usc_ncut_fiedler_plan(S, cus, flags)
+    return {"tri": code & 0xF, "eig_lds": (code >> 4) & 1, "bt": (code >> 8) & 0xF}
+
+
+# usc_ncut_fiedler_plan (include/usc3d.h): tridiagonalisation 0 stepwise, 1 rows in registers <10,3>, 2 <16,4>, 3 LDS,
+# 4 global memory; back-transformation 0 the 1024-thread kernel, 1-3 quad<2,3,4>
+@pytest.mark.parametrize("S,tri,eig_lds,bt", [
+    (3, 0, 1, 1), (7, 0, 1, 1), (8, 1, 1, 1), (130, 1, 1, 1), (512, 1, 1, 1), (513, 1, 1, 2), (640, 1, 1, 2),
+    (641, 2, 1, 2), (768, 2, 1, 2), (769, 2, 1, 3), (800, 2, 1, 3), (801, 2, 0, 3), (1024, 2, 0, 3),
+    (1025, 4, 0, 0), (4000, 4, 0, 0), (4001, 0, 0, 0), (8000, 0, 0, 0)])
+def test_fiedler_plan_boundaries_on_256_cus(S, tri, eig_lds, bt):
+    assert _fiedler_plan(S) == {"tri": tri, "eig_lds": eig_lds, "bt": bt}
+
+
+def test_fiedler_plan_rows_in_lds_only_below_64_cus():
+    assert _fiedler_plan(640, cus=32)["tri"] == 3                     # 32 workgroups of 20 rows: too many for registers
+    for cus in (64, 128, 256, 304):
+        assert all(_fiedler_plan(S, cus)["tri"] != 3 for S in range(3, 8001)), cus
+    assert all(_fiedler_plan(S, cus=7)["tri"] == 0 for S in range(3, 8001))      # too few CUs for one launch
+
+
+def test_fiedler_plan_flag_forces_stepwise_and_range_is_checked():
+    for cus in (7, 32, 64, 256):
+        for S in range(3, 8001):
+            plain, forced = lib.usc_ncut_fiedler_plan(S, cus, 0), lib.usc_ncut_fiedler_plan(S, cus, 1)
+            assert forced & 0xF == 0 and forced & ~0xF == plain & ~0xF, (S, cus)   # eigen / back-transform unchanged
+    for S in (-1, 0, 2, 8001):
+        assert lib.usc_ncut_fiedler_plan(S, 256, 0) == -1

@@ -316,7 +316,8 @@ __global__ __launch_bounds__(256) void tri_update_kernel(TriState t, int64_t i) 
 // counter, drain or fence.  Slots ping-pong between two buffers (nobody can run more than one step ahead).
 // The arithmetic per element is that of the stepwise kernels, so both paths give the same T and reflectors.
 // Waits are bounded: a thread that does not see its slots arrive raises the error word and everybody leaves
-// (d[0] becomes NaN, which the caller sees as a NaN eigenpair) instead of hanging the device.
+// (d[0] becomes NaN, which the caller sees as a NaN eigenpair) instead of hanging the device; pseudo_masks/ncut.py
+// then solves once more with the stepwise path (usc_ncut_fiedler_ex flag bit 0).
 struct Slot {          // 16 bytes, written and read as ONE dwordx4 access: a value never shows without its tag
   double value;
   uint64_t tag;
@@ -1130,43 +1131,79 @@ __global__ __launch_bounds__(256) void tri_backtransform_quad_kernel(TriState t,
   }
 }
 
-// One-launch tridiagonalisation when the co-resident grid and its LDS fit; false -> caller runs the stepwise path.
-// USC3D_TRI_STEPWISE=1 forces the stepwise path (A/B measurements).
-static bool launch_persistent(const TriState& t, double* tail, hipStream_t st) {
+// Launch plan of the tridiagonalisation (host only).  The one-launch form needs n in [8, 4000], at least 8 CUs and a
+// co-resident grid whose LDS fits; everything else runs stepwise.  USC3D_TRI_STEPWISE=1 (A/B measurements) and flag
+// bit 0 force the stepwise path.
+enum { kTriStepwise = 0, kTriReg10 = 1, kTriReg16 = 2, kTriLds = 3, kTriGlobal = 4 };
+struct TriPlan {
+  int form = kTriStepwise;
+  int G = 0, R = 0, ld = 0;
+  size_t lds = 0;
+};
+static TriPlan tri_plan(int64_t n, int cus, int32_t flags) {
   static const int mode = [] { const char* e = getenv("USC3D_TRI_STEPWISE"); return (e && e[0] == '1') ? 1 : 0; }();
-  if (mode == 1) return false;
+  TriPlan p;
+  if (mode == 1 || (flags & 1)) return p;
+  if (n < 8 || n > 4000 || cus < 8) return p;
+  // few workgroups: every arrival is an atomic on one word, and a step's work is tiny (n = 625: 2.4 kFLOP per row)
+  p.G = 64;
+  if (p.G > cus) p.G = cus;
+  if ((int64_t)p.G > n / 2) p.G = (int)(n / 2);
+  p.R = (int)ceil_div(n, p.G);
+  p.ld = (int)(((n + 15) / 32) * 32 + 16);   // >= n, = 16 mod 32
+  const size_t vec_bytes = (size_t)4 * n * sizeof(double);
+  const size_t row_bytes = (size_t)p.R * p.ld * sizeof(double);
+  p.lds = vec_bytes;
+  if (n <= 640 && p.R <= 12) {
+    p.form = kTriReg10;
+  } else if (n <= 1024 && p.R <= 16) {
+    p.form = kTriReg16;
+  } else if (vec_bytes + row_bytes <= 150 * 1024) {
+    p.form = kTriLds;
+    p.lds = vec_bytes + row_bytes;
+  } else {
+    p.form = kTriGlobal;
+  }
+  if (p.lds > 150 * 1024) p.form = kTriStepwise;
+  return p;
+}
+
+// Back-transformation kernel for S (the USC3D_BACKTRANSFORM_QUAD=0 / _WAVE=0 switches select the earlier forms):
+// 0 tri_backtransform_kernel, 1..3 tri_backtransform_quad_kernel<2, 3, 4>, 4..7 tri_backtransform_wave_kernel<4, 8, 11, 16>.
+static int backtransform_plan(int64_t S) {
+  static const bool bt_wave = !(getenv("USC3D_BACKTRANSFORM_WAVE") && getenv("USC3D_BACKTRANSFORM_WAVE")[0] == '0');
+  static const bool bt_quad = !(getenv("USC3D_BACKTRANSFORM_QUAD") && getenv("USC3D_BACKTRANSFORM_QUAD")[0] == '0');
+  if (bt_quad && S <= 512) return 1;
+  if (bt_quad && S <= 768) return 2;
+  if (bt_quad && S <= 1024) return 3;
+  if (bt_wave && S <= 256) return 4;
+  if (bt_wave && S <= 512) return 5;
+  if (bt_wave && S <= 704) return 6;
+  if (bt_wave && S <= 1024) return 7;
+  return 0;
+}
+
+// One-launch tridiagonalisation as planned; false -> caller runs the stepwise path (also when the kernel cannot get
+// the LDS it needs).
+static bool launch_persistent(const TriState& t, const TriPlan& p, double* tail, hipStream_t st) {
   const int64_t n = t.n;
-  if (n < 8 || n > 4000) return false;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
-    return false;
   TriPersist a;
   a.t = t;
-  // few workgroups: every arrival is an atomic on one word, and a step's work is tiny (n = 625: 2.4 kFLOP per row)
-  a.G = 64;
-  if (a.G > cus) a.G = cus;
-  if ((int64_t)a.G > n / 2) a.G = (int)(n / 2);
-  a.R = (int)ceil_div(n, a.G);
+  a.G = p.G;
+  a.R = p.R;
   a.pbuf = reinterpret_cast<Slot*>(tail);
   a.rowbuf = a.pbuf + 2 * n;
   a.sync = reinterpret_cast<unsigned int*>(a.rowbuf + 2 * n);
-  a.ld = (int)(((n + 15) / 32) * 32 + 16);   // >= n, = 16 mod 32
-  const size_t vec_bytes = (size_t)4 * n * sizeof(double);
-  const size_t row_bytes = (size_t)a.R * a.ld * sizeof(double);
+  a.ld = p.ld;
   void (*kern)(TriPersist) = nullptr;
-  size_t lds = vec_bytes;
-  if (n <= 640 && a.R <= 12) {
-    kern = tri_persistent_kernel<kRowsReg, 10, 3>;
-  } else if (n <= 1024 && a.R <= 16) {
-    kern = tri_persistent_kernel<kRowsReg, 16, 4>;
-  } else if (vec_bytes + row_bytes <= 150 * 1024) {
-    kern = tri_persistent_kernel<kRowsLds, 1, 1>;
-    lds = vec_bytes + row_bytes;
-  } else {
-    kern = tri_persistent_kernel<kRowsGlobal, 1, 1>;
+  switch (p.form) {
+    case kTriReg10: kern = tri_persistent_kernel<kRowsReg, 10, 3>; break;
+    case kTriReg16: kern = tri_persistent_kernel<kRowsReg, 16, 4>; break;
+    case kTriLds: kern = tri_persistent_kernel<kRowsLds, 1, 1>; break;
+    case kTriGlobal: kern = tri_persistent_kernel<kRowsGlobal, 1, 1>; break;
+    default: return false;
   }
-  if (lds > 150 * 1024) return false;
+  const size_t lds = p.lds;
   if (lds > 64 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return false;
@@ -1225,11 +1262,21 @@ int usc_ncut_binarize(const float* simA, const float* simB, int64_t S, float tau
 
 int64_t usc_ncut_fiedler_ws_bytes(int64_t S) { return (2 * S * S + 20 * S + 32) * 8; }
 
-int usc_ncut_fiedler(const uint8_t* Abin, const double* deg, int64_t S, double eps, double* evec, double* eval,
-                     void* ws, int64_t ws_bytes, usc_stream_t s) {
+int32_t usc_ncut_fiedler_plan(int64_t S, int32_t cus, int32_t flags) {
+  if (S < 3 || S > 8000) return -1;
+  return tri_plan(S, cus, flags).form | (S <= kEigLdsMax ? 16 : 0) | (backtransform_plan(S) << 8);
+}
+
+int usc_ncut_fiedler_ex(const uint8_t* Abin, const double* deg, int64_t S, double eps, double* evec, double* eval,
+                        void* ws, int64_t ws_bytes, usc_stream_t s, int32_t flags) {
   USC_REQUIRE(S >= 3 && S <= 8000 && Abin && deg && evec && eval && ws, "usc_ncut_fiedler: bad argument (3 <= S <= 8000)");
   USC_REQUIRE(ws_bytes >= usc_ncut_fiedler_ws_bytes(S), "usc_ncut_fiedler: workspace too small");
   hipStream_t st = as_stream(s);
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    cus = 0;   // -> stepwise
+  const TriPlan tp = tri_plan(S, cus, flags);
+  const int32_t plan = usc_ncut_fiedler_plan(S, cus, flags);
   double* w = (double*)ws;
   TriState t{};
   t.n = S;
@@ -1243,7 +1290,7 @@ int usc_ncut_fiedler(const uint8_t* Abin, const double* deg, int64_t S, double e
   double* work = z + S;   // 5 S
   double* work_tail = work + 5 * S;   // offset 2S^2 + 10S doubles: 16-byte aligned; 8S + 2 doubles: tagged p / row slots + error word
   hipLaunchKernelGGL(ncut_laplacian_kernel, dim3(stream_grid(S * S, 256)), dim3(256), 0, st, Abin, deg, S, eps, t.C);
-  if (!launch_persistent(t, work_tail, st)) {
+  if (!launch_persistent(t, tp, work_tail, st)) {
     for (int64_t i = 0; i + 1 < S; ++i) {
       const int64_t m = S - i - 1;
       hipLaunchKernelGGL(tri_reflect_symv_kernel, dim3((unsigned)ceil_div(m, 4)), dim3(256), (size_t)S * sizeof(double), st, t, i);
@@ -1251,31 +1298,28 @@ int usc_ncut_fiedler(const uint8_t* Abin, const double* deg, int64_t S, double e
     }
     hipLaunchKernelGGL(tri_last_diag_kernel, dim3(1), dim3(64), 0, st, t);
   }
-  if (S <= kEigLdsMax)
+  if (plan & 16)
     hipLaunchKernelGGL(tri_eig_kernel<1>, dim3(1), dim3(128), (size_t)S * 10 * sizeof(double), st, (const double*)t.d,
                        (const double*)t.e, S, 1, eval, z, work);
   else
     hipLaunchKernelGGL(tri_eig_kernel<0>, dim3(1), dim3(128), 0, st, (const double*)t.d, (const double*)t.e, S, 1, eval, z, work);
-  static const bool bt_wave = !(getenv("USC3D_BACKTRANSFORM_WAVE") && getenv("USC3D_BACKTRANSFORM_WAVE")[0] == '0');
-  static const bool bt_quad = !(getenv("USC3D_BACKTRANSFORM_QUAD") && getenv("USC3D_BACKTRANSFORM_QUAD")[0] == '0');
-  if (bt_quad && S <= 512)
-    hipLaunchKernelGGL(tri_backtransform_quad_kernel<2>, dim3(1), dim3(256), 0, st, t, deg, (const double*)z, evec);
-  else if (bt_quad && S <= 768)
-    hipLaunchKernelGGL(tri_backtransform_quad_kernel<3>, dim3(1), dim3(256), 0, st, t, deg, (const double*)z, evec);
-  else if (bt_quad && S <= 1024)
-    hipLaunchKernelGGL(tri_backtransform_quad_kernel<4>, dim3(1), dim3(256), 0, st, t, deg, (const double*)z, evec);
-  else if (bt_wave && S <= 256)
-    hipLaunchKernelGGL(tri_backtransform_wave_kernel<4>, dim3(1), dim3(64), 0, st, t, deg, (const double*)z, evec);
-  else if (bt_wave && S <= 512)
-    hipLaunchKernelGGL(tri_backtransform_wave_kernel<8>, dim3(1), dim3(64), 0, st, t, deg, (const double*)z, evec);
-  else if (bt_wave && S <= 704)
-    hipLaunchKernelGGL(tri_backtransform_wave_kernel<11>, dim3(1), dim3(64), 0, st, t, deg, (const double*)z, evec);
-  else if (bt_wave && S <= 1024)
-    hipLaunchKernelGGL(tri_backtransform_wave_kernel<16>, dim3(1), dim3(64), 0, st, t, deg, (const double*)z, evec);
-  else
-    hipLaunchKernelGGL(tri_backtransform_kernel, dim3(1), dim3(1024), 0, st, t, deg, z, evec);
+  switch ((plan >> 8) & 15) {
+    case 1: hipLaunchKernelGGL(tri_backtransform_quad_kernel<2>, dim3(1), dim3(256), 0, st, t, deg, (const double*)z, evec); break;
+    case 2: hipLaunchKernelGGL(tri_backtransform_quad_kernel<3>, dim3(1), dim3(256), 0, st, t, deg, (const double*)z, evec); break;
+    case 3: hipLaunchKernelGGL(tri_backtransform_quad_kernel<4>, dim3(1), dim3(256), 0, st, t, deg, (const double*)z, evec); break;
+    case 4: hipLaunchKernelGGL(tri_backtransform_wave_kernel<4>, dim3(1), dim3(64), 0, st, t, deg, (const double*)z, evec); break;
+    case 5: hipLaunchKernelGGL(tri_backtransform_wave_kernel<8>, dim3(1), dim3(64), 0, st, t, deg, (const double*)z, evec); break;
+    case 6: hipLaunchKernelGGL(tri_backtransform_wave_kernel<11>, dim3(1), dim3(64), 0, st, t, deg, (const double*)z, evec); break;
+    case 7: hipLaunchKernelGGL(tri_backtransform_wave_kernel<16>, dim3(1), dim3(64), 0, st, t, deg, (const double*)z, evec); break;
+    default: hipLaunchKernelGGL(tri_backtransform_kernel, dim3(1), dim3(1024), 0, st, t, deg, z, evec); break;
+  }
   USC_CHECK_LAUNCH("usc_ncut_fiedler");
   return USC_OK;
+}
+
+int usc_ncut_fiedler(const uint8_t* Abin, const double* deg, int64_t S, double eps, double* evec, double* eval,
+                     void* ws, int64_t ws_bytes, usc_stream_t s) {
+  return usc_ncut_fiedler_ex(Abin, deg, S, eps, evec, eval, ws, ws_bytes, s, 0);
 }
 
 }  // extern "C"

@@ -11,6 +11,8 @@ The visualisation-only accumulations of the reference loop (:441-447, :478-489) 
 """
 from __future__ import annotations
 
+import warnings
+
 import numpy as np
 import torch
 
@@ -105,35 +107,57 @@ def get_masked_affinity_matrix(painting, feats, mask):
     return feats, painting.squeeze()
 
 
-def second_smallest_eigenvector(A, D, eps=1e-5):
-    """Generalized eigenvector #2 of (D - A, D) — `eigh(D - A, D, subset_by_index=[1, 2])` of the reference
-    (:138-146), computed on the device with LAPACK's sign.  A: device u8 affinity, D: device degree vector."""
+_FIEDLER_STEPWISE = 1        # usc_ncut_fiedler_ex flags bit 0: stepwise tridiagonalisation
+
+
+def _fiedler(A, D, eps, stepwise=False):
+    """Queue the generalized eigensolve of (D - A, D) on the current stream -> (evec f64[S], evals f64[2]) on the
+    device.  `stepwise` forces the launch-per-Householder-step tridiagonalisation instead of the one-launch kernel."""
     S = A.shape[0]
     evec = torch.empty(S, dtype=torch.float64, device=A.device)
     evals = torch.empty(2, dtype=torch.float64, device=A.device)
     ws = torch.empty(lib.usc_ncut_fiedler_ws_bytes(S), dtype=torch.uint8, device=A.device)
-    check(lib.usc_ncut_fiedler(A.data_ptr(), D.data_ptr(), S, float(eps), evec.data_ptr(), evals.data_ptr(),
-                               ws.data_ptr(), ws.numel(), ops._stream()), "usc_ncut_fiedler")
+    check(lib.usc_ncut_fiedler_ex(A.data_ptr(), D.data_ptr(), S, float(eps), evec.data_ptr(), evals.data_ptr(),
+                                  ws.data_ptr(), ws.numel(), ops._stream(), _FIEDLER_STEPWISE if stepwise else 0),
+          "usc_ncut_fiedler_ex")
+    return evec, evals
+
+
+def _finite_or_stepwise(vec, A, D, eps):
+    """`vec` (host f64[S]) when it is finite.  A one-launch tridiagonalisation whose workgroups lose sight of each other
+    gives up and returns a NaN eigenpair (ncut.hip, kSpinLimit): then solve once more with the stepwise path, and fail
+    loudly rather than hand a non-finite vector to the cut logic."""
+    if np.isfinite(vec).all():
+        return vec
+    warnings.warn(f"usc_ncut_fiedler: non-finite eigenvector (S = {len(vec)}), solving again with the stepwise "
+                  "tridiagonalisation", RuntimeWarning, stacklevel=3)
+    evec, _ = _fiedler(A, D, eps, stepwise=True)
     vec = evec.cpu().numpy()
+    if not np.isfinite(vec).all():
+        raise RuntimeError(f"usc_ncut_fiedler: non-finite eigenvector (S = {len(vec)}) from the stepwise solve too")
+    return vec
+
+
+def second_smallest_eigenvector(A, D, eps=1e-5):
+    """Generalized eigenvector #2 of (D - A, D) — `eigh(D - A, D, subset_by_index=[1, 2])` of the reference
+    (:138-146), computed on the device with LAPACK's sign.  A: device u8 affinity, D: device degree vector."""
+    evec, _ = _fiedler(A, D, eps)
+    vec = _finite_or_stepwise(evec.cpu().numpy(), A, D, eps)
     return np.copy(vec), vec
 
 
 def second_smallest_eigenvector_async(A, D, eps=1e-5, host=None):
     """The same solve without waiting for it: -> (pinned host f64[S], event).  The vector is valid once the event has
     fired (`event.synchronize()`); nothing else on the host waits, so several scenes' solves can be in flight on
-    their own streams from ONE host thread (`unscene3d_steps`)."""
+    their own streams from ONE host thread (`unscene3d_steps`).  The caller checks the vector is finite."""
     S = A.shape[0]
-    evec = torch.empty(S, dtype=torch.float64, device=A.device)
-    evals = torch.empty(2, dtype=torch.float64, device=A.device)
-    ws = torch.empty(lib.usc_ncut_fiedler_ws_bytes(S), dtype=torch.uint8, device=A.device)
-    check(lib.usc_ncut_fiedler(A.data_ptr(), D.data_ptr(), S, float(eps), evec.data_ptr(), evals.data_ptr(),
-                               ws.data_ptr(), ws.numel(), ops._stream()), "usc_ncut_fiedler")
+    evec, evals = _fiedler(A, D, eps)
     if host is None or host.numel() != S:
         host = torch.empty(S, dtype=torch.float64).pin_memory()     # callers in a loop pass their buffer back in
     host.copy_(evec, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record()
-    return host, ev, (evec, evals, ws)         # the device buffers stay referenced until the copy has run
+    return host, ev, (evec, evals)         # the device buffers stay referenced until the copy has run
 
 
 def get_salient_areas(second_smallest_vec):
@@ -279,7 +303,7 @@ def unscene3d_steps(aggregated_features, unique_segments, seg_connectivity, segm
         host, event, keep = second_smallest_eigenvector_async(A, D, eps, host=host)
         yield event
         event.synchronize()
-        vec = host.numpy().copy()
+        vec = _finite_or_stepwise(host.numpy().copy(), A, D, eps)
         del keep
         if eigvec_hook is not None:
             vec = eigvec_hook(it, vec)
