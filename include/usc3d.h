@@ -1059,6 +1059,17 @@ int usc_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_a
                    int64_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int64_t step, usc_stream_t s);
 
+/* The same step on the data-parallel SUM of the gradients: g = grad[i] * grad_scale, then usc_adamw_step's
+ * arithmetic.  grad_scale = 1.0f / (float)world (the division done once, in f32) reproduces torch's
+ * `flat.div_(world)` bit for bit: for a host scalar divisor torch multiplies by the f32 reciprocal — exact for a
+ * power of two, one rounding of 1/world otherwise (world 3: grad * 0x1.555556p-2f, not grad / 3.0f).
+ * write_back_grad != 0 stores g back (grad holds the mean afterwards; 32 B per parameter), 0 leaves the sum
+ * (28 B per parameter, and no averaging pass over the buffer before it). */
+int usc_adamw_step_scaled(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                          float grad_scale, int32_t write_back_grad,
+                          float lr, float beta1, float beta2, float eps, float weight_decay,
+                          int64_t step, usc_stream_t s);
+
 /* ------------------------------------------------------------------------
  * A1  elastic distortion of the training augmentation — the per-point half of
  * datasets/semseg.py:651-688 `elastic_distortion` (called from freemask_semseg.py:356-361):

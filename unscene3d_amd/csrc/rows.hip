@@ -885,6 +885,43 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 }
 
 
+// AdamW on the data-parallel SUM: the same step on g = grad * grad_scale, where grad holds the all-reduced sum and
+// grad_scale = 1.0f / (float)world — the product torch's `flat.div_(world)` computes for a host scalar divisor, so the
+// trajectory keeps the bits of div_ + adamw_kernel (the product is a statement of its own: under -ffp-contract=on it is
+// rounded once and never fused into the moment updates).  Takes the averaging pass (8 B per parameter) off the step:
+// reads p, g, m, v and writes p, m, v — 28 B per parameter, 32 B with kWriteBack (g stored back: p.grad holds the mean).
+template <bool kWriteBack>
+__global__ __launch_bounds__(256) void adamw_scaled_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v, int64_t n4,
+                                                          int64_t n, float grad_scale, float lr, float beta1, float beta2,
+                                                          float eps, float wd, float step_size, float bc2_sqrt) {
+  auto upd = [&](float& pp, float& graw, float& mm, float& vv) {
+    const float gg = graw * grad_scale;
+    graw = gg;
+    pp -= lr * wd * pp;
+    mm = mm + (1.0f - beta1) * (gg - mm);      // lerp(m, g, 1 - beta1)
+    vv = beta2 * vv + (1.0f - beta2) * gg * gg;
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    pp -= step_size * mm / denom;
+  };
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n4; j += (int64_t)gridDim.x * 256) {
+    float4 pv = reinterpret_cast<float4*>(p)[j], mv = reinterpret_cast<float4*>(m)[j], vv = reinterpret_cast<float4*>(v)[j];
+    float4 gv = reinterpret_cast<const float4*>(g)[j];
+    upd(pv.x, gv.x, mv.x, vv.x); upd(pv.y, gv.y, mv.y, vv.y); upd(pv.z, gv.z, mv.z, vv.z); upd(pv.w, gv.w, mv.w, vv.w);
+    reinterpret_cast<float4*>(p)[j] = pv; reinterpret_cast<float4*>(m)[j] = mv; reinterpret_cast<float4*>(v)[j] = vv;
+    if (kWriteBack) reinterpret_cast<float4*>(g)[j] = gv;
+  }
+  if (blockIdx.x == 0) {
+    const int64_t j = n4 * 4 + threadIdx.x;
+    if (j < n) {
+      float gj = g[j];
+      upd(p[j], gj, m[j], v[j]);
+      if (kWriteBack) g[j] = gj;
+    }
+  }
+}
+
+
 // ---------------------------------------------------------------------------
 // TILE FORM of the batch norm around a split-K convolution (maps of a few hundred to ~12 k rows: the U-Net's three
 // coarsest levels).  There every launch sits on its ~4.5 us floor, and a conv -> BN -> ReLU unit was FOUR of them after
@@ -1528,6 +1565,28 @@ int usc_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_a
   hipLaunchKernelGGL(adamw_kernel, dim3(stream_grid(n4 > 0 ? n4 : 1, 256)), dim3(256), 0, as_stream(s), param, grad,
                      exp_avg, exp_avg_sq, n4, n, lr, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt);
   USC_CHECK_LAUNCH("usc_adamw_step");
+  return USC_OK;
+}
+
+int usc_adamw_step_scaled(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float grad_scale,
+                          int32_t write_back_grad, float lr, float beta1, float beta2, float eps, float weight_decay,
+                          int64_t step, usc_stream_t s) {
+  USC_REQUIRE(n >= 0 && step >= 1, "usc_adamw_step_scaled: bad sizes");
+  if (n == 0) return USC_OK;
+  USC_REQUIRE(param && grad && exp_avg && exp_avg_sq, "usc_adamw_step_scaled: null pointer");
+  USC_REQUIRE((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
+              "usc_adamw_step_scaled: buffers must be 16-byte aligned");
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+  const int64_t n4 = n / 4;
+  const dim3 grid(stream_grid(n4 > 0 ? n4 : 1, 256));
+  if (write_back_grad)
+    hipLaunchKernelGGL((adamw_scaled_kernel<true>), grid, dim3(256), 0, as_stream(s), param, grad, exp_avg, exp_avg_sq,
+                       n4, n, grad_scale, lr, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt);
+  else
+    hipLaunchKernelGGL((adamw_scaled_kernel<false>), grid, dim3(256), 0, as_stream(s), param, grad, exp_avg, exp_avg_sq,
+                       n4, n, grad_scale, lr, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt);
+  USC_CHECK_LAUNCH("usc_adamw_step_scaled");
   return USC_OK;
 }
 

@@ -55,11 +55,19 @@ class BucketedGradReducer:
     started (more reports than learned) would race with the collective; it is detected, exchanged between the ranks
     with that step's collectives and raised on every rank two steps later (`RuntimeError`; the flag is read from pinned
     host memory without a stream synchronisation).
+
+    `average=False`: `finish()` leaves the SUM in the flat buffer (no `div_` pass over it) — for a consumer that scales
+    while it reads (`optim.FlatAdamW.enable_early_reduced`: `usc_adamw_step_scaled`).  `on_reduced(lo, hi, stream)`: called
+    once per bucket right behind that bucket's all-reduce, with the bucket's range of the flat buffer and the stream the
+    collective was issued on (None for host tensors: the call is synchronous) — work queued there on [lo, hi) sees the
+    reduced values.  The calls come in the order the collectives were issued: the same on every rank.
     """
 
-    def __init__(self, params, flat, world_size: int, bucket_bytes: int = 24 << 20):
+    def __init__(self, params, flat, world_size: int, bucket_bytes: int = 24 << 20, average: bool = True,
+                 on_reduced=None):
         self.params = list(params)
         self.flat, self.world = flat, world_size
+        self.average, self.on_reduced = bool(average), on_reduced
         self.bounds, self.members = [], []          # bucket -> (start, end) in flat, list of param indices
         self.bucket_of = {}
         off, start, cur = 0, 0, []
@@ -152,10 +160,14 @@ class BucketedGradReducer:
                     dist.all_reduce(self.flat[s:e])
                 self._on_stream = cs
                 self.launched[b] = True
+                if self.on_reduced is not None:
+                    self.on_reduced(s, e, cs)
                 return
             units.join_lane(self.flat.device)
         dist.all_reduce(self.flat[s:e])
         self.launched[b] = True
+        if self.on_reduced is not None:
+            self.on_reduced(s, e, torch.cuda.current_stream(self.flat.device) if self.flat.is_cuda else None)
 
     def _advance(self):
         while self.cursor < len(self.order) and self._complete(self.order[self.cursor]):
@@ -163,7 +175,7 @@ class BucketedGradReducer:
             self.cursor += 1
 
     def finish(self):
-        """After backward: reduce what has not been started (same order on every rank), wait, average."""
+        """After backward: reduce what has not been started (same order on every rank), wait, average (`average`)."""
         import torch.distributed as dist
         self.started_during_backward = sum(self.launched)
         # Late-write flags of EARLIER steps, each copied to pinned host memory behind its all-reduce.  A .item() on the
@@ -199,7 +211,8 @@ class BucketedGradReducer:
             torch.cuda.current_stream().wait_stream(cs)
             self._on_stream = None
         dist.all_reduce(self._late_flag, op=dist.ReduceOp.MAX)      # stream-ordered for RCCL; a 4-byte host wait for gloo
-        self.flat.div_(self.world)
+        if self.average:
+            self.flat.div_(self.world)
         if self._late_flag.is_cuda:
             # ONE pinned allocation for the reducer's lifetime, used as a ring (a slot is read two steps after it was
             # written).  Round 6: a fresh `torch.zeros(1).pin_memory()` per step asked the driver for pinned memory

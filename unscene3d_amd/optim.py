@@ -53,6 +53,12 @@ class FlatAdamW(torch.optim.Optimizer):
             off += p.numel()
         self._early_stream = None      # enable_early(): the stream the early ranges run on
         self._early_done = []          # [lo, hi) spans already stepped in the current step
+        self._reducer = None           # enable_early_reduced(): the gradient reducer whose buckets trigger their ranges
+        self._grad_scale, self._write_back = 1.0, False
+        self._joins = []               # streams early ranges of the current step were queued on (step() joins them)
+        self._views_checked = False    # _check_views() has run for the current step
+        self.callback_ranges = 0       # ranges stepped from a bucket callback in the last finished step (tests; tools)
+        self._callback_ranges = 0
 
     def _check_views(self):
         """Every p.data / p.grad must still be the view handed out in __init__ (module.to(), .float(),
@@ -73,6 +79,13 @@ class FlatAdamW(torch.optim.Optimizer):
     def _launch(self, lo, hi, step_no):
         g = self.param_groups[0]
         b1, b2 = g["betas"]
+        if self._reducer is not None:      # the flat gradient buffer holds the ranks' SUM: scaled while it is read
+            check(lib.usc_adamw_step_scaled(_ptr(self.flat_param[lo:hi]), _ptr(self.flat_grad[lo:hi]),
+                                            _ptr(self.exp_avg[lo:hi]), _ptr(self.exp_avg_sq[lo:hi]), hi - lo,
+                                            self._grad_scale, int(self._write_back), float(g["lr"]), float(b1), float(b2),
+                                            float(g["eps"]), float(g["weight_decay"]), step_no, _stream()),
+                  "usc_adamw_step_scaled")
+            return
         check(lib.usc_adamw_step(_ptr(self.flat_param[lo:hi]), _ptr(self.flat_grad[lo:hi]), _ptr(self.exp_avg[lo:hi]),
                                  _ptr(self.exp_avg_sq[lo:hi]), hi - lo, float(g["lr"]), float(b1), float(b2), float(g["eps"]),
                                  float(g["weight_decay"]), step_no, _stream()), "usc_adamw_step")
@@ -84,16 +97,75 @@ class FlatAdamW(torch.optim.Optimizer):
         weight-gradient lane; step() covers the rest and lets the caller's stream wait for `stream`.  Same kernel, same
         per-element arithmetic: the trajectory keeps its bits.  What it takes off the end of the step: the 0.18 ms of the
         one 1.1 GB AdamW launch (39.6 M parameters x 28 B), of which the backbone's 95 % now run beside the backward pass.
-        Not with a gradient reducer: a reduced bucket is what would have to trigger the range."""
+        Not with a gradient reducer: a reduced bucket is what has to trigger the range — enable_early_reduced()."""
         from . import ops
+        if self._reducer is not None:
+            raise RuntimeError("FlatAdamW.enable_early: enable_early_reduced() is on (one trigger per optimizer: either "
+                               "the step program's final reports or a reducer's buckets); disable_early() first")
         self._early_stream = stream
         ops.PARAMS_FINAL_HOOK = self._on_final
 
+    def enable_early_reduced(self, reducer, write_back_grad: bool = False):
+        """Optimizer in the backward pass under a gradient reducer (any world size — the same program at N = 1 over a
+        one-rank group): `reducer` (ddp.BucketedGradReducer over this optimizer's flat gradient buffer, built with
+        `average=False`) calls back right behind every bucket's all-reduce, and the bucket's range is stepped at once on
+        the stream the collective ran on, with `usc_adamw_step_scaled(grad_scale = 1 / world)`: the kernel reads the SUM
+        and scales it, so the averaging pass over the whole buffer at the end of `finish()` is gone and the one large
+        AdamW launch at the end of the step is cut into the buckets, most of them beside the backward pass.  The scale is
+        the f32 reciprocal torch's `div_` multiplies by: parameters and moments keep the bits of `div_` + `step()`.
+        write_back_grad: store the mean back into the gradient buffer (else it holds the sum after the step).
+        A bucket is complete when every kernel that writes its gradients is queued, and every backward of this package
+        queues a layer's input gradient — the last reader of its weights — before it reports the weight gradient."""
+        if self._early_stream is not None:
+            raise RuntimeError("FlatAdamW.enable_early_reduced: enable_early() is on; disable_early() first")
+        if self._reducer is not None:
+            raise RuntimeError("FlatAdamW.enable_early_reduced: already registered with a reducer")
+        if reducer.flat.data_ptr() != self.flat_grad.data_ptr() or reducer.flat.numel() != self.flat_grad.numel():
+            raise RuntimeError("FlatAdamW.enable_early_reduced: the reducer works on another gradient buffer")
+        if reducer.average or reducer.on_reduced is not None:
+            raise RuntimeError("FlatAdamW.enable_early_reduced: build the reducer with average=False and no on_reduced "
+                               "(this optimizer scales the sum itself and registers its own callback)")
+        import numpy as np
+        self._reducer = reducer
+        self._grad_scale = float(np.float32(1.0) / np.float32(reducer.world))     # what flat.div_(world) multiplies by
+        self._write_back = bool(write_back_grad)
+        reducer.on_reduced = self._on_reduced
+
     def disable_early(self):
+        """Back to one launch in step().  A reducer registered by enable_early_reduced() averages again itself."""
         from . import ops
         if ops.PARAMS_FINAL_HOOK == self._on_final:
             ops.PARAMS_FINAL_HOOK = None
         self._early_stream = None
+        if self._reducer is not None:
+            if self._early_done:
+                raise RuntimeError("FlatAdamW.disable_early: ranges of the running step were already stepped on the "
+                                   "reduced sum; call step() first")
+            self._reducer.on_reduced, self._reducer.average = None, True
+            self._reducer = None
+
+    def _claim(self, spans):
+        """Bookkeeping in front of an early launch: the views are checked once per step, and a span is stepped once."""
+        if not self._views_checked:
+            self._check_views()
+            self._views_checked = True
+        for lo, hi in spans:
+            if any(lo < dhi and dlo < hi for dlo, dhi in self._early_done):
+                raise RuntimeError(f"FlatAdamW: parameters [{lo}, {hi}) were already stepped in this step (two backward "
+                                   "passes before one step()?); call step() after every backward pass, or disable_early()")
+
+    @torch.no_grad()
+    def _on_reduced(self, lo, hi, stream):
+        self._claim([(lo, hi)])
+        if stream is None:
+            self._launch(lo, hi, self.steps + 1)
+        else:
+            with torch.cuda.stream(stream):
+                self._launch(lo, hi, self.steps + 1)
+            if all(stream.cuda_stream != s.cuda_stream for s in self._joins):
+                self._joins.append(stream)
+        self._early_done.append((lo, hi))
+        self._callback_ranges += 1
 
     @torch.no_grad()
     def _on_final(self, params):
@@ -110,6 +182,7 @@ class FlatAdamW(torch.optim.Optimizer):
             else:
                 merged.append([lo, hi])
         from . import units
+        self._claim(merged)
         cur = torch.cuda.current_stream()
         ev = torch.cuda.Event()
         ev.record(cur)
@@ -121,17 +194,24 @@ class FlatAdamW(torch.optim.Optimizer):
             for lo, hi in merged:
                 self._launch(lo, hi, self.steps + 1)
         self._early_done.extend((lo, hi) for lo, hi in merged)
+        if all(st.cuda_stream != s.cuda_stream for s in self._joins):
+            self._joins.append(st)
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        self._check_views()
+        if not self._views_checked:
+            self._check_views()
+        self._views_checked = False
         self.steps += 1
         done, self._early_done = sorted(self._early_done), []
+        joins, self._joins = self._joins, []
+        self.callback_ranges, self._callback_ranges = self._callback_ranges, 0
         if not done:
             self._launch(0, self.flat_param.numel(), self.steps)
             return loss
-        torch.cuda.current_stream().wait_stream(self._early_stream)      # the early ranges' updates are in before the next forward
+        for st in joins:               # the early ranges' updates are in before the next forward
+            torch.cuda.current_stream().wait_stream(st)
         pos = 0
         for lo, hi in done + [(self.flat_param.numel(), self.flat_param.numel())]:
             if lo > pos:

@@ -287,10 +287,24 @@ class InstanceSegmentation(nn.Module):
         v["bbox_preds"], v["bbox_gt"] = {}, {}
         return out
 
-    def configure_optimizers(self, steps_per_epoch: int, epochs: int = None):
+    def configure_optimizers(self, steps_per_epoch: int, epochs: int = None, *, flat: bool = False,
+                             total_steps: int = None):
+        """Default: the reference's pair (:953-966), torch.optim.AdamW over all parameters + OneCycleLR per batch.
+        flat=True: `optim.FlatAdamW` over the parameters that receive gradients (the backbone's `final` head is not part
+        of the forward pass) on one flat gradient buffer (`ddp.flatten_grads` layout, the buffer the gradient exchange
+        works on) -> (optimizer, scheduler, flat gradient buffer).  total_steps: the schedule's length, instead of
+        epochs x steps_per_epoch."""
         o = self.config.optimizer
+        span = (dict(total_steps=int(total_steps)) if total_steps is not None else
+                dict(epochs=epochs or self.config.trainer.max_epochs, steps_per_epoch=steps_per_epoch))
+        if flat:
+            from ..ddp import flatten_grads
+            from ..optim import FlatAdamW
+            params = [p for n, p in self.named_parameters() if ".backbone.final." not in n]
+            flat_grad = flatten_grads(params)
+            optimizer = FlatAdamW(params, lr=o.lr, flat_grad=flat_grad)      # same defaults as torch.optim.AdamW
+            scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=o.lr, **span)
+            return optimizer, scheduler, flat_grad
         optimizer = torch.optim.AdamW(self.parameters(), lr=o.lr)
-        scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=o.lr,
-                                                        epochs=epochs or self.config.trainer.max_epochs,
-                                                        steps_per_epoch=steps_per_epoch)
+        scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=o.lr, **span)
         return optimizer, scheduler
