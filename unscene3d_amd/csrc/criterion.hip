@@ -377,10 +377,18 @@ int usc_lsap_batch(const float* cost, int32_t n_prob, int32_t nr, int32_t nc, in
 // ===================================================================================================
 // The set criterion itself (reference models/matcher.py:98-168 cost matrices; models/criterion.py:22-73 dice / BCE,
 // :138-216 label + mask losses) for all prediction levels of one scene in a handful of launches:
-//   crit_partial   per (level, 32-row chunk): sum_s softplus(x), sum_s sigmoid(x), and per target t
-//                  sum_s x*tm[t,s], sum_s sigmoid(x)*tm[t,s]           (x = mask logits [S, Q], one query per lane)
-//   crit_cost      chunks summed in order -> cost_mask = (sum softplus - sum x*tm)/S  (== mean BCE: softplus(-x) =
-//                  softplus(x) - x), cost_dice = 1 - (2 N + 1)/(sum sigmoid + |tm| + 1), cost_class = -softmax[label]
+//   crit_partial   per (level, 32-row chunk): sum_s softplus(x), sum_s sigmoid(x), and per target t sum_s x*tm[t,s],
+//                  sum_s sigmoid(x)*tm[t,s] and the BCE numerator sum_s (tm[t,s] ? softplus(-x) : softplus(x))
+//                  (x = mask logits [S, Q], one query per lane)
+//   crit_cost      chunks summed in order.  The pair BCE exists twice:
+//                  * in the assignment cost as (sum softplus - sum x*tm)/S (softplus(-x) = softplus(x) - x).  On a
+//                    confidently predicted target the two sums are ~10 |tm| and their difference ~1e-4 S, so this form
+//                    is ~2e-3 off THERE — 1e-6 of the cost matrix's range, which is all an assignment needs — and it
+//                    is kept bit for bit: every assignment, and with it every gradient of a training run, stays what
+//                    it was (an ulp on a cost flips near-ties between the decoder's similar queries);
+//                  * in cmask, which IS loss_mask on the matched pairs, as the numerator added term by term like the
+//                    reference's pos @ tm.T + neg @ (1 - tm).T: nothing cancels.
+//                  cost_dice = 1 - (2 N + 1)/(sum sigmoid + |tm| + 1), cost_class = -softmax[label]
 //                  -> C = w_mask*cost_mask + w_class*cost_class + w_dice*cost_dice  [L, Q, T]
 //   usc_lsap_batch the assignment (above)
 //   crit_loss      the matcher's cost_mask / cost_dice ARE the mask losses of a (query, target) pair: the loss of a
@@ -394,7 +402,8 @@ constexpr int kCritMaxLevels = 16;
 constexpr int kCritCols = 128;          // queries per level (one per lane of the 128-thread workgroups)
 struct CritLevels { const float* x[kCritMaxLevels]; float* dx[kCritMaxLevels]; };
 
-__device__ inline float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+// workspace rows per (level, chunk): sum softplus | sum sigmoid | per target: sum x*tm | sum sigmoid*tm | BCE numerator
+template <int TMAX> constexpr int kCritRows = 3 * TMAX + 2;
 __device__ inline float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 
 // tm u8[T, S] -> bits u32[S] (bit t = tm[t, s] != 0), cnt i32[T] += popcount (integer atomics: exact)
@@ -417,15 +426,18 @@ __global__ __launch_bounds__(128) void crit_partial_kernel(CritLevels lv, int ld
                                                            float* __restrict__ partial) {
   const int q = threadIdx.x, chunk = blockIdx.x, l = blockIdx.y;
   const float* __restrict__ X = lv.x[l];
-  float nsum = 0.f, ssum = 0.f, xs[TMAX], gs[TMAX];
+  float nsum = 0.f, ssum = 0.f, xs[TMAX], gs[TMAX], bce[TMAX];
 #pragma unroll
-  for (int t = 0; t < TMAX; ++t) { xs[t] = 0.f; gs[t] = 0.f; }
+  for (int t = 0; t < TMAX; ++t) { xs[t] = 0.f; gs[t] = 0.f; bce[t] = 0.f; }
   const int s0 = chunk * 32, s1 = s0 + 32 < S ? s0 + 32 : S;
   if (q < Q) {
     for (int s = s0; s < s1; ++s) {
       const float x = X[(int64_t)s * ld + q];
       const uint32_t b = bits[s];
-      const float sp = softplus_f(x), sg = sigmoid_f(x);
+      // softplus(+-x) = max(+-x, 0) + lt.  An infinite or NaN logit poisons every pair cost of its query, as the
+      // reference's (1 - y) x + ... does (0 * inf): the assignment then reports status 1 and the run stops
+      const float lt = fabsf(x) < INFINITY ? log1pf(expf(-fabsf(x))) : NAN;
+      const float sp = fmaxf(x, 0.f) + lt, sn = fmaxf(-x, 0.f) + lt, sg = sigmoid_f(x);
       nsum += sp;
       ssum += sg;
 #pragma unroll
@@ -433,14 +445,19 @@ __global__ __launch_bounds__(128) void crit_partial_kernel(CritLevels lv, int ld
         const bool m = (b >> t) & 1u;
         xs[t] += m ? x : 0.f;
         gs[t] += m ? sg : 0.f;
+        bce[t] += m ? sn : sp;
       }
     }
   }
-  float* dst = partial + ((int64_t)(l * nchunk + chunk) * (2 * TMAX + 2)) * kCritCols + q;
+  float* dst = partial + ((int64_t)(l * nchunk + chunk) * kCritRows<TMAX>) * kCritCols + q;
   dst[0] = nsum;
   dst[kCritCols] = ssum;
 #pragma unroll
-  for (int t = 0; t < TMAX; ++t) { dst[(2 + t) * kCritCols] = xs[t]; dst[(2 + TMAX + t) * kCritCols] = gs[t]; }
+  for (int t = 0; t < TMAX; ++t) {
+    dst[(2 + t) * kCritCols] = xs[t];
+    dst[(2 + TMAX + t) * kCritCols] = gs[t];
+    dst[(2 + 2 * TMAX + t) * kCritCols] = bce[t];
+  }
 }
 
 struct CritCostArgs {
@@ -460,15 +477,19 @@ template <int TMAX>
 __global__ __launch_bounds__(128) void crit_cost_kernel(CritCostArgs a) {
   const int q = threadIdx.x, l = blockIdx.x;
   if (q >= a.Q) return;
-  float nsum = 0.f, ssum = 0.f, xs[TMAX], gs[TMAX];
+  float nsum = 0.f, ssum = 0.f, xs[TMAX], gs[TMAX], bce[TMAX];
 #pragma unroll
-  for (int t = 0; t < TMAX; ++t) { xs[t] = 0.f; gs[t] = 0.f; }
+  for (int t = 0; t < TMAX; ++t) { xs[t] = 0.f; gs[t] = 0.f; bce[t] = 0.f; }
   for (int c = 0; c < a.nchunk; ++c) {
-    const float* src = a.partial + ((int64_t)(l * a.nchunk + c) * (2 * TMAX + 2)) * kCritCols + q;
+    const float* src = a.partial + ((int64_t)(l * a.nchunk + c) * kCritRows<TMAX>) * kCritCols + q;
     nsum += src[0];
     ssum += src[kCritCols];
 #pragma unroll
-    for (int t = 0; t < TMAX; ++t) { xs[t] += src[(2 + t) * kCritCols]; gs[t] += src[(2 + TMAX + t) * kCritCols]; }
+    for (int t = 0; t < TMAX; ++t) {
+      xs[t] += src[(2 + t) * kCritCols];
+      gs[t] += src[(2 + TMAX + t) * kCritCols];
+      bce[t] += src[(2 + 2 * TMAX + t) * kCritCols];
+    }
   }
   // class part: log softmax over the C logits of this query
   const float* lg = a.logits + (int64_t)l * a.ls_level + (int64_t)q * a.ls_q;
@@ -489,9 +510,9 @@ __global__ __launch_bounds__(128) void crit_cost_kernel(CritCostArgs a) {
       // report status 1, which the host side raises on (scipy raises ValueError on such a matrix, matcher.py:163)
       const bool bad = lab != 253 && (lab < 0 || lab >= a.C);
       const float cclass = lab == 253 ? -1.f : bad ? NAN : -(expf(lg[lab] - mx) / se);
-      const float cm = (nsum - xs[t]) / (float)a.S;
+      const float cm = (nsum - xs[t]) / (float)a.S;          // the assignment's BCE (header: kept bit for bit)
       const float cd = 1.f - (2.f * gs[t] + 1.f) / (ssum + (float)a.cnt[t] + 1.f);
-      a.cmask[o + t] = cm;
+      a.cmask[o + t] = bce[t] / (float)a.S;                  // the loss's BCE
       a.cdice[o + t] = cd;
       a.nmat[o + t] = gs[t];
       a.cost[o + t] = (a.w_mask * cm + a.w_class * cclass) + a.w_dice * cd;
@@ -531,15 +552,18 @@ __global__ __launch_bounds__(128) void crit_loss_kernel(const float* __restrict_
     __syncthreads();
   }
   if (q == 0) {
-    float lm = 0.f, ldice = 0.f;
+    // the BCE terms of a level can be equal to the last bit (identical queries early in training): added in f32, T of
+    // them drift by T/2 ulps; <= 32 terms on one thread in f64 keep the mean at the terms' own accuracy
+    double lm = 0.0;
+    float ldice = 0.f;
     for (int t = 0; t < T; ++t) {
       const int64_t o = ((int64_t)l * Q + src[(int64_t)l * T + t]) * T + tid[(int64_t)l * T + t];
-      lm += cmask[o];
+      lm += (double)cmask[o];
       ldice += cdice[o];
     }
     part[l * 4 + 0] = rnum[0];
     part[l * 4 + 1] = rden[0];
-    part[l * 4 + 2] = lm / (float)T;
+    part[l * 4 + 2] = (float)(lm / (double)T);
     part[l * 4 + 3] = ldice / (float)T;
   }
 }
@@ -631,7 +655,7 @@ extern "C" {
 
 int64_t usc_criterion_ws_bytes(int32_t L, int32_t S, int32_t T) {
   const int64_t nchunk = usc::ceil_div(S, 32);
-  return usc::align_up((int64_t)L * nchunk * (2 * usc::tmax_of(T) + 2) * usc::kCritCols * 4, 256);
+  return usc::align_up((int64_t)L * nchunk * (3 * usc::tmax_of(T) + 2) * usc::kCritCols * 4, 256);
 }
 
 int usc_criterion_target_bits(const uint8_t* tm, int32_t T, int32_t S, uint32_t* bits, int32_t* cnt, usc_stream_t s) {
