@@ -765,6 +765,32 @@ int usc_criterion_backward(const float* const* masks, float* const* dmasks, int3
                            const int32_t* tcls, const float* class_w, const float* gtable,
                            const float* den_tot, int32_t C, int64_t ls_level, int64_t ls_q,
                            float* dlogits, usc_stream_t s);
+/* DropLoss inside the device criterion (reference models/criterion.py:194-200: a matched pair whose prediction
+ * (x > 0) overlaps its target with IoU below the threshold gets weight 0 in loss_mask and loss_dice; the divisor stays
+ * T).  Replaces the torch op chain `(fg * tm).sum(1) / (fg + tm).sum(1) >= thresh` on the gathered [T, S] masks.
+ *   usc_criterion_drop_counts  after usc_lsap_batch: counts i32[2,L,T] = per matched pair (row order of src / tid)
+ *                              I = |pred & target| and F = |pred|; integer sums, exact.  counts is zeroed here
+ *   usc_criterion_losses_ex    usc_criterion_losses that also takes counts, cnt i32[T] (usc_criterion_target_bits) and
+ *                              the threshold and writes wts f32[L,T] = 1 if U > 0 and f32(I) / f32(U) >= thresh else 0,
+ *                              U = F + cnt - I, applied inside the same fixed-order sums.  counts = cnt = wts = NULL:
+ *                              exactly usc_criterion_losses
+ *   usc_criterion_backward_ex  usc_criterion_backward that also takes wts: the dmasks column of a pair with weight 0
+ *                              is exactly 0.  wts = NULL: exactly usc_criterion_backward */
+int usc_criterion_drop_counts(const float* const* masks, int32_t L, int32_t ld, int32_t S,
+                              int32_t Q, int32_t T, const uint32_t* bits, const int64_t* src,
+                              const int64_t* tid, int32_t* counts, usc_stream_t s);
+int usc_criterion_losses_ex(const float* cmask, const float* cdice, const float* logp,
+                            const int64_t* src, const int64_t* tid, const int64_t* labels,
+                            const float* class_w, int32_t L, int32_t Q, int32_t T, int32_t C,
+                            int32_t noobj, int32_t* tcls, float* part, const int32_t* counts,
+                            const int32_t* cnt, float thresh, float* wts, usc_stream_t s);
+int usc_criterion_backward_ex(const float* const* masks, float* const* dmasks, int32_t L,
+                              int32_t ld, int32_t S, int32_t Q, int32_t T, const uint32_t* bits,
+                              const int32_t* cnt, const int64_t* src, const int64_t* tid,
+                              const float* nmat, const float* ssum, const float* logp,
+                              const int32_t* tcls, const float* class_w, const float* gtable,
+                              const float* den_tot, int32_t C, int64_t ls_level, int64_t ls_q,
+                              float* dlogits, const float* wts, usc_stream_t s);
 
 /* Linear layer on a handful of rows (the 100 decoder queries):
  *   y[M,N] = x[M,K] W[N,K]^T + b[N]   (b may be NULL);  N, K multiples of 32.

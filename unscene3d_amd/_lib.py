@@ -183,6 +183,11 @@ SIGNATURES = {
     "usc_criterion_table": (C.c_int, [_p, _i32, _i32, _p, _p, _p]),
     "usc_criterion_backward": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                          _i32, _i64, _i64, _p, _p]),
+    "usc_criterion_drop_counts": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
+    "usc_criterion_losses_ex": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _f32,
+                                          _p, _p]),
+    "usc_criterion_backward_ex": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                            _p, _i32, _i64, _i64, _p, _p, _p]),
     "usc_self_attn_fwd": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p]),
     "usc_self_attn_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
     "usc_linear_fwd": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p]),

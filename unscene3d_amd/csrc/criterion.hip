@@ -394,6 +394,11 @@ int usc_lsap_batch(const float* cost, int32_t n_prob, int32_t nr, int32_t nc, in
 //   crit_loss      the matcher's cost_mask / cost_dice ARE the mask losses of a (query, target) pair: the loss of a
 //                  level is their sum over the matched pairs / T; weighted cross entropy over the queries
 //   crit_bwd_*     d loss / d mask logits (matched columns only, everything else exactly 0) and d loss / d class logits
+//   crit_drop_counts  DropLoss only (reference models/criterion.py:194-200), after the assignment: per matched pair the
+//                  integer counts I = |pred & target| and F = |pred|, pred = (x > 0), summed per 32-row chunk and added
+//                  with integer atomics (exact, order-free).  crit_loss<true> turns them into the 0 / 1 pair weights
+//                  w = [U > 0 and f32(I) / f32(U) >= thresh], U = F + |target| - I, and leaves dropped pairs out of the
+//                  same fixed-order sums; crit_bwd_masks<true> writes their columns as exact zeros
 // Every sum has a fixed order; the target masks travel as one bit per (row, target) (T <= 32).
 namespace usc {
 namespace {
@@ -520,12 +525,51 @@ __global__ __launch_bounds__(128) void crit_cost_kernel(CritCostArgs a) {
   }
 }
 
-// one workgroup per level: losses of the matched pairs + weighted cross entropy
+// DropLoss: overlap counts of the matched pairs (reference models/criterion.py:196-197: `pred_foreground * target_mask`
+// and `pred_foreground + target_mask` on bool tensors are AND and OR).  Grid (32-row chunk, level), one column per
+// thread; a matched column counts its foreground rows (x > 0: a NaN logit is not foreground) and those of them inside
+// its target, in integers, and adds them to counts i32[2, L, T] (I | F, pair order = the row order of src / tid), which
+// the caller has zeroed.  Columns >= Q are never read.
+__global__ __launch_bounds__(128) void crit_drop_counts_kernel(CritLevels lv, int ld, int S, int Q, int T, int L,
+                                                               const uint32_t* __restrict__ bits,
+                                                               const int64_t* __restrict__ src,
+                                                               const int64_t* __restrict__ tid,
+                                                               int32_t* __restrict__ counts) {
+  __shared__ int pmap[kCritCols];
+  const int col = threadIdx.x, chunk = blockIdx.x, l = blockIdx.y;
+  pmap[col] = -1;
+  __syncthreads();
+  if (col < T) {
+    const int q = (int)src[(int64_t)l * T + col];
+    if (q >= 0 && q < kCritCols) pmap[q] = col;
+  }
+  __syncthreads();
+  const int p = col < Q ? pmap[col] : -1;
+  if (p < 0) return;
+  const int t = (int)tid[(int64_t)l * T + p] & 31;
+  const float* __restrict__ X = lv.x[l];
+  const int s0 = chunk * 32, s1 = s0 + 32 < S ? s0 + 32 : S;
+  int nI = 0, nF = 0;
+  for (int s = s0; s < s1; ++s) {
+    const bool fg = X[(int64_t)s * ld + col] > 0.f;
+    nF += fg ? 1 : 0;
+    nI += fg ? (int)((bits[s] >> t) & 1u) : 0;
+  }
+  if (nI) atomicAdd(&counts[(int64_t)l * T + p], nI);
+  if (nF) atomicAdd(&counts[((int64_t)L + l) * T + p], nF);
+}
+
+// one workgroup per level: losses of the matched pairs + weighted cross entropy.  DROP: the pair weights of DropLoss
+// from `counts` (crit_drop_counts) and the target sizes `cnt`, written to wts f32[L, T] in pair order
+template <bool DROP>
 __global__ __launch_bounds__(128) void crit_loss_kernel(const float* __restrict__ cmask, const float* __restrict__ cdice,
                                                         const float* __restrict__ logp, const int64_t* __restrict__ src,
                                                         const int64_t* __restrict__ tid, const int64_t* __restrict__ labels,
                                                         const float* __restrict__ class_w, int Q, int T, int C, int noobj,
-                                                        int32_t* __restrict__ tcls, float* __restrict__ part) {
+                                                        int32_t* __restrict__ tcls, float* __restrict__ part,
+                                                        const int32_t* __restrict__ counts,
+                                                        const int32_t* __restrict__ cnt, float thresh,
+                                                        float* __restrict__ wts) {
   __shared__ int tc[kCritCols];
   __shared__ float rnum[kCritCols], rden[kCritCols];
   const int q = threadIdx.x, l = blockIdx.x;
@@ -558,6 +602,16 @@ __global__ __launch_bounds__(128) void crit_loss_kernel(const float* __restrict_
     float ldice = 0.f;
     for (int t = 0; t < T; ++t) {
       const int64_t o = ((int64_t)l * Q + src[(int64_t)l * T + t]) * T + tid[(int64_t)l * T + t];
+      if (DROP) {
+        // torch divides the two integer sums in float32 and compares with the float32 threshold; 0 / 0 = NaN is
+        // dropped.  Both counts are below 2^24, so the float64 quotient rounded to float32 IS the correctly rounded
+        // float32 quotient (53 >= 2 * 24 + 2 bits), whatever the division the compiler emits for float32
+        const int I = counts[(int64_t)l * T + t], F = counts[((int64_t)gridDim.x + l) * T + t];
+        const int U = F + cnt[tid[(int64_t)l * T + t]] - I;
+        const bool keep = U > 0 && (float)((double)I / (double)U) >= thresh;
+        wts[(int64_t)l * T + t] = keep ? 1.f : 0.f;
+        if (!keep) continue;               // a dropped pair adds exactly 0 (also where its terms are not finite)
+      }
       lm += (double)cmask[o];
       ldice += cdice[o];
     }
@@ -591,15 +645,19 @@ struct CritBwdArgs {
   const int64_t* src; const int64_t* tid;
   const float* nmat; const float* ssum;
   const float* gtable;      // d total / d table [L, 4]
+  const float* wts;         // DropLoss: pair weights [L, T] (crit_bwd_masks_kernel<true> only)
 };
 
-// d loss / d mask logits of every level: grid (chunk, level), one column per thread, full padded width written
+// d loss / d mask logits of every level: grid (chunk, level), one column per thread, full padded width written.
+// DROP: the column of a pair with weight 0 is written as zeros, like an unmatched one
+template <bool DROP>
 __global__ __launch_bounds__(128) void crit_bwd_masks_kernel(CritBwdArgs a) {
   __shared__ int qmap[kCritCols];
   const int col = threadIdx.x, chunk = blockIdx.x, l = blockIdx.y;
   qmap[col] = -1;
   __syncthreads();
-  if (col < a.T) qmap[(int)a.src[(int64_t)l * a.T + col]] = (int)a.tid[(int64_t)l * a.T + col];
+  if (col < a.T && !(DROP && a.wts[(int64_t)l * a.T + col] == 0.f))
+    qmap[(int)a.src[(int64_t)l * a.T + col]] = (int)a.tid[(int64_t)l * a.T + col];
   __syncthreads();
   if (col >= a.ld) return;
   const int t = col < a.Q ? qmap[col] : -1;
@@ -694,17 +752,49 @@ int usc_criterion_costs(const float* const* masks, int32_t L, int32_t ld, int32_
   return USC_OK;
 }
 
-int usc_criterion_losses(const float* cmask, const float* cdice, const float* logp, const int64_t* src, const int64_t* tid,
-                         const int64_t* labels, const float* class_w, int32_t L, int32_t Q, int32_t T, int32_t C,
-                         int32_t noobj, int32_t* tcls, float* part, usc_stream_t s) {
+int usc_criterion_drop_counts(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
+                              const uint32_t* bits, const int64_t* src, const int64_t* tid, int32_t* counts,
+                              usc_stream_t s) {
+  using namespace usc;
+  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && T >= 1 && T <= 32 && T <= Q && S >= 1,
+              "usc_criterion_drop_counts: needs <= 16 levels, <= 128 queries, 1..32 targets");
+  USC_REQUIRE(masks && bits && src && tid && counts, "usc_criterion_drop_counts: null argument");
+  CritLevels lv{};
+  for (int l = 0; l < L; ++l) { USC_REQUIRE(masks[l], "usc_criterion_drop_counts: null level"); lv.x[l] = masks[l]; }
+  hipStream_t st = as_stream(s);
+  (void)hipMemsetAsync(counts, 0, (size_t)2 * L * T * 4, st);
+  hipLaunchKernelGGL(crit_drop_counts_kernel, dim3((unsigned)ceil_div(S, 32), L), dim3(128), 0, st, lv, (int)ld, (int)S,
+                     (int)Q, (int)T, (int)L, bits, src, tid, counts);
+  USC_CHECK_LAUNCH("usc_criterion_drop_counts");
+  return USC_OK;
+}
+
+int usc_criterion_losses_ex(const float* cmask, const float* cdice, const float* logp, const int64_t* src,
+                            const int64_t* tid, const int64_t* labels, const float* class_w, int32_t L, int32_t Q,
+                            int32_t T, int32_t C, int32_t noobj, int32_t* tcls, float* part, const int32_t* counts,
+                            const int32_t* cnt, float thresh, float* wts, usc_stream_t s) {
   using namespace usc;
   USC_REQUIRE(L >= 1 && Q >= 1 && Q <= kCritCols && T >= 1 && T <= 32 && T <= Q && C >= 1 && noobj >= 0 && noobj < C,
               "usc_criterion_losses: bad sizes");
   USC_REQUIRE(cmask && cdice && logp && src && tid && labels && class_w && tcls && part, "usc_criterion_losses: null argument");
-  hipLaunchKernelGGL(crit_loss_kernel, dim3(L), dim3(128), 0, as_stream(s), cmask, cdice, logp, src, tid, labels, class_w,
-                     (int)Q, (int)T, (int)C, (int)noobj, tcls, part);
+  USC_REQUIRE((counts && cnt && wts) || (!counts && !cnt && !wts),
+              "usc_criterion_losses_ex: counts, cnt and wts go together (all three, or none for no DropLoss)");
+  if (wts)
+    hipLaunchKernelGGL(crit_loss_kernel<true>, dim3(L), dim3(128), 0, as_stream(s), cmask, cdice, logp, src, tid, labels,
+                       class_w, (int)Q, (int)T, (int)C, (int)noobj, tcls, part, counts, cnt, thresh, wts);
+  else
+    hipLaunchKernelGGL(crit_loss_kernel<false>, dim3(L), dim3(128), 0, as_stream(s), cmask, cdice, logp, src, tid, labels,
+                       class_w, (int)Q, (int)T, (int)C, (int)noobj, tcls, part, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr, 0.f, (float*)nullptr);
   USC_CHECK_LAUNCH("usc_criterion_losses");
   return USC_OK;
+}
+
+int usc_criterion_losses(const float* cmask, const float* cdice, const float* logp, const int64_t* src, const int64_t* tid,
+                         const int64_t* labels, const float* class_w, int32_t L, int32_t Q, int32_t T, int32_t C,
+                         int32_t noobj, int32_t* tcls, float* part, usc_stream_t s) {
+  return usc_criterion_losses_ex(cmask, cdice, logp, src, tid, labels, class_w, L, Q, T, C, noobj, tcls, part, nullptr,
+                                 nullptr, 0.f, nullptr, s);
 }
 
 int usc_criterion_table(const float* parts, int32_t B, int32_t L, float* table, float* den_tot, usc_stream_t s) {
@@ -716,11 +806,11 @@ int usc_criterion_table(const float* parts, int32_t B, int32_t L, float* table, 
   return USC_OK;
 }
 
-int usc_criterion_backward(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S, int32_t Q,
-                           int32_t T, const uint32_t* bits, const int32_t* cnt, const int64_t* src, const int64_t* tid,
-                           const float* nmat, const float* ssum, const float* logp, const int32_t* tcls,
-                           const float* class_w, const float* gtable, const float* den_tot, int32_t C, int64_t ls_level,
-                           int64_t ls_q, float* dlogits, usc_stream_t s) {
+int usc_criterion_backward_ex(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S, int32_t Q,
+                              int32_t T, const uint32_t* bits, const int32_t* cnt, const int64_t* src, const int64_t* tid,
+                              const float* nmat, const float* ssum, const float* logp, const int32_t* tcls,
+                              const float* class_w, const float* gtable, const float* den_tot, int32_t C, int64_t ls_level,
+                              int64_t ls_q, float* dlogits, const float* wts, usc_stream_t s) {
   using namespace usc;
   USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && ld <= kCritCols && T >= 1 &&
                   T <= 32 && S >= 1 && C >= 1, "usc_criterion_backward: bad sizes");
@@ -733,13 +823,23 @@ int usc_criterion_backward(const float* const* masks, float* const* dmasks, int3
     a.lv.dx[l] = dmasks[l];
   }
   a.ld = ld; a.S = S; a.Q = Q; a.T = T; a.nchunk = (int)ceil_div(S, 32);
-  a.bits = bits; a.cnt = cnt; a.src = src; a.tid = tid; a.nmat = nmat; a.ssum = ssum; a.gtable = gtable;
+  a.bits = bits; a.cnt = cnt; a.src = src; a.tid = tid; a.nmat = nmat; a.ssum = ssum; a.gtable = gtable; a.wts = wts;
   hipStream_t st = as_stream(s);
-  hipLaunchKernelGGL(crit_bwd_masks_kernel, dim3(a.nchunk, L), dim3(128), 0, st, a);
+  if (wts) hipLaunchKernelGGL(crit_bwd_masks_kernel<true>, dim3(a.nchunk, L), dim3(128), 0, st, a);
+  else hipLaunchKernelGGL(crit_bwd_masks_kernel<false>, dim3(a.nchunk, L), dim3(128), 0, st, a);
   hipLaunchKernelGGL(crit_bwd_logits_kernel, dim3(L), dim3(128), 0, st, logp, tcls, class_w, gtable, den_tot, (int)Q, (int)C,
                      ls_level, ls_q, dlogits);
   USC_CHECK_LAUNCH("usc_criterion_backward");
   return USC_OK;
+}
+
+int usc_criterion_backward(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S, int32_t Q,
+                           int32_t T, const uint32_t* bits, const int32_t* cnt, const int64_t* src, const int64_t* tid,
+                           const float* nmat, const float* ssum, const float* logp, const int32_t* tcls,
+                           const float* class_w, const float* gtable, const float* den_tot, int32_t C, int64_t ls_level,
+                           int64_t ls_q, float* dlogits, usc_stream_t s) {
+  return usc_criterion_backward_ex(masks, dmasks, L, ld, S, Q, T, bits, cnt, src, tid, nmat, ssum, logp, tcls, class_w,
+                                   gtable, den_tot, C, ls_level, ls_q, dlogits, nullptr, s);
 }
 
 }  // extern "C"

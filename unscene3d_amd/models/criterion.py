@@ -38,7 +38,10 @@ class _FusedCriterion(torch.autograd.Function):
     mask / dice losses (1 launch) — no device->host copy, no host solve — and one table launch for the batch.
     Inputs: class logits f32[L,B,Q,C] and, per scene and level, the mask logits f32[S_b, ld] (ld >= Q: the padded
     tables of models.mask3d._mask_logits are taken as they are).  Output: the [L*4] loss table
-    (loss_ce, loss_mask, loss_dice, loss_noise_robust = 0 per level)."""
+    (loss_ce, loss_mask, loss_dice, loss_noise_robust = 0 per level).
+    With `crit.use_droploss` (reference models/criterion.py:194-200) one more launch per scene counts the overlap of
+    every matched pair after the assignment, the `_ex` loss / backward entry points turn the counts into the 0 / 1 pair
+    weights and apply them; the weights stay on the device (`crit.last_drop_weights`)."""
 
     @staticmethod
     def forward(ctx, crit, targets, mask_type, logits, *mask_tables):
@@ -50,6 +53,7 @@ class _FusedCriterion(torch.autograd.Function):
         logits = logits.contiguous()
         st = ops._stream()
         m = crit.matcher
+        drop = bool(crit.use_droploss)
         parts = torch.empty((B, L, 4), dtype=torch.float32, device=dev)
         scenes = []
         for b in range(B):
@@ -78,12 +82,25 @@ class _FusedCriterion(torch.autograd.Function):
                   "usc_criterion_costs")
             src, tid, status = ops.lsap_batch(cost)                                 # [L,T] queries (ascending), targets
             tcls = torch.empty((L, Q), dtype=torch.int32, device=dev)
-            check(lib.usc_criterion_losses(comps[0].data_ptr(), comps[1].data_ptr(), logp.data_ptr(), src.data_ptr(),
-                                           tid.data_ptr(), labels.data_ptr(), crit.empty_weight.data_ptr(), L, Q, T, NC,
-                                           crit.num_classes, tcls.data_ptr(), parts[b].data_ptr(), st),
-                  "usc_criterion_losses")
+            wts = None
+            if drop:
+                counts = torch.empty((2, L, T), dtype=torch.int32, device=dev)      # I | F per matched pair
+                wts = torch.empty((L, T), dtype=torch.float32, device=dev)
+                check(lib.usc_criterion_drop_counts(ptrs, L, ld, S, Q, T, bits.data_ptr(), src.data_ptr(), tid.data_ptr(),
+                                                    counts.data_ptr(), st), "usc_criterion_drop_counts")
+                check(lib.usc_criterion_losses_ex(comps[0].data_ptr(), comps[1].data_ptr(), logp.data_ptr(),
+                                                  src.data_ptr(), tid.data_ptr(), labels.data_ptr(),
+                                                  crit.empty_weight.data_ptr(), L, Q, T, NC, crit.num_classes,
+                                                  tcls.data_ptr(), parts[b].data_ptr(), counts.data_ptr(), cnt.data_ptr(),
+                                                  float(crit.droploss_iou_thresh), wts.data_ptr(), st),
+                      "usc_criterion_losses_ex")
+            else:
+                check(lib.usc_criterion_losses(comps[0].data_ptr(), comps[1].data_ptr(), logp.data_ptr(), src.data_ptr(),
+                                               tid.data_ptr(), labels.data_ptr(), crit.empty_weight.data_ptr(), L, Q, T,
+                                               NC, crit.num_classes, tcls.data_ptr(), parts[b].data_ptr(), st),
+                      "usc_criterion_losses")
             scenes.append(dict(tabs=tabs, S=S, ld=ld, T=T, bits=bits, cnt=cnt, src=src, tid=tid, comps=comps, ssum=ssum,
-                               logp=logp, tcls=tcls, status=status))
+                               logp=logp, tcls=tcls, status=status, wts=wts))
         table = torch.empty((L, 4), dtype=torch.float32, device=dev)
         den_tot = torch.empty(L, dtype=torch.float32, device=dev)
         check(lib.usc_criterion_table(parts.data_ptr(), B, L, table.data_ptr(), den_tot.data_ptr(), st),
@@ -94,6 +111,7 @@ class _FusedCriterion(torch.autograd.Function):
         ctx.save_for_backward(*[t for sc in scenes for t in sc.pop("tabs")])
         ctx.scenes, ctx.den_tot, ctx.shape, ctx.class_w = scenes, den_tot, (L, B, Q, NC), crit.empty_weight
         crit.last_indices = [[(sc["src"][l], sc["tid"][l]) for sc in scenes] for l in range(L)]   # device tensors
+        crit.last_drop_weights = [[sc["wts"][l] for sc in scenes] for l in range(L)] if drop else None   # device tensors
         crit.last_lsap_status = [sc["status"] for sc in scenes]
         crit._queue_status_check(crit.last_lsap_status)
         return table.reshape(-1)
@@ -114,12 +132,14 @@ class _FusedCriterion(torch.autograd.Function):
             dtab = torch.empty((L, sc["S"], sc["ld"]), dtype=torch.float32, device=dev)
             ptrs = (C.c_void_p * L)(*[t.data_ptr() for t in saved[b * L:(b + 1) * L]])
             dptrs = (C.c_void_p * L)(*[dtab[l].data_ptr() for l in range(L)])
-            check(lib.usc_criterion_backward(ptrs, dptrs, L, sc["ld"], sc["S"], Q, sc["T"], sc["bits"].data_ptr(),
-                                             sc["cnt"].data_ptr(), sc["src"].data_ptr(), sc["tid"].data_ptr(),
-                                             sc["comps"][2].data_ptr(), sc["ssum"].data_ptr(), sc["logp"].data_ptr(),
-                                             sc["tcls"].data_ptr(), ctx.class_w.data_ptr(), g.data_ptr(),
-                                             ctx.den_tot.data_ptr(), NC, B * Q * NC, NC, dlogits[:, b].data_ptr(), st),
-                  "usc_criterion_backward")
+            args = (ptrs, dptrs, L, sc["ld"], sc["S"], Q, sc["T"], sc["bits"].data_ptr(), sc["cnt"].data_ptr(),
+                    sc["src"].data_ptr(), sc["tid"].data_ptr(), sc["comps"][2].data_ptr(), sc["ssum"].data_ptr(),
+                    sc["logp"].data_ptr(), sc["tcls"].data_ptr(), ctx.class_w.data_ptr(), g.data_ptr(),
+                    ctx.den_tot.data_ptr(), NC, B * Q * NC, NC, dlogits[:, b].data_ptr())
+            if sc["wts"] is not None:
+                check(lib.usc_criterion_backward_ex(*args, sc["wts"].data_ptr(), st), "usc_criterion_backward_ex")
+            else:
+                check(lib.usc_criterion_backward(*args, st), "usc_criterion_backward")
             grads.extend(dtab.unbind(0))
         return (None, None, None, dlogits, *grads)
 
@@ -240,6 +260,7 @@ class SetCriterion(nn.Module):
                 fg = m > 0.0
                 iou = (fg * tgt).sum(dim=1) / (fg + tgt).sum(dim=1)
                 weights = (iou >= self.droploss_iou_thresh).float()
+                self.__dict__.setdefault("_level_drop_weights", []).append(weights)
             else:
                 weights = torch.ones(m.shape[0], device=dev)
             tgt = tgt.float()
@@ -335,24 +356,28 @@ class SetCriterion(nn.Module):
         # ---- masks: per scene, all levels at once
         loss_mask = torch.zeros(L, device=dev)
         loss_dice = torch.zeros(L, device=dev)
+        drop_w = []
         for b, tgt in enumerate(targets):
             pm = torch.stack([lv["pred_masks"][b] for lv in levels])                       # [L,S,Q]
             src = torch.stack([all_indices[l][b][0] for l in range(L)]).to(dev)            # [L,T]
             tid = torch.stack([all_indices[l][b][1] for l in range(L)]).to(dev)            # [L,T]
             mp = torch.gather(pm, 2, src[:, None, :].expand(-1, pm.shape[1], -1)).transpose(1, 2)   # [L,T,S]
-            tm = tgt[mask_type].to(dev)[tid].float()                                      # [L,T,S]
+            tm = tgt[mask_type].to(dev)[tid]                                              # [L,T,S]
             T = tm.shape[1]
-            if self.use_droploss:
+            if self.use_droploss:     # on the target as given, like loss_masks: bool * bool / bool + bool = AND / OR
                 fg = mp > 0.0
                 iou = (fg * tm).sum(2) / (fg + tm).sum(2)
                 wts = (iou >= self.droploss_iou_thresh).float()
             else:
                 wts = torch.ones(mp.shape[:2], device=dev)
+            drop_w.append(wts)
+            tm = tm.float()
             bce = F.binary_cross_entropy_with_logits(mp, tm, reduction="none")
             loss_mask = loss_mask + (wts[..., None] * bce).mean(2).sum(1) / T
             p = mp.sigmoid()
             dice = 1 - (2 * (p * tm).sum(2) + 1) / (p.sum(2) + tm.sum(2) + 1)
             loss_dice = loss_dice + (wts * dice).sum(1) / T
+        self.last_drop_weights = [[w[l] for w in drop_w] for l in range(L)] if self.use_droploss else None
         # one [L, 4] table; the per-key scalars are views of it.  `flat` hands the table to the trainer, whose weighted
         # sum then differentiates through ONE stack instead of 4 L selects (~120 tiny backward launches per step)
         table = torch.stack([loss_ce, loss_mask, loss_dice, torch.zeros(L, dtype=torch.float32, device=dev)], dim=1)
@@ -367,9 +392,9 @@ class SetCriterion(nn.Module):
 
     def _fused_tables(self, levels, targets, mask_type):
         """The per-(scene, level) mask-logit tables [S, ld] for the device criterion, or None when the fused path does
-        not apply (CPU tensors, sub-sampled points, drop loss, noise-robust loss, > 32 targets or > 128 queries ...)."""
+        not apply (CPU tensors, sub-sampled points, noise-robust loss, > 32 targets or > 128 queries ...)."""
         if not (FUSED and self.losses == ["labels", "masks"] and self.num_points == -1 and self.matcher.num_points == -1
-                and self.weight_dict.get("loss_noise_robust", 0) == 0 and not self.use_droploss and targets
+                and self.weight_dict.get("loss_noise_robust", 0) == 0 and targets
                 and 1 <= len(levels) <= 16):
             return None
         lg = levels[0]["pred_logits"]
@@ -444,10 +469,13 @@ class SetCriterion(nn.Module):
             return self._batched_losses(levels, targets, all_indices, mask_type)
 
         losses = {}
+        self.__dict__["_level_drop_weights"] = []
         for loss in self.losses:
             losses.update(self.get_loss(loss, final, targets, all_indices[0], num_masks, mask_type, coords))
         for i, aux in enumerate(levels[1:]):
             for loss in self.losses:
                 ld = self.get_loss(loss, aux, targets, all_indices[i + 1], num_masks, mask_type, coords)
                 losses.update({f"{k}_{i}": v for k, v in ld.items()})
+        w, B = self.__dict__.pop("_level_drop_weights"), len(targets)
+        self.last_drop_weights = [w[l * B:(l + 1) * B] for l in range(len(levels))] if len(w) == len(levels) * B else None
         return losses
