@@ -1,5 +1,5 @@
-"""The device set criterion (csrc/criterion.hip: usc_criterion_* and usc_lsap_batch, driven by
-models/criterion.py::_FusedCriterion) against oracle/criterion_ref.py in float64, over tests/criterion_cases.py.
+"""The device set criterion (csrc/criterion.hip: usc_criterion_* and usc_lsap_batch, driven by criterion_device.py
+under models/criterion.py::_FusedCriterion) against oracle/criterion_ref.py in float64, over tests/criterion_cases.py.
 
 The bound is relative to the reference's own float32 arithmetic, not a constant: with
     dev = the device, o32 = the oracle in float32 on the CPU, o64 = the oracle in float64, all on the same inputs,
@@ -26,7 +26,6 @@ nothing there.
 Every test prints its figures (`pytest -s`); test_report_worst_ratios prints the worst err(dev, o64) / err(o32, o64)
 per regime and quantity, the numbers quoted in DESIGN.md section 3.10.
 """
-import ctypes as C
 import warnings
 
 import numpy as np
@@ -98,72 +97,48 @@ def _same_bits(a, b):
 
 
 # ---- the entry-point layer ------------------------------------------------------------------------------------------
-def device_entry_points(case, dev, pad=0.0):
-    """usc_criterion_target_bits -> _costs -> usc_lsap_batch -> _losses -> _table -> _backward, issued as
-    _FusedCriterion.forward / backward issue them, every intermediate kept (CPU tensors).  Outputs and the workspace
-    start out as NaN, so an element a kernel does not write shows.  pad: the value of the table columns Q <= col < ld."""
-    from unscene3d_amd import ops
-    from unscene3d_amd._lib import check, lib
-    L, B, Q, NC, ld = case["L"], case["B"], case["Q"], case["C"], case["ld"]
-    st = ops._stream()
-    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)      # noqa: E731
+_POISON = {torch.float32: float("nan"), torch.int32: -1, torch.uint8: 0xFF}          # 0xFF bytes: NaN as float32
+
+
+def device_entry_points(case, dev, pad=0.0, thresh=None):
+    """criterion_device.scene_forward -> table -> scene_backward, the functions _FusedCriterion.forward / backward call,
+    every intermediate kept (CPU tensors).  thresh: the DropLoss threshold (None: no DropLoss, no `counts` / `wts`).
+    Outputs and the workspace start out as NaN / -1, so an element a kernel does not write shows.  pad: the value of the
+    table columns Q <= col < ld."""
+    from unscene3d_amd import criterion_device as D
+    L, B, Q, NC = case["L"], case["B"], case["Q"], case["C"]
+
+    def poisoned(shape, dtype):
+        return torch.full(shape, _POISON[dtype], dtype=dtype, device=dev)
     logits = torch.stack(case["logits"]).to(dev).contiguous()                                   # [L, B, Q, C]
     class_w = torch.ones(NC, dtype=torch.float32)
     class_w[-1] = case["eos_coef"]
     class_w = class_w.to(dev)
     g = CC.gtable(case).to(dev).reshape(-1).contiguous()
-    parts = nan(B, L, 4)
-    scenes, keep = [], []
+    weights = tuple(CC.COST_WEIGHTS[k] for k in ("cost_mask", "cost_class", "cost_dice"))
+    parts = poisoned((B, L, 4), torch.float32)
+    tabs, states = [], []
     for b in range(B):
-        tabs = []
+        tabs.append([])
         for l in range(L):
             t = case["masks"][l][b].clone()
             t[:, Q:] = pad
-            tabs.append(t.to(dev).contiguous())
-        S, T = case["S"][b], case["T"][b]
+            tabs[b].append(t.to(dev).contiguous())
         tm8 = case["tm"][b].to(dev).contiguous().view(torch.uint8)
         labels = case["labels"][b].to(dev).contiguous()
-        bits = torch.full((S,), -1, dtype=torch.int32, device=dev)
-        cnt = torch.full((T,), -1, dtype=torch.int32, device=dev)
-        check(lib.usc_criterion_target_bits(tm8.data_ptr(), T, S, bits.data_ptr(), cnt.data_ptr(), st), "target_bits")
-        ptrs = (C.c_void_p * L)(*[t.data_ptr() for t in tabs])
-        cost, comps, ssum, logp = nan(L, Q, T), nan(3, L, Q, T), nan(L, Q), nan(L, Q, NC)
-        wsb = lib.usc_criterion_ws_bytes(L, S, T)
-        ws = torch.full((wsb,), 0xFF, dtype=torch.uint8, device=dev)                            # NaN as float32
-        lg = logits[:, b]
-        check(lib.usc_criterion_costs(ptrs, L, ld, S, Q, T, bits.data_ptr(), cnt.data_ptr(), lg.data_ptr(), B * Q * NC,
-                                      NC, NC, labels.data_ptr(), CC.COST_WEIGHTS["cost_mask"],
-                                      CC.COST_WEIGHTS["cost_class"], CC.COST_WEIGHTS["cost_dice"], cost.data_ptr(),
-                                      comps[0].data_ptr(), comps[1].data_ptr(), comps[2].data_ptr(), ssum.data_ptr(),
-                                      logp.data_ptr(), ws.data_ptr(), wsb, st), "costs")
-        src, tid, status = ops.lsap_batch(cost)
-        tcls = torch.full((L, Q), -7, dtype=torch.int32, device=dev)
-        check(lib.usc_criterion_losses(comps[0].data_ptr(), comps[1].data_ptr(), logp.data_ptr(), src.data_ptr(),
-                                       tid.data_ptr(), labels.data_ptr(), class_w.data_ptr(), L, Q, T, NC, NC - 1,
-                                       tcls.data_ptr(), parts[b].data_ptr(), st), "losses")
-        scenes.append(dict(bits=bits, cnt=cnt, cost=cost, cmask=comps[0], cdice=comps[1], nmat=comps[2], ssum=ssum,
-                           logp=logp, src=src, tid=tid, status=status, tcls=tcls))
-        keep.append((tabs, labels, tm8, ws, comps))
-    table, den_tot = nan(L, 4), nan(L)
-    check(lib.usc_criterion_table(parts.data_ptr(), B, L, table.data_ptr(), den_tot.data_ptr(), st), "table")
-    dlogits = nan(L, B, Q, NC)
-    for b, sc in enumerate(scenes):
-        tabs = keep[b][0]
-        S, T = case["S"][b], case["T"][b]
-        dtab = nan(L, S, ld)
-        ptrs = (C.c_void_p * L)(*[t.data_ptr() for t in tabs])
-        dptrs = (C.c_void_p * L)(*[dtab[l].data_ptr() for l in range(L)])
-        check(lib.usc_criterion_backward(ptrs, dptrs, L, ld, S, Q, T, sc["bits"].data_ptr(), sc["cnt"].data_ptr(),
-                                         sc["src"].data_ptr(), sc["tid"].data_ptr(), sc["nmat"].data_ptr(),
-                                         sc["ssum"].data_ptr(), sc["logp"].data_ptr(), sc["tcls"].data_ptr(),
-                                         class_w.data_ptr(), g.data_ptr(), den_tot.data_ptr(), NC, B * Q * NC, NC,
-                                         dlogits[:, b].data_ptr(), st), "backward")
-        sc["dmasks"] = dtab
+        states.append(D.scene_forward(tabs[b], tm8, labels, logits, b, weights, class_w, NC - 1, parts[b], thresh,
+                                      alloc=poisoned))
+    table, den_tot = D.table(parts, alloc=poisoned)
+    dlogits = poisoned((L, B, Q, NC), torch.float32)
+    scenes = []
+    for b, st in enumerate(states):
+        assert (st.S, st.T, st.ld) == (case["S"][b], case["T"][b], case["ld"])
+        sc = {k: v for k, v in st._asdict().items() if torch.is_tensor(v)}
+        sc["dmasks"] = D.scene_backward(st, tabs[b], b, class_w, g, den_tot, dlogits, alloc=poisoned)
+        scenes.append(sc)
     torch.cuda.synchronize()
-    out = dict(scenes=[{k: v.cpu() for k, v in sc.items()} for sc in scenes], parts=parts.cpu(), table=table.cpu(),
-               den_tot=den_tot.cpu(), dlogits=dlogits.cpu())
-    del keep
-    return out
+    return dict(scenes=[{k: v.cpu() for k, v in sc.items()} for sc in scenes], parts=parts.cpu(), table=table.cpu(),
+                den_tot=den_tot.cpu(), dlogits=dlogits.cpu())
 
 
 @pytest.fixture(scope="module", params=range(len(IDS)), ids=IDS)

@@ -1,6 +1,7 @@
 """DropLoss inside the device set criterion (csrc/criterion.hip: usc_criterion_drop_counts, usc_criterion_losses_ex,
-usc_criterion_backward_ex, driven by models/criterion.py::_FusedCriterion when `use_droploss` is set) against the
-weighted float64 restatement of tests/droploss_ref.py, which tests/test_droploss_host.py pins on the reference's golden.
+usc_criterion_backward_ex, driven by criterion_device.py under models/criterion.py::_FusedCriterion when `use_droploss`
+is set) against the weighted float64 restatement of tests/droploss_ref.py, which tests/test_droploss_host.py pins on the
+reference's golden.
 
 Cases: droploss_ref.GPU_CASES, a covering selection of criterion_cases._SHAPES (S in {1, 31, 32, 33, 609}, T in {1, 8,
 9, 16, 17, 32}, Q in {32, 63, 100, 128}, ld = Q / between / 128, L in {1, 13, 16}, B up to 3, every regime; the
@@ -13,7 +14,6 @@ sums restated: float64 / float32 accumulation of the stored pair terms in pair o
 parts, table, losses and gradients by test_gpu_criterion_f64's  err(dev, o64) <= 4 err(o32, o64) + floor  with the same
 floors, both oracles being the weighted restatement under the device's assignment.
 """
-import ctypes as C
 import warnings
 
 import numpy as np
@@ -31,76 +31,8 @@ KINDS = ("0.1", "0.01", "tie")
 
 
 def entry_points(case, dev, thresh, pad=0.0):
-    """test_gpu_criterion_f64.device_entry_points with the DropLoss calls: ... -> usc_lsap_batch ->
-    usc_criterion_drop_counts -> usc_criterion_losses_ex -> _table -> usc_criterion_backward_ex.  Outputs and the
-    workspace start out as NaN / -1."""
-    from unscene3d_amd import ops
-    from unscene3d_amd._lib import check, lib
-    L, B, Q, NC, ld = case["L"], case["B"], case["Q"], case["C"], case["ld"]
-    st = ops._stream()
-    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)      # noqa: E731
-    logits = torch.stack(case["logits"]).to(dev).contiguous()
-    class_w = torch.ones(NC, dtype=torch.float32)
-    class_w[-1] = case["eos_coef"]
-    class_w = class_w.to(dev)
-    g = CC.gtable(case).to(dev).reshape(-1).contiguous()
-    parts = nan(B, L, 4)
-    scenes, keep = [], []
-    for b in range(B):
-        tabs = []
-        for l in range(L):
-            t = case["masks"][l][b].clone()
-            t[:, Q:] = pad
-            tabs.append(t.to(dev).contiguous())
-        S, T = case["S"][b], case["T"][b]
-        tm8 = case["tm"][b].to(dev).contiguous().view(torch.uint8)
-        labels = case["labels"][b].to(dev).contiguous()
-        bits = torch.full((S,), -1, dtype=torch.int32, device=dev)
-        cnt = torch.full((T,), -1, dtype=torch.int32, device=dev)
-        check(lib.usc_criterion_target_bits(tm8.data_ptr(), T, S, bits.data_ptr(), cnt.data_ptr(), st), "target_bits")
-        ptrs = (C.c_void_p * L)(*[t.data_ptr() for t in tabs])
-        cost, comps, ssum, logp = nan(L, Q, T), nan(3, L, Q, T), nan(L, Q), nan(L, Q, NC)
-        wsb = lib.usc_criterion_ws_bytes(L, S, T)
-        ws = torch.full((wsb,), 0xFF, dtype=torch.uint8, device=dev)
-        lg = logits[:, b]
-        check(lib.usc_criterion_costs(ptrs, L, ld, S, Q, T, bits.data_ptr(), cnt.data_ptr(), lg.data_ptr(), B * Q * NC,
-                                      NC, NC, labels.data_ptr(), CC.COST_WEIGHTS["cost_mask"],
-                                      CC.COST_WEIGHTS["cost_class"], CC.COST_WEIGHTS["cost_dice"], cost.data_ptr(),
-                                      comps[0].data_ptr(), comps[1].data_ptr(), comps[2].data_ptr(), ssum.data_ptr(),
-                                      logp.data_ptr(), ws.data_ptr(), wsb, st), "costs")
-        src, tid, status = ops.lsap_batch(cost)
-        tcls = torch.full((L, Q), -7, dtype=torch.int32, device=dev)
-        counts = torch.full((2, L, T), -1, dtype=torch.int32, device=dev)
-        wts = nan(L, T)
-        check(lib.usc_criterion_drop_counts(ptrs, L, ld, S, Q, T, bits.data_ptr(), src.data_ptr(), tid.data_ptr(),
-                                            counts.data_ptr(), st), "drop_counts")
-        check(lib.usc_criterion_losses_ex(comps[0].data_ptr(), comps[1].data_ptr(), logp.data_ptr(), src.data_ptr(),
-                                          tid.data_ptr(), labels.data_ptr(), class_w.data_ptr(), L, Q, T, NC, NC - 1,
-                                          tcls.data_ptr(), parts[b].data_ptr(), counts.data_ptr(), cnt.data_ptr(),
-                                          float(thresh), wts.data_ptr(), st), "losses_ex")
-        scenes.append(dict(bits=bits, cnt=cnt, cost=cost, cmask=comps[0], cdice=comps[1], nmat=comps[2], ssum=ssum,
-                           logp=logp, src=src, tid=tid, status=status, tcls=tcls, counts=counts, wts=wts))
-        keep.append((tabs, labels, tm8, ws, comps))
-    table, den_tot = nan(L, 4), nan(L)
-    check(lib.usc_criterion_table(parts.data_ptr(), B, L, table.data_ptr(), den_tot.data_ptr(), st), "table")
-    dlogits = nan(L, B, Q, NC)
-    for b, sc in enumerate(scenes):
-        tabs = keep[b][0]
-        S, T = case["S"][b], case["T"][b]
-        dtab = nan(L, S, ld)
-        ptrs = (C.c_void_p * L)(*[t.data_ptr() for t in tabs])
-        dptrs = (C.c_void_p * L)(*[dtab[l].data_ptr() for l in range(L)])
-        check(lib.usc_criterion_backward_ex(ptrs, dptrs, L, ld, S, Q, T, sc["bits"].data_ptr(), sc["cnt"].data_ptr(),
-                                            sc["src"].data_ptr(), sc["tid"].data_ptr(), sc["nmat"].data_ptr(),
-                                            sc["ssum"].data_ptr(), sc["logp"].data_ptr(), sc["tcls"].data_ptr(),
-                                            class_w.data_ptr(), g.data_ptr(), den_tot.data_ptr(), NC, B * Q * NC, NC,
-                                            dlogits[:, b].data_ptr(), sc["wts"].data_ptr(), st), "backward_ex")
-        sc["dmasks"] = dtab
-    torch.cuda.synchronize()
-    out = dict(scenes=[{k: v.cpu() for k, v in sc.items()} for sc in scenes], parts=parts.cpu(), table=table.cpu(),
-               den_tot=den_tot.cpu(), dlogits=dlogits.cpu())
-    del keep
-    return out
+    """test_gpu_criterion_f64.device_entry_points with a DropLoss threshold (the argument order the tests below use)."""
+    return F64.device_entry_points(case, dev, pad, thresh)
 
 
 def _indices(run, case):

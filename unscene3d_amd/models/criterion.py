@@ -2,9 +2,20 @@
 weighted cross-entropy over C+1 classes (`eos_coef` on the no-object class, ignore_index 253),
 sigmoid-BCE + dice on the matched masks, each divided by the number of target masks.
 
-Differences from the reference are organisational only: all 13 levels' cost matrices are built on
-the device first and copied to the host in ONE transfer (the reference syncs 13*B times), then
-scipy solves them; the loss arithmetic and its reduction order follow the reference line by line."""
+Differences from the reference are organisational only; the loss arithmetic and its reduction order follow the
+reference line by line.  `SetCriterion.forward` takes one of three paths:
+
+* device (the default): `_FusedCriterion` over criterion_device.py / csrc/criterion.hip.  Costs, assignment, losses and
+  gradients of all levels stay on the device, nothing is copied to the host.  Runs when `_fused_tables` accepts the
+  inputs: USC3D_FUSED_CRITERION is not 0, labels + masks losses on all points without the noise-robust loss
+  (`_plain_losses`), float32 HIP predictions with 1-16 levels and at most 128 queries, and per scene 1-32 targets whose
+  masks and labels are on the device.
+* batched operators: `match_all_levels` builds all levels' cost matrices with torch operators and copies them to the host
+  in ONE transfer (the reference syncs 13*B times), scipy solves them, `_batched_losses` computes all levels at once.
+  Runs for `_plain_losses` inputs the device path does not take (CPU tensors, more than 32 targets, ...); on HIP
+  tensors it warns once.
+* per level: `get_loss` level by level, as the reference does.  Runs for everything else: point sub-sampling, the
+  noise-robust loss, another list of losses, or imposed assignments of unequal length."""
 import os
 
 import torch
@@ -25,121 +36,57 @@ def sigmoid_ce_loss(inputs, targets, num_masks: float, weights):
     return loss.mean(1).sum() / num_masks
 
 
-dice_loss_jit = dice_loss
-sigmoid_ce_loss_jit = sigmoid_ce_loss
-
-
 FUSED = os.environ.get("USC3D_FUSED_CRITERION", "1") == "1"
 
 
 class _FusedCriterion(torch.autograd.Function):
-    """Matching + losses of all prediction levels on the device (csrc/criterion.hip): per scene the cost matrices of
-    the 13 levels (2 launches), their assignments (usc_lsap_batch, scipy's algorithm and tie-breaking), the label /
-    mask / dice losses (1 launch) — no device->host copy, no host solve — and one table launch for the batch.
+    """Matching + losses of all prediction levels on the device: the autograd wrapper of criterion_device.scene_forward /
+    table / scene_backward (the launches are described there).
     Inputs: class logits f32[L,B,Q,C] and, per scene and level, the mask logits f32[S_b, ld] (ld >= Q: the padded
     tables of models.mask3d._mask_logits are taken as they are).  Output: the [L*4] loss table
-    (loss_ce, loss_mask, loss_dice, loss_noise_robust = 0 per level).
-    With `crit.use_droploss` (reference models/criterion.py:194-200) one more launch per scene counts the overlap of
-    every matched pair after the assignment, the `_ex` loss / backward entry points turn the counts into the 0 / 1 pair
-    weights and apply them; the weights stay on the device (`crit.last_drop_weights`)."""
+    (loss_ce, loss_mask, loss_dice, loss_noise_robust = 0 per level).  With `crit.use_droploss` (reference
+    models/criterion.py:194-200) the 0 / 1 pair weights stay on the device (`crit.last_drop_weights`)."""
 
     @staticmethod
     def forward(ctx, crit, targets, mask_type, logits, *mask_tables):
-        import ctypes as C
-        from .. import ops
-        from .._lib import check, lib
+        from .. import criterion_device as D
         L, B, Q, NC = logits.shape
-        dev = logits.device
         logits = logits.contiguous()
-        st = ops._stream()
         m = crit.matcher
-        drop = bool(crit.use_droploss)
-        parts = torch.empty((B, L, 4), dtype=torch.float32, device=dev)
-        scenes = []
+        thresh = float(crit.droploss_iou_thresh) if crit.use_droploss else None
+        parts = torch.empty((B, L, 4), dtype=torch.float32, device=logits.device)
+        tabs, scenes = [], []
         for b in range(B):
-            tabs = [t.contiguous() for t in mask_tables[b * L:(b + 1) * L]]
-            S, ld = tabs[0].shape
+            tabs_b = [t.contiguous() for t in mask_tables[b * L:(b + 1) * L]]
             tm = targets[b][mask_type]
             labels = targets[b]["labels"].to(torch.int64).contiguous()
-            T = int(tm.shape[0])
             tm8 = tm.contiguous().view(torch.uint8) if tm.dtype == torch.bool else (tm != 0).contiguous().view(torch.uint8)
-            bits = torch.empty(S, dtype=torch.int32, device=dev)
-            cnt = torch.empty(T, dtype=torch.int32, device=dev)
-            check(lib.usc_criterion_target_bits(tm8.data_ptr(), T, S, bits.data_ptr(), cnt.data_ptr(), st),
-                  "usc_criterion_target_bits")
-            ptrs = (C.c_void_p * L)(*[t.data_ptr() for t in tabs])
-            cost = torch.empty((L, Q, T), dtype=torch.float32, device=dev)
-            comps = torch.empty((3, L, Q, T), dtype=torch.float32, device=dev)      # cmask | cdice | nmat
-            ssum = torch.empty((L, Q), dtype=torch.float32, device=dev)
-            logp = torch.empty((L, Q, NC), dtype=torch.float32, device=dev)
-            wsb = lib.usc_criterion_ws_bytes(L, S, T)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            lg = logits[:, b]                                                       # [L,Q,C] view: strides (B*Q*C, C, 1)
-            check(lib.usc_criterion_costs(ptrs, L, ld, S, Q, T, bits.data_ptr(), cnt.data_ptr(), lg.data_ptr(),
-                                          B * Q * NC, NC, NC, labels.data_ptr(), float(m.cost_mask), float(m.cost_class),
-                                          float(m.cost_dice), cost.data_ptr(), comps[0].data_ptr(), comps[1].data_ptr(),
-                                          comps[2].data_ptr(), ssum.data_ptr(), logp.data_ptr(), ws.data_ptr(), wsb, st),
-                  "usc_criterion_costs")
-            src, tid, status = ops.lsap_batch(cost)                                 # [L,T] queries (ascending), targets
-            tcls = torch.empty((L, Q), dtype=torch.int32, device=dev)
-            wts = None
-            if drop:
-                counts = torch.empty((2, L, T), dtype=torch.int32, device=dev)      # I | F per matched pair
-                wts = torch.empty((L, T), dtype=torch.float32, device=dev)
-                check(lib.usc_criterion_drop_counts(ptrs, L, ld, S, Q, T, bits.data_ptr(), src.data_ptr(), tid.data_ptr(),
-                                                    counts.data_ptr(), st), "usc_criterion_drop_counts")
-                check(lib.usc_criterion_losses_ex(comps[0].data_ptr(), comps[1].data_ptr(), logp.data_ptr(),
-                                                  src.data_ptr(), tid.data_ptr(), labels.data_ptr(),
-                                                  crit.empty_weight.data_ptr(), L, Q, T, NC, crit.num_classes,
-                                                  tcls.data_ptr(), parts[b].data_ptr(), counts.data_ptr(), cnt.data_ptr(),
-                                                  float(crit.droploss_iou_thresh), wts.data_ptr(), st),
-                      "usc_criterion_losses_ex")
-            else:
-                check(lib.usc_criterion_losses(comps[0].data_ptr(), comps[1].data_ptr(), logp.data_ptr(), src.data_ptr(),
-                                               tid.data_ptr(), labels.data_ptr(), crit.empty_weight.data_ptr(), L, Q, T,
-                                               NC, crit.num_classes, tcls.data_ptr(), parts[b].data_ptr(), st),
-                      "usc_criterion_losses")
-            scenes.append(dict(tabs=tabs, S=S, ld=ld, T=T, bits=bits, cnt=cnt, src=src, tid=tid, comps=comps, ssum=ssum,
-                               logp=logp, tcls=tcls, status=status, wts=wts))
-        table = torch.empty((L, 4), dtype=torch.float32, device=dev)
-        den_tot = torch.empty(L, dtype=torch.float32, device=dev)
-        check(lib.usc_criterion_table(parts.data_ptr(), B, L, table.data_ptr(), den_tot.data_ptr(), st),
-              "usc_criterion_table")
+            sc = D.scene_forward(tabs_b, tm8, labels, logits, b, (m.cost_mask, m.cost_class, m.cost_dice),
+                                 crit.empty_weight, crit.num_classes, parts[b], thresh)
+            scenes.append(sc._replace(cost=None, counts=None))          # the backward needs neither: freed here, as before
+            tabs.extend(tabs_b)
+        table, den_tot = D.table(parts)
         # the differentiable inputs go through save_for_backward (version check: a table modified in place between
         # forward and backward raises instead of differentiating stale numbers); the per-scene intermediates are this
         # Function's own tensors
-        ctx.save_for_backward(*[t for sc in scenes for t in sc.pop("tabs")])
+        ctx.save_for_backward(*tabs)
         ctx.scenes, ctx.den_tot, ctx.shape, ctx.class_w = scenes, den_tot, (L, B, Q, NC), crit.empty_weight
-        crit.last_indices = [[(sc["src"][l], sc["tid"][l]) for sc in scenes] for l in range(L)]   # device tensors
-        crit.last_drop_weights = [[sc["wts"][l] for sc in scenes] for l in range(L)] if drop else None   # device tensors
-        crit.last_lsap_status = [sc["status"] for sc in scenes]
+        crit.last_indices = [[(sc.src[l], sc.tid[l]) for sc in scenes] for l in range(L)]              # device tensors
+        crit.last_drop_weights = [[sc.wts[l] for sc in scenes] for l in range(L)] if crit.use_droploss else None
+        crit.last_lsap_status = [sc.status for sc in scenes]
         crit._queue_status_check(crit.last_lsap_status)
         return table.reshape(-1)
 
     @staticmethod
     def backward(ctx, dflat):
-        import ctypes as C
-        from .. import ops
-        from .._lib import check, lib
-        L, B, Q, NC = ctx.shape
+        from .. import criterion_device as D
+        L = ctx.shape[0]
         g = dflat.contiguous()
-        dev = g.device
-        st = ops._stream()
-        dlogits = torch.empty((L, B, Q, NC), dtype=torch.float32, device=dev)
+        dlogits = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
         grads = []
         saved = ctx.saved_tensors
         for b, sc in enumerate(ctx.scenes):
-            dtab = torch.empty((L, sc["S"], sc["ld"]), dtype=torch.float32, device=dev)
-            ptrs = (C.c_void_p * L)(*[t.data_ptr() for t in saved[b * L:(b + 1) * L]])
-            dptrs = (C.c_void_p * L)(*[dtab[l].data_ptr() for l in range(L)])
-            args = (ptrs, dptrs, L, sc["ld"], sc["S"], Q, sc["T"], sc["bits"].data_ptr(), sc["cnt"].data_ptr(),
-                    sc["src"].data_ptr(), sc["tid"].data_ptr(), sc["comps"][2].data_ptr(), sc["ssum"].data_ptr(),
-                    sc["logp"].data_ptr(), sc["tcls"].data_ptr(), ctx.class_w.data_ptr(), g.data_ptr(),
-                    ctx.den_tot.data_ptr(), NC, B * Q * NC, NC, dlogits[:, b].data_ptr())
-            if sc["wts"] is not None:
-                check(lib.usc_criterion_backward_ex(*args, sc["wts"].data_ptr(), st), "usc_criterion_backward_ex")
-            else:
-                check(lib.usc_criterion_backward(*args, st), "usc_criterion_backward")
+            dtab = D.scene_backward(sc, saved[b * L:(b + 1) * L], b, ctx.class_w, g, ctx.den_tot, dlogits)
             grads.extend(dtab.unbind(0))
         return (None, None, None, dlogits, *grads)
 
@@ -147,6 +94,17 @@ class _FusedCriterion(torch.autograd.Function):
 class LossDict(dict):
     """The criterion's {name: scalar} result plus `flat`: the same scalars as one vector in key order."""
     flat = None
+
+
+def _loss_dict(flat, L):
+    """The [L * 4] loss table as a LossDict: the reference's key per level (no suffix, then _0 ... _{L-2}), each a view."""
+    out = LossDict()
+    for l in range(L):
+        sfx = "" if l == 0 else f"_{l - 1}"
+        for j, name in enumerate(("loss_ce", "loss_mask", "loss_dice", "loss_noise_robust")):
+            out[name + sfx] = flat[4 * l + j]
+    out.flat = flat
+    return out
 
 
 class SetCriterion(nn.Module):
@@ -381,21 +339,17 @@ class SetCriterion(nn.Module):
         # one [L, 4] table; the per-key scalars are views of it.  `flat` hands the table to the trainer, whose weighted
         # sum then differentiates through ONE stack instead of 4 L selects (~120 tiny backward launches per step)
         table = torch.stack([loss_ce, loss_mask, loss_dice, torch.zeros(L, dtype=torch.float32, device=dev)], dim=1)
-        flat = table.reshape(-1)
-        out = LossDict()
-        for l in range(L):
-            sfx = "" if l == 0 else f"_{l - 1}"
-            for j, name in enumerate(("loss_ce", "loss_mask", "loss_dice", "loss_noise_robust")):
-                out[name + sfx] = flat[4 * l + j]
-        out.flat = flat
-        return out
+        return _loss_dict(table.reshape(-1), L)
+
+    def _plain_losses(self):
+        """Labels + masks on all points, no noise-robust loss: what the device and the batched-operator paths compute."""
+        return (self.losses == ["labels", "masks"] and self.num_points == -1
+                and self.weight_dict.get("loss_noise_robust", 0) == 0)
 
     def _fused_tables(self, levels, targets, mask_type):
         """The per-(scene, level) mask-logit tables [S, ld] for the device criterion, or None when the fused path does
         not apply (CPU tensors, sub-sampled points, noise-robust loss, > 32 targets or > 128 queries ...)."""
-        if not (FUSED and self.losses == ["labels", "masks"] and self.num_points == -1 and self.matcher.num_points == -1
-                and self.weight_dict.get("loss_noise_robust", 0) == 0 and targets
-                and 1 <= len(levels) <= 16):
+        if not (FUSED and self._plain_losses() and self.matcher.num_points == -1 and targets and 1 <= len(levels) <= 16):
             return None
         lg = levels[0]["pred_logits"]
         if not (lg.is_cuda and lg.dtype == torch.float32 and lg.dim() == 3 and lg.shape[1] <= 128
@@ -442,14 +396,7 @@ class SetCriterion(nn.Module):
                 nm = torch.full((1,), float(sum(len(t["labels"]) for t in targets)), dtype=torch.float, device=tables[0].device)
                 torch.distributed.all_reduce(nm)
             logits = torch.stack([lv["pred_logits"] for lv in levels])                       # [L,B,Q,C]
-            flat = _FusedCriterion.apply(self, targets, mask_type, logits, *tables)
-            out = LossDict()
-            for l in range(len(levels)):
-                sfx = "" if l == 0 else f"_{l - 1}"
-                for j, name in enumerate(("loss_ce", "loss_mask", "loss_dice", "loss_noise_robust")):
-                    out[name + sfx] = flat[4 * l + j]
-            out.flat = flat
-            return out
+            return _loss_dict(_FusedCriterion.apply(self, targets, mask_type, logits, *tables), len(levels))
         all_indices = self.match_all_levels(levels, targets, mask_type)
         self.last_indices = all_indices
 
@@ -461,11 +408,9 @@ class SetCriterion(nn.Module):
         else:
             num_masks = max(float(num_masks), 1.0)
 
-        batchable = (self.losses == ["labels", "masks"] and self.num_points == -1
-                     and self.weight_dict.get("loss_noise_robust", 0) == 0)
         same_T = all(len(all_indices[l][b][0]) == len(all_indices[0][b][0]) for l in range(len(levels))
                      for b in range(len(targets)))
-        if batchable and same_T:
+        if self._plain_losses() and same_T:
             return self._batched_losses(levels, targets, all_indices, mask_type)
 
         losses = {}
