@@ -791,6 +791,45 @@ int usc_criterion_backward_ex(const float* const* masks, float* const* dmasks, i
                               const int32_t* tcls, const float* class_w, const float* gtable,
                               const float* den_tot, int32_t C, int64_t ls_level, int64_t ls_q,
                               float* dlogits, const float* wts, usc_stream_t s);
+/* The device criterion for 33 .. 128 targets per scene (1 <= T <= 128, T <= Q <= 128, L <= 16; opt-in through
+ * SetCriterion(device_max_targets=...)).  Same arguments and results as the functions they are named after, with the
+ * target bits W = ceil(T / 32) words wide and word-major: bits u32[W, S], word w = the bits of the targets
+ * 32w .. 32w+31 in the one-word layout.  Replace, for such scenes, the torch-operator path of
+ * SetCriterion.match_all_levels / _batched_losses (one device->host copy of the cost matrices and a scipy solve per
+ * level and scene).
+ *   usc_criterion_target_bits_wide  usc_criterion_target_bits writing W words per row; cnt i32[T] as there
+ *   usc_criterion_costs_wide        usc_criterion_costs once per word, one word after the other on the stream: word w
+ *                                   fills the columns 32w .. of the [L,Q,T] outputs (2 W launches; the workspace of
+ *                                   usc_criterion_ws_bytes(L, S, T) is the 32-target one, reused per word).  The
+ *                                   entries of a pair are the bits usc_criterion_costs gives for that pair
+ *   usc_criterion_drop_counts_wide  usc_criterion_drop_counts; a pair's target bit is word tid >> 5, bit tid & 31
+ *   usc_criterion_losses_wide       usc_criterion_losses_ex (counts = cnt = wts = NULL: no DropLoss) over <= 128 pairs
+ *   usc_criterion_backward_wide     usc_criterion_backward_ex (wts = NULL: no DropLoss) */
+int usc_criterion_target_bits_wide(const uint8_t* tm, int32_t T, int32_t S, uint32_t* bits,
+                                   int32_t* cnt, usc_stream_t s);
+int usc_criterion_costs_wide(const float* const* masks, int32_t L, int32_t ld, int32_t S,
+                             int32_t Q, int32_t T, const uint32_t* bits, const int32_t* cnt,
+                             const float* logits, int64_t ls_level, int64_t ls_q, int32_t C,
+                             const int64_t* labels, float w_mask, float w_class, float w_dice,
+                             float* cost, float* cmask, float* cdice, float* nmat, float* ssum,
+                             float* logp, void* ws, int64_t ws_bytes, usc_stream_t s);
+int usc_criterion_drop_counts_wide(const float* const* masks, int32_t L, int32_t ld, int32_t S,
+                                   int32_t Q, int32_t T, const uint32_t* bits,
+                                   const int64_t* src, const int64_t* tid, int32_t* counts,
+                                   usc_stream_t s);
+int usc_criterion_losses_wide(const float* cmask, const float* cdice, const float* logp,
+                              const int64_t* src, const int64_t* tid, const int64_t* labels,
+                              const float* class_w, int32_t L, int32_t Q, int32_t T, int32_t C,
+                              int32_t noobj, int32_t* tcls, float* part, const int32_t* counts,
+                              const int32_t* cnt, float thresh, float* wts, usc_stream_t s);
+int usc_criterion_backward_wide(const float* const* masks, float* const* dmasks, int32_t L,
+                                int32_t ld, int32_t S, int32_t Q, int32_t T,
+                                const uint32_t* bits, const int32_t* cnt, const int64_t* src,
+                                const int64_t* tid, const float* nmat, const float* ssum,
+                                const float* logp, const int32_t* tcls, const float* class_w,
+                                const float* gtable, const float* den_tot, int32_t C,
+                                int64_t ls_level, int64_t ls_q, float* dlogits, const float* wts,
+                                usc_stream_t s);
 
 /* Linear layer on a handful of rows (the 100 decoder queries):
  *   y[M,N] = x[M,K] W[N,K]^T + b[N]   (b may be NULL);  N, K multiples of 32.

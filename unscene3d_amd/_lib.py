@@ -188,6 +188,14 @@ SIGNATURES = {
                                           _p, _p]),
     "usc_criterion_backward_ex": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                             _p, _i32, _i64, _i64, _p, _p, _p]),
+    "usc_criterion_target_bits_wide": (C.c_int, [_p, _i32, _i32, _p, _p, _p]),
+    "usc_criterion_costs_wide": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _i64, _i32, _p, _f32, _f32,
+                                           _f32, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "usc_criterion_drop_counts_wide": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
+    "usc_criterion_losses_wide": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _f32,
+                                            _p, _p]),
+    "usc_criterion_backward_wide": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                              _p, _i32, _i64, _i64, _p, _p, _p]),
     "usc_self_attn_fwd": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p]),
     "usc_self_attn_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
     "usc_linear_fwd": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p]),

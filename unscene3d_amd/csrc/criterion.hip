@@ -400,6 +400,15 @@ int usc_lsap_batch(const float* cost, int32_t n_prob, int32_t nr, int32_t nc, in
 //                  w = [U > 0 and f32(I) / f32(U) >= thresh], U = F + |target| - I, and leaves dropped pairs out of the
 //                  same fixed-order sums; crit_bwd_masks<true> writes their columns as exact zeros
 // Every sum has a fixed order; the target masks travel as one bit per (row, target) (T <= 32).
+//
+// 33 .. 128 targets (the usc_criterion_*_wide entry points): the bits become W = ceil(T / 32) words per row, stored
+// word-major (bits u32[W, S]: word w is a contiguous u32[S] in exactly the layout above, for the targets 32w .. 32w+31).
+// The cost pair crit_partial<TMAX> + crit_cost<TMAX> runs once per word, one word after the other on the stream and over
+// the same workspace: word w reads bits + w S, labels + 32w and cnt + 32w, handles min(32, T - 32w) targets and writes
+// the columns 32w .. of the [L, Q, T] outputs at row stride T.  The per-pair arithmetic is the one of the <= 32 path, so
+// a pair's cost does not depend on how many other targets the scene has; ssum / logp do not depend on the word and are
+// rewritten with the same bits by every word.  No TMAX above 32: 3 TMAX accumulators per lane are 96 registers already.
+// Everything after the costs looks a target's bit up as word tid >> 5, bit tid & 31.
 namespace usc {
 namespace {
 
@@ -411,17 +420,19 @@ struct CritLevels { const float* x[kCritMaxLevels]; float* dx[kCritMaxLevels]; }
 template <int TMAX> constexpr int kCritRows = 3 * TMAX + 2;
 __device__ inline float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 
-// tm u8[T, S] -> bits u32[S] (bit t = tm[t, s] != 0), cnt i32[T] += popcount (integer atomics: exact)
+// tm u8[T, S] -> bits u32[W, S] (word w = blockIdx.y, bit t of it = tm[32w + t, s] != 0), cnt i32[T] += popcount
+// (integer atomics: exact).  One word (T <= 32, gridDim.y = 1): bits u32[S]
 __global__ __launch_bounds__(256) void crit_target_bits_kernel(const uint8_t* __restrict__ tm, int T, int S,
                                                                uint32_t* __restrict__ bits, int32_t* __restrict__ cnt) {
   const int s = blockIdx.x * 256 + threadIdx.x;
+  const int t0 = 32 * (int)blockIdx.y, n = T - t0 < 32 ? T - t0 : 32;
   uint32_t b = 0;
   if (s < S)
-    for (int t = 0; t < T; ++t) b |= (tm[(int64_t)t * S + s] != 0 ? 1u : 0u) << t;
-  if (s < S) bits[s] = b;
-  for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < n; ++t) b |= (tm[(int64_t)(t0 + t) * S + s] != 0 ? 1u : 0u) << t;
+  if (s < S) bits[(int64_t)blockIdx.y * S + s] = b;
+  for (int t = 0; t < n; ++t) {
     const unsigned long long m = __ballot((b >> t) & 1u);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&cnt[t], (int)__popcll(m));
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&cnt[t0 + t], (int)__popcll(m));
   }
 }
 
@@ -469,11 +480,13 @@ struct CritCostArgs {
   const float* partial; int nchunk;
   const float* logits; int64_t ls_level, ls_q; int C;          // logits[l*ls_level + q*ls_q + c]
   const int64_t* labels; const int32_t* cnt;
-  int S, Q, T; float w_mask, w_class, w_dice;
-  float* cost;      // [L, Q, T]  (the LSAP input)
-  float* cmask;     // [L, Q, T]
-  float* cdice;     // [L, Q, T]
-  float* nmat;      // [L, Q, T]  sum_s sigmoid(x) tm
+  int S, Q, T;      // T: the targets of this launch (one 32-target word of the scene's)
+  int t0, tstride;  // their first column in the outputs and the outputs' row stride (0 and T up to 32 targets)
+  float w_mask, w_class, w_dice;
+  float* cost;      // [L, Q, tstride]  (the LSAP input)
+  float* cmask;     // [L, Q, tstride]
+  float* cdice;     // [L, Q, tstride]
+  float* nmat;      // [L, Q, tstride]  sum_s sigmoid(x) tm
   float* ssum;      // [L, Q]     sum_s sigmoid(x)
   float* logp;      // [L, Q, C]  log softmax of the class logits
 };
@@ -506,7 +519,7 @@ __global__ __launch_bounds__(128) void crit_cost_kernel(CritCostArgs a) {
   float* lp = a.logp + ((int64_t)l * a.Q + q) * a.C;
   for (int c = 0; c < a.C; ++c) lp[c] = (lg[c] - mx) - lse;
   a.ssum[(int64_t)l * a.Q + q] = ssum;
-  const int64_t o = ((int64_t)l * a.Q + q) * a.T;
+  const int64_t o = ((int64_t)l * a.Q + q) * a.tstride + a.t0;
 #pragma unroll
   for (int t = 0; t < TMAX; ++t) {
     if (t < a.T) {
@@ -531,7 +544,7 @@ __global__ __launch_bounds__(128) void crit_cost_kernel(CritCostArgs a) {
 // its target, in integers, and adds them to counts i32[2, L, T] (I | F, pair order = the row order of src / tid), which
 // the caller has zeroed.  Columns >= Q are never read.
 __global__ __launch_bounds__(128) void crit_drop_counts_kernel(CritLevels lv, int ld, int S, int Q, int T, int L,
-                                                               const uint32_t* __restrict__ bits,
+                                                               const uint32_t* __restrict__ bits_all,
                                                                const int64_t* __restrict__ src,
                                                                const int64_t* __restrict__ tid,
                                                                int32_t* __restrict__ counts) {
@@ -546,7 +559,10 @@ __global__ __launch_bounds__(128) void crit_drop_counts_kernel(CritLevels lv, in
   __syncthreads();
   const int p = col < Q ? pmap[col] : -1;
   if (p < 0) return;
-  const int t = (int)tid[(int64_t)l * T + p] & 31;
+  // the target's bit: word tid >> 5 of the word-major bits, bit tid & 31 (an id outside [0, T) reads inside the array)
+  const int tg = (int)tid[(int64_t)l * T + p] & 127, t = tg & 31;
+  const int wlast = (T - 1) >> 5;
+  const uint32_t* __restrict__ bits = bits_all + (int64_t)(tg >> 5 < wlast ? tg >> 5 : wlast) * S;
   const float* __restrict__ X = lv.x[l];
   const int s0 = chunk * 32, s1 = s0 + 32 < S ? s0 + 32 : S;
   int nI = 0, nF = 0;
@@ -597,7 +613,7 @@ __global__ __launch_bounds__(128) void crit_loss_kernel(const float* __restrict_
   }
   if (q == 0) {
     // the BCE terms of a level can be equal to the last bit (identical queries early in training): added in f32, T of
-    // them drift by T/2 ulps; <= 32 terms on one thread in f64 keep the mean at the terms' own accuracy
+    // them drift by T/2 ulps; <= 128 terms on one thread in f64 keep the mean at the terms' own accuracy
     double lm = 0.0;
     float ldice = 0.f;
     for (int t = 0; t < T; ++t) {
@@ -670,12 +686,14 @@ __global__ __launch_bounds__(128) void crit_bwd_masks_kernel(CritBwdArgs a) {
   }
   const float N = a.nmat[((int64_t)l * a.Q + col) * a.T + t];
   const float D1 = a.ssum[(int64_t)l * a.Q + col] + (float)a.cnt[t] + 1.f;
+  const uint32_t* __restrict__ wbits = a.bits + (int64_t)(t >> 5) * a.S;      // the word of this column's target
+  const int bit = t & 31;
   const float ga = a.gtable[l * 4 + 1] / ((float)a.S * (float)a.T);
   const float gb = a.gtable[l * 4 + 2] / (float)a.T / (D1 * D1);
   const float c1 = 2.f * N + 1.f, c2 = 2.f * D1;
   for (int s = s0; s < s1; ++s) {
     const float x = X[(int64_t)s * a.ld + col];
-    const float y = (a.bits[s] >> t) & 1u ? 1.f : 0.f;
+    const float y = (wbits[s] >> bit) & 1u ? 1.f : 0.f;
     const float sg = sigmoid_f(x);
     dX[(int64_t)s * a.ld + col] = ga * (sg - y) + gb * (sg * (1.f - sg)) * (c1 - y * c2);
   }
@@ -716,14 +734,58 @@ int64_t usc_criterion_ws_bytes(int32_t L, int32_t S, int32_t T) {
   return usc::align_up((int64_t)L * nchunk * (3 * usc::tmax_of(T) + 2) * usc::kCritCols * 4, 256);
 }
 
-int usc_criterion_target_bits(const uint8_t* tm, int32_t T, int32_t S, uint32_t* bits, int32_t* cnt, usc_stream_t s) {
-  USC_REQUIRE(T >= 1 && T <= 32 && S >= 1, "usc_criterion_target_bits: needs 1..32 targets");
-  USC_REQUIRE(tm && bits && cnt, "usc_criterion_target_bits: null argument");
+// Every entry point exists twice: the <= 32-target one (one word of target bits per row) and its _wide twin for up to
+// 128 targets (W = ceil(T / 32) words, word-major).  Both run the same kernels; `tcap` is the entry point's bound.
+static int crit_target_bits(const uint8_t* tm, int32_t T, int32_t S, uint32_t* bits, int32_t* cnt, usc_stream_t s,
+                            int tcap, const char* name) {
+  USC_REQUIRE(T >= 1 && T <= tcap && S >= 1, "%s: needs 1..%d targets", name, tcap);
+  USC_REQUIRE(tm && bits && cnt, "%s: null argument", name);
   hipStream_t st = usc::as_stream(s);
   (void)hipMemsetAsync(cnt, 0, (size_t)T * 4, st);
-  hipLaunchKernelGGL(usc::crit_target_bits_kernel, dim3((unsigned)usc::ceil_div(S, 256)), dim3(256), 0, st, tm, (int)T,
-                     (int)S, bits, cnt);
-  USC_CHECK_LAUNCH("usc_criterion_target_bits");
+  hipLaunchKernelGGL(usc::crit_target_bits_kernel, dim3((unsigned)usc::ceil_div(S, 256), (unsigned)usc::ceil_div(T, 32)),
+                     dim3(256), 0, st, tm, (int)T, (int)S, bits, cnt);
+  USC_CHECK_LAUNCH(name);
+  return USC_OK;
+}
+
+int usc_criterion_target_bits(const uint8_t* tm, int32_t T, int32_t S, uint32_t* bits, int32_t* cnt, usc_stream_t s) {
+  return crit_target_bits(tm, T, S, bits, cnt, s, 32, "usc_criterion_target_bits");
+}
+
+int usc_criterion_target_bits_wide(const uint8_t* tm, int32_t T, int32_t S, uint32_t* bits, int32_t* cnt,
+                                   usc_stream_t s) {
+  return crit_target_bits(tm, T, S, bits, cnt, s, 128, "usc_criterion_target_bits_wide");
+}
+
+static int crit_costs(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
+                      const uint32_t* bits, const int32_t* cnt, const float* logits, int64_t ls_level, int64_t ls_q,
+                      int32_t C, const int64_t* labels, float w_mask, float w_class, float w_dice, float* cost,
+                      float* cmask, float* cdice, float* nmat, float* ssum, float* logp, void* ws, int64_t ws_bytes,
+                      usc_stream_t s, int tcap, const char* name) {
+  using namespace usc;
+  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && T >= 1 && T <= tcap &&
+                  (tcap == 32 || T <= Q) && S >= 1 && C >= 1,
+              "%s: needs <= 16 levels, <= 128 queries, 1..%d targets%s", name, tcap,
+              tcap == 32 ? "" : ", not more targets than queries");
+  USC_REQUIRE(masks && bits && cnt && logits && labels && cost && cmask && cdice && nmat && ssum && logp && ws &&
+                  ws_bytes >= usc_criterion_ws_bytes(L, S, T), "%s: bad argument", name);
+  CritLevels lv{};
+  for (int l = 0; l < L; ++l) { USC_REQUIRE(masks[l], "%s: null level", name); lv.x[l] = masks[l]; }
+  const int nchunk = (int)ceil_div(S, 32);
+  hipStream_t st = as_stream(s);
+  // one 32-target word after the other, over the same workspace (stream order keeps word w + 1 behind word w)
+  for (int t0 = 0; t0 < T; t0 += 32) {
+    const int Tw = T - t0 < 32 ? T - t0 : 32;
+    const uint32_t* wbits = bits + (int64_t)(t0 / 32) * S;
+    CritCostArgs ca{(const float*)ws, nchunk, logits, ls_level, ls_q, C, labels + t0, cnt + t0, S, Q, Tw, t0, T,
+                    w_mask, w_class, w_dice, cost, cmask, cdice, nmat, ssum, logp};
+    switch (tmax_of(Tw)) {
+      case 8: launch_cost<8>(lv, L, ld, S, Q, wbits, nchunk, (float*)ws, ca, st); break;
+      case 16: launch_cost<16>(lv, L, ld, S, Q, wbits, nchunk, (float*)ws, ca, st); break;
+      default: launch_cost<32>(lv, L, ld, S, Q, wbits, nchunk, (float*)ws, ca, st); break;
+    }
+  }
+  USC_CHECK_LAUNCH(name);
   return USC_OK;
 }
 
@@ -732,53 +794,60 @@ int usc_criterion_costs(const float* const* masks, int32_t L, int32_t ld, int32_
                         int32_t C, const int64_t* labels, float w_mask, float w_class, float w_dice, float* cost,
                         float* cmask, float* cdice, float* nmat, float* ssum, float* logp, void* ws, int64_t ws_bytes,
                         usc_stream_t s) {
+  return crit_costs(masks, L, ld, S, Q, T, bits, cnt, logits, ls_level, ls_q, C, labels, w_mask, w_class, w_dice, cost,
+                    cmask, cdice, nmat, ssum, logp, ws, ws_bytes, s, 32, "usc_criterion_costs");
+}
+
+int usc_criterion_costs_wide(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
+                             const uint32_t* bits, const int32_t* cnt, const float* logits, int64_t ls_level,
+                             int64_t ls_q, int32_t C, const int64_t* labels, float w_mask, float w_class, float w_dice,
+                             float* cost, float* cmask, float* cdice, float* nmat, float* ssum, float* logp, void* ws,
+                             int64_t ws_bytes, usc_stream_t s) {
+  return crit_costs(masks, L, ld, S, Q, T, bits, cnt, logits, ls_level, ls_q, C, labels, w_mask, w_class, w_dice, cost,
+                    cmask, cdice, nmat, ssum, logp, ws, ws_bytes, s, 128, "usc_criterion_costs_wide");
+}
+
+static int crit_drop_counts(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
+                            const uint32_t* bits, const int64_t* src, const int64_t* tid, int32_t* counts,
+                            usc_stream_t s, int tcap, const char* name) {
   using namespace usc;
-  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && T >= 1 && T <= 32 && S >= 1 && C >= 1,
-              "usc_criterion_costs: needs <= 16 levels, <= 128 queries, 1..32 targets");
-  USC_REQUIRE(masks && bits && cnt && logits && labels && cost && cmask && cdice && nmat && ssum && logp && ws &&
-                  ws_bytes >= usc_criterion_ws_bytes(L, S, T), "usc_criterion_costs: bad argument");
+  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && T >= 1 && T <= tcap && T <= Q && S >= 1,
+              "%s: needs <= 16 levels, <= 128 queries, 1..%d targets", name, tcap);
+  USC_REQUIRE(masks && bits && src && tid && counts, "%s: null argument", name);
   CritLevels lv{};
-  for (int l = 0; l < L; ++l) { USC_REQUIRE(masks[l], "usc_criterion_costs: null level"); lv.x[l] = masks[l]; }
-  const int nchunk = (int)ceil_div(S, 32);
-  CritCostArgs ca{(const float*)ws, nchunk, logits, ls_level, ls_q, C, labels, cnt, S, Q, T, w_mask, w_class, w_dice,
-                  cost, cmask, cdice, nmat, ssum, logp};
+  for (int l = 0; l < L; ++l) { USC_REQUIRE(masks[l], "%s: null level", name); lv.x[l] = masks[l]; }
   hipStream_t st = as_stream(s);
-  switch (tmax_of(T)) {
-    case 8: launch_cost<8>(lv, L, ld, S, Q, bits, nchunk, (float*)ws, ca, st); break;
-    case 16: launch_cost<16>(lv, L, ld, S, Q, bits, nchunk, (float*)ws, ca, st); break;
-    default: launch_cost<32>(lv, L, ld, S, Q, bits, nchunk, (float*)ws, ca, st); break;
-  }
-  USC_CHECK_LAUNCH("usc_criterion_costs");
+  (void)hipMemsetAsync(counts, 0, (size_t)2 * L * T * 4, st);
+  hipLaunchKernelGGL(crit_drop_counts_kernel, dim3((unsigned)ceil_div(S, 32), L), dim3(128), 0, st, lv, (int)ld, (int)S,
+                     (int)Q, (int)T, (int)L, bits, src, tid, counts);
+  USC_CHECK_LAUNCH(name);
   return USC_OK;
 }
 
 int usc_criterion_drop_counts(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
                               const uint32_t* bits, const int64_t* src, const int64_t* tid, int32_t* counts,
                               usc_stream_t s) {
-  using namespace usc;
-  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && T >= 1 && T <= 32 && T <= Q && S >= 1,
-              "usc_criterion_drop_counts: needs <= 16 levels, <= 128 queries, 1..32 targets");
-  USC_REQUIRE(masks && bits && src && tid && counts, "usc_criterion_drop_counts: null argument");
-  CritLevels lv{};
-  for (int l = 0; l < L; ++l) { USC_REQUIRE(masks[l], "usc_criterion_drop_counts: null level"); lv.x[l] = masks[l]; }
-  hipStream_t st = as_stream(s);
-  (void)hipMemsetAsync(counts, 0, (size_t)2 * L * T * 4, st);
-  hipLaunchKernelGGL(crit_drop_counts_kernel, dim3((unsigned)ceil_div(S, 32), L), dim3(128), 0, st, lv, (int)ld, (int)S,
-                     (int)Q, (int)T, (int)L, bits, src, tid, counts);
-  USC_CHECK_LAUNCH("usc_criterion_drop_counts");
-  return USC_OK;
+  return crit_drop_counts(masks, L, ld, S, Q, T, bits, src, tid, counts, s, 32, "usc_criterion_drop_counts");
 }
 
-int usc_criterion_losses_ex(const float* cmask, const float* cdice, const float* logp, const int64_t* src,
-                            const int64_t* tid, const int64_t* labels, const float* class_w, int32_t L, int32_t Q,
-                            int32_t T, int32_t C, int32_t noobj, int32_t* tcls, float* part, const int32_t* counts,
-                            const int32_t* cnt, float thresh, float* wts, usc_stream_t s) {
+int usc_criterion_drop_counts_wide(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
+                                   const uint32_t* bits, const int64_t* src, const int64_t* tid, int32_t* counts,
+                                   usc_stream_t s) {
+  return crit_drop_counts(masks, L, ld, S, Q, T, bits, src, tid, counts, s, 128, "usc_criterion_drop_counts_wide");
+}
+
+static int crit_losses(const float* cmask, const float* cdice, const float* logp, const int64_t* src,
+                       const int64_t* tid, const int64_t* labels, const float* class_w, int32_t L, int32_t Q,
+                       int32_t T, int32_t C, int32_t noobj, int32_t* tcls, float* part, const int32_t* counts,
+                       const int32_t* cnt, float thresh, float* wts, usc_stream_t s, int tcap, const char* name) {
   using namespace usc;
-  USC_REQUIRE(L >= 1 && Q >= 1 && Q <= kCritCols && T >= 1 && T <= 32 && T <= Q && C >= 1 && noobj >= 0 && noobj < C,
-              "usc_criterion_losses: bad sizes");
-  USC_REQUIRE(cmask && cdice && logp && src && tid && labels && class_w && tcls && part, "usc_criterion_losses: null argument");
+  USC_REQUIRE(L >= 1 && (tcap == 32 || L <= kCritMaxLevels) && Q >= 1 && Q <= kCritCols && T >= 1 && T <= tcap &&
+                  T <= Q && C >= 1 && noobj >= 0 && noobj < C,
+              "%s: bad sizes (needs%s <= 128 queries, 1..%d targets, not more than queries)", name,
+              tcap == 32 ? "" : " <= 16 levels,", tcap);
+  USC_REQUIRE(cmask && cdice && logp && src && tid && labels && class_w && tcls && part, "%s: null argument", name);
   USC_REQUIRE((counts && cnt && wts) || (!counts && !cnt && !wts),
-              "usc_criterion_losses_ex: counts, cnt and wts go together (all three, or none for no DropLoss)");
+              "%s: counts, cnt and wts go together (all three, or none for no DropLoss)", name);
   if (wts)
     hipLaunchKernelGGL(crit_loss_kernel<true>, dim3(L), dim3(128), 0, as_stream(s), cmask, cdice, logp, src, tid, labels,
                        class_w, (int)Q, (int)T, (int)C, (int)noobj, tcls, part, counts, cnt, thresh, wts);
@@ -786,8 +855,16 @@ int usc_criterion_losses_ex(const float* cmask, const float* cdice, const float*
     hipLaunchKernelGGL(crit_loss_kernel<false>, dim3(L), dim3(128), 0, as_stream(s), cmask, cdice, logp, src, tid, labels,
                        class_w, (int)Q, (int)T, (int)C, (int)noobj, tcls, part, (const int32_t*)nullptr,
                        (const int32_t*)nullptr, 0.f, (float*)nullptr);
-  USC_CHECK_LAUNCH("usc_criterion_losses");
+  USC_CHECK_LAUNCH(name);
   return USC_OK;
+}
+
+int usc_criterion_losses_ex(const float* cmask, const float* cdice, const float* logp, const int64_t* src,
+                            const int64_t* tid, const int64_t* labels, const float* class_w, int32_t L, int32_t Q,
+                            int32_t T, int32_t C, int32_t noobj, int32_t* tcls, float* part, const int32_t* counts,
+                            const int32_t* cnt, float thresh, float* wts, usc_stream_t s) {
+  return crit_losses(cmask, cdice, logp, src, tid, labels, class_w, L, Q, T, C, noobj, tcls, part, counts, cnt, thresh,
+                     wts, s, 32, "usc_criterion_losses");
 }
 
 int usc_criterion_losses(const float* cmask, const float* cdice, const float* logp, const int64_t* src, const int64_t* tid,
@@ -795,6 +872,14 @@ int usc_criterion_losses(const float* cmask, const float* cdice, const float* lo
                          int32_t noobj, int32_t* tcls, float* part, usc_stream_t s) {
   return usc_criterion_losses_ex(cmask, cdice, logp, src, tid, labels, class_w, L, Q, T, C, noobj, tcls, part, nullptr,
                                  nullptr, 0.f, nullptr, s);
+}
+
+int usc_criterion_losses_wide(const float* cmask, const float* cdice, const float* logp, const int64_t* src,
+                              const int64_t* tid, const int64_t* labels, const float* class_w, int32_t L, int32_t Q,
+                              int32_t T, int32_t C, int32_t noobj, int32_t* tcls, float* part, const int32_t* counts,
+                              const int32_t* cnt, float thresh, float* wts, usc_stream_t s) {
+  return crit_losses(cmask, cdice, logp, src, tid, labels, class_w, L, Q, T, C, noobj, tcls, part, counts, cnt, thresh,
+                     wts, s, 128, "usc_criterion_losses_wide");
 }
 
 int usc_criterion_table(const float* parts, int32_t B, int32_t L, float* table, float* den_tot, usc_stream_t s) {
@@ -806,19 +891,21 @@ int usc_criterion_table(const float* parts, int32_t B, int32_t L, float* table, 
   return USC_OK;
 }
 
-int usc_criterion_backward_ex(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S, int32_t Q,
-                              int32_t T, const uint32_t* bits, const int32_t* cnt, const int64_t* src, const int64_t* tid,
-                              const float* nmat, const float* ssum, const float* logp, const int32_t* tcls,
-                              const float* class_w, const float* gtable, const float* den_tot, int32_t C, int64_t ls_level,
-                              int64_t ls_q, float* dlogits, const float* wts, usc_stream_t s) {
+static int crit_backward(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S, int32_t Q,
+                         int32_t T, const uint32_t* bits, const int32_t* cnt, const int64_t* src, const int64_t* tid,
+                         const float* nmat, const float* ssum, const float* logp, const int32_t* tcls,
+                         const float* class_w, const float* gtable, const float* den_tot, int32_t C, int64_t ls_level,
+                         int64_t ls_q, float* dlogits, const float* wts, usc_stream_t s, int tcap, const char* name) {
   using namespace usc;
   USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && ld <= kCritCols && T >= 1 &&
-                  T <= 32 && S >= 1 && C >= 1, "usc_criterion_backward: bad sizes");
+                  T <= tcap && (tcap == 32 || T <= Q) && S >= 1 && C >= 1,
+              "%s: bad sizes (needs <= 16 levels, <= 128 queries and columns, 1..%d targets%s)", name, tcap,
+              tcap == 32 ? "" : ", not more than queries");
   USC_REQUIRE(masks && dmasks && bits && cnt && src && tid && nmat && ssum && logp && tcls && class_w && gtable &&
-                  den_tot && dlogits, "usc_criterion_backward: null argument");
+                  den_tot && dlogits, "%s: null argument", name);
   CritBwdArgs a{};
   for (int l = 0; l < L; ++l) {
-    USC_REQUIRE(masks[l] && dmasks[l], "usc_criterion_backward: null level");
+    USC_REQUIRE(masks[l] && dmasks[l], "%s: null level", name);
     a.lv.x[l] = masks[l];
     a.lv.dx[l] = dmasks[l];
   }
@@ -829,8 +916,17 @@ int usc_criterion_backward_ex(const float* const* masks, float* const* dmasks, i
   else hipLaunchKernelGGL(crit_bwd_masks_kernel<false>, dim3(a.nchunk, L), dim3(128), 0, st, a);
   hipLaunchKernelGGL(crit_bwd_logits_kernel, dim3(L), dim3(128), 0, st, logp, tcls, class_w, gtable, den_tot, (int)Q, (int)C,
                      ls_level, ls_q, dlogits);
-  USC_CHECK_LAUNCH("usc_criterion_backward");
+  USC_CHECK_LAUNCH(name);
   return USC_OK;
+}
+
+int usc_criterion_backward_ex(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S, int32_t Q,
+                              int32_t T, const uint32_t* bits, const int32_t* cnt, const int64_t* src, const int64_t* tid,
+                              const float* nmat, const float* ssum, const float* logp, const int32_t* tcls,
+                              const float* class_w, const float* gtable, const float* den_tot, int32_t C, int64_t ls_level,
+                              int64_t ls_q, float* dlogits, const float* wts, usc_stream_t s) {
+  return crit_backward(masks, dmasks, L, ld, S, Q, T, bits, cnt, src, tid, nmat, ssum, logp, tcls, class_w, gtable,
+                       den_tot, C, ls_level, ls_q, dlogits, wts, s, 32, "usc_criterion_backward");
 }
 
 int usc_criterion_backward(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S, int32_t Q,
@@ -840,6 +936,16 @@ int usc_criterion_backward(const float* const* masks, float* const* dmasks, int3
                            int64_t ls_q, float* dlogits, usc_stream_t s) {
   return usc_criterion_backward_ex(masks, dmasks, L, ld, S, Q, T, bits, cnt, src, tid, nmat, ssum, logp, tcls, class_w,
                                    gtable, den_tot, C, ls_level, ls_q, dlogits, nullptr, s);
+}
+
+int usc_criterion_backward_wide(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S,
+                                int32_t Q, int32_t T, const uint32_t* bits, const int32_t* cnt, const int64_t* src,
+                                const int64_t* tid, const float* nmat, const float* ssum, const float* logp,
+                                const int32_t* tcls, const float* class_w, const float* gtable, const float* den_tot,
+                                int32_t C, int64_t ls_level, int64_t ls_q, float* dlogits, const float* wts,
+                                usc_stream_t s) {
+  return crit_backward(masks, dmasks, L, ld, S, Q, T, bits, cnt, src, tid, nmat, ssum, logp, tcls, class_w, gtable,
+                       den_tot, C, ls_level, ls_q, dlogits, wts, s, 128, "usc_criterion_backward_wide");
 }
 
 }  // extern "C"

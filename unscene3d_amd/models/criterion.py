@@ -9,11 +9,13 @@ reference line by line.  `SetCriterion.forward` takes one of three paths:
   gradients of all levels stay on the device, nothing is copied to the host.  Runs when `_fused_tables` accepts the
   inputs: USC3D_FUSED_CRITERION is not 0, labels + masks losses on all points without the noise-robust loss
   (`_plain_losses`), float32 HIP predictions with 1-16 levels and at most 128 queries, and per scene 1-32 targets whose
-  masks and labels are on the device.
+  masks and labels are on the device.  `SetCriterion(device_max_targets=N)`, 32 <= N <= 128 (config:
+  `loss.device_max_targets`), raises the 32 to min(N, queries): such scenes run the wide entry points of
+  criterion_device.py (one pass of the cost kernels per 32 targets).
 * batched operators: `match_all_levels` builds all levels' cost matrices with torch operators and copies them to the host
   in ONE transfer (the reference syncs 13*B times), scipy solves them, `_batched_losses` computes all levels at once.
-  Runs for `_plain_losses` inputs the device path does not take (CPU tensors, more than 32 targets, ...); on HIP
-  tensors it warns once.
+  Runs for `_plain_losses` inputs the device path does not take (CPU tensors, more than `device_max_targets` targets,
+  ...); on HIP tensors it warns once.
 * per level: `get_loss` level by level, as the reference does.  Runs for everything else: point sub-sampling, the
   noise-robust loss, another list of losses, or imposed assignments of unequal length."""
 import os
@@ -62,7 +64,8 @@ class _FusedCriterion(torch.autograd.Function):
             labels = targets[b]["labels"].to(torch.int64).contiguous()
             tm8 = tm.contiguous().view(torch.uint8) if tm.dtype == torch.bool else (tm != 0).contiguous().view(torch.uint8)
             sc = D.scene_forward(tabs_b, tm8, labels, logits, b, (m.cost_mask, m.cost_class, m.cost_dice),
-                                 crit.empty_weight, crit.num_classes, parts[b], thresh)
+                                 crit.empty_weight, crit.num_classes, parts[b], thresh,
+                                 max_targets=crit.device_max_targets)
             scenes.append(sc._replace(cost=None, counts=None))          # the backward needs neither: freed here, as before
             tabs.extend(tabs_b)
         table, den_tot = D.table(parts)
@@ -71,6 +74,7 @@ class _FusedCriterion(torch.autograd.Function):
         # Function's own tensors
         ctx.save_for_backward(*tabs)
         ctx.scenes, ctx.den_tot, ctx.shape, ctx.class_w = scenes, den_tot, (L, B, Q, NC), crit.empty_weight
+        ctx.max_targets = crit.device_max_targets
         crit.last_indices = [[(sc.src[l], sc.tid[l]) for sc in scenes] for l in range(L)]              # device tensors
         crit.last_drop_weights = [[sc.wts[l] for sc in scenes] for l in range(L)] if crit.use_droploss else None
         crit.last_lsap_status = [sc.status for sc in scenes]
@@ -86,7 +90,8 @@ class _FusedCriterion(torch.autograd.Function):
         grads = []
         saved = ctx.saved_tensors
         for b, sc in enumerate(ctx.scenes):
-            dtab = D.scene_backward(sc, saved[b * L:(b + 1) * L], b, ctx.class_w, g, ctx.den_tot, dlogits)
+            dtab = D.scene_backward(sc, saved[b * L:(b + 1) * L], b, ctx.class_w, g, ctx.den_tot, dlogits,
+                                    max_targets=ctx.max_targets)
             grads.extend(dtab.unbind(0))
         return (None, None, None, dlogits, *grads)
 
@@ -110,8 +115,14 @@ def _loss_dict(flat, L):
 class SetCriterion(nn.Module):
     def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses, num_points, oversample_ratio,
                  importance_sample_ratio, class_weights, directions="xyz", use_droploss=False,
-                 droploss_iou_thresh=0.1):
+                 droploss_iou_thresh=0.1, device_max_targets=32):
         super().__init__()
+        # the most targets per scene the device criterion takes (32: one word of target bits per row; up to 128: the
+        # wide entry points, opt-in).  Scenes above it, or above the number of queries, take the operator path
+        if isinstance(device_max_targets, bool) or not isinstance(device_max_targets, int) \
+                or not 32 <= device_max_targets <= 128:
+            raise ValueError(f"SetCriterion: device_max_targets must be an integer in 32 .. 128, not {device_max_targets!r}")
+        self.device_max_targets = device_max_targets
         self.num_classes = num_classes - 1
         self.class_weights, self.matcher, self.weight_dict = class_weights, matcher, weight_dict
         self.eos_coef, self.losses = eos_coef, list(losses)
@@ -348,7 +359,8 @@ class SetCriterion(nn.Module):
 
     def _fused_tables(self, levels, targets, mask_type):
         """The per-(scene, level) mask-logit tables [S, ld] for the device criterion, or None when the fused path does
-        not apply (CPU tensors, sub-sampled points, noise-robust loss, > 32 targets or > 128 queries ...)."""
+        not apply (CPU tensors, sub-sampled points, noise-robust loss, more than min(device_max_targets, Q) targets in a
+        scene — device_max_targets is 32 unless the constructor was given up to 128 — or > 128 queries ...)."""
         if not (FUSED and self._plain_losses() and self.matcher.num_points == -1 and targets and 1 <= len(levels) <= 16):
             return None
         lg = levels[0]["pred_logits"]
@@ -359,7 +371,7 @@ class SetCriterion(nn.Module):
         tables = []
         for b, tgt in enumerate(targets):
             tm = tgt.get(mask_type)
-            if tm is None or not tm.is_cuda or not (1 <= tm.shape[0] <= min(32, Q)) or "labels" not in tgt:
+            if tm is None or not tm.is_cuda or not (1 <= tm.shape[0] <= min(self.device_max_targets, Q)) or "labels" not in tgt:
                 return None
             lab = tgt["labels"]
             if not (torch.is_tensor(lab) and lab.is_cuda and lab.numel() == tm.shape[0]):
@@ -382,11 +394,12 @@ class SetCriterion(nn.Module):
         tables = self._fused_tables(levels, targets, mask_type)
         if tables is None and FUSED and levels[0]["pred_logits"].is_cuda and not self.__dict__.get("_warned_operator_path"):
             # e.g. a prediction table that lost its `_usc_padded` companion by being cloned / re-wrapped, host-side
-            # targets, > 32 targets: correct, but ~150 stock launches and a device->host copy per step slower
+            # targets, > device_max_targets targets: correct, but ~150 stock launches and a device->host copy per step slower
             self.__dict__["_warned_operator_path"] = True
             import warnings
             warnings.warn("SetCriterion: the device criterion (csrc/criterion.hip) does not apply to these inputs; "
-                          "using the torch-operator path (see SetCriterion._fused_tables for the conditions)")
+                          "using the torch-operator path (see SetCriterion._fused_tables for the conditions; scenes "
+                          f"with more than {self.device_max_targets} targets need a larger device_max_targets, up to 128)")
         if tables is not None:
             if is_dist_avail_and_initialized():   # the reference's collective (criterion.py:258-260); its result is
                 # never used by the losses (loss_masks overwrites num_masks, :189), so nobody waits for it here

@@ -134,7 +134,8 @@ class InstanceSegmentation(nn.Module):
                                       oversample_ratio=l.oversample_ratio,
                                       importance_sample_ratio=l.importance_sample_ratio,
                                       class_weights=l.class_weights, directions=l.directions,
-                                      use_droploss=l.use_droploss, droploss_iou_thresh=l.droploss_iou_thresh)
+                                      use_droploss=l.use_droploss, droploss_iou_thresh=l.droploss_iou_thresh,
+                                      device_max_targets=getattr(l, "device_max_targets", 32))
 
     def forward(self, x, point2segment=None, raw_coordinates=None, is_eval=False, num_segments=None):
         return self.model(x, point2segment, raw_coordinates=raw_coordinates, is_eval=is_eval,
