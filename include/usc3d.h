@@ -728,108 +728,68 @@ int usc_lsap_batch(const float* cost, int32_t n_prob, int32_t nr, int32_t nc,
                    int64_t* row_ind, int64_t* col_ind, int32_t* status, usc_stream_t s);
 
 /* The set criterion on the device, per scene and for all L <= 16 prediction levels at once (reference
- * models/matcher.py:98-168 cost matrices; models/criterion.py:22-73, :138-216 losses).  masks[l] / dmasks[l]: the
- * level's mask logits f32[S, ld] (ld >= Q columns, Q <= 128 queries) and their gradient; logits: class logits
- * addressed as logits[l*ls_level + q*ls_q + c], c < C; labels i64[T] (253 = ignore), T <= 32 targets.
- *   usc_criterion_target_bits  tm u8[T,S] -> bits u32[S] (bit t = row s belongs to target t), cnt i32[T] = |tm[t]|
+ * models/matcher.py:98-168 cost matrices; models/criterion.py:22-73, :138-216 losses, :194-200 DropLoss).  masks[l] /
+ * dmasks[l]: the level's mask logits f32[S, ld] (ld >= Q columns, Q <= 128 queries) and their gradient; logits: class
+ * logits addressed as logits[l*ls_level + q*ls_q + c], c < C; labels i64[T] (253 = ignore).
+ * max_targets, 32 .. 128 (anything else is an error), is the caller's bound on T: T outside 1 .. max_targets is
+ * refused before anything is launched (SetCriterion passes its device_max_targets, 32 unless opted in).  The target
+ * bits are W = ceil(T / 32) words per row, word-major: bits u32[W, S], word w = the targets 32w .. 32w+31; up to 32
+ * targets that is u32[S].  usc_criterion_drop_counts and _losses need T <= Q for every T; _costs and _backward need it
+ * only above 32 targets; _losses alone has no bound on L (its kernel takes no per-level pointer table).
+ *   usc_criterion_target_bits  tm u8[T,S] -> bits (bit t of word w = row s belongs to target 32w + t), cnt i32[T] =
+ *                              |tm[t]|
  *   usc_criterion_costs        cost = w_mask*BCE + w_class*(-p[label]) + w_dice*dice  f32[L,Q,T] (the LSAP input), its
  *                              parts cmask / cdice [L,Q,T], nmat [L,Q,T] = sum_s sigmoid(x) tm, ssum [L,Q] =
- *                              sum_s sigmoid(x), logp [L,Q,C] = log softmax (kept for the losses and the backward)
+ *                              sum_s sigmoid(x), logp [L,Q,C] = log softmax (kept for the losses and the backward).
+ *                              Once per word, one word after the other on the stream: word w fills the columns 32w ..
+ *                              (2 W launches); the workspace of usc_criterion_ws_bytes(L, S, T) is reused per word, so
+ *                              above 32 targets it is the 32-target size.  A pair's entries do not depend on the
+ *                              scene's other targets
+ *   usc_criterion_drop_counts  DropLoss only, after usc_lsap_batch: counts i32[2,L,T] = per matched pair (row order of
+ *                              src / tid) I = |pred & target| and F = |pred|, pred = (x > 0); integer sums, exact.
+ *                              counts is zeroed here
  *   usc_criterion_losses       src/tid i64[L,T] (usc_lsap_batch) -> part f32[L,4] = (sum w*nll, sum w, mask loss, dice
- *                              loss) of this scene, tcls i32[L,Q] = target class per query (noobj = C-1 unmatched)
+ *                              loss) of this scene, tcls i32[L,Q] = target class per query (noobj = C-1 unmatched).
+ *                              DropLoss (a matched pair whose prediction overlaps its target with IoU below thresh gets
+ *                              weight 0 in the mask and dice loss; the divisor stays T): given counts, cnt and thresh it
+ *                              writes wts f32[L,T] = 1 if U > 0 and f32(I) / f32(U) >= thresh else 0, U = F + cnt - I,
+ *                              and applies them inside the same fixed-order sums.  counts = cnt = wts = NULL: no DropLoss
  *   usc_criterion_table        parts [B,L,4] of the batch's scenes -> table [L,4] = (loss_ce, loss_mask, loss_dice, 0),
  *                              den_tot [L]
  *   usc_criterion_backward     gtable = d total / d table [L,4] -> dmasks (full padded width, zero outside the matched
- *                              columns) and dlogits (same addressing as logits)
+ *                              columns) and dlogits (same addressing as logits).  wts (usc_criterion_losses): the
+ *                              column of a pair with weight 0 is exactly 0.  wts = NULL: no DropLoss
  * Fixed summation order everywhere.  Replaces the torch op chains of HungarianMatcher.memory_efficient_forward and
- * SetCriterion.loss_labels / loss_masks. */
+ * SetCriterion.loss_labels / loss_masks, with DropLoss `(fg * tm).sum(1) / (fg + tm).sum(1) >= thresh` on the gathered
+ * [T, S] masks, and above 32 targets the operator path's device->host copy and scipy solve per level and scene. */
 int64_t usc_criterion_ws_bytes(int32_t L, int32_t S, int32_t T);
-int usc_criterion_target_bits(const uint8_t* tm, int32_t T, int32_t S, uint32_t* bits,
-                              int32_t* cnt, usc_stream_t s);
+int usc_criterion_target_bits(const uint8_t* tm, int32_t T, int32_t max_targets, int32_t S,
+                              uint32_t* bits, int32_t* cnt, usc_stream_t s);
 int usc_criterion_costs(const float* const* masks, int32_t L, int32_t ld, int32_t S,
-                        int32_t Q, int32_t T, const uint32_t* bits, const int32_t* cnt,
-                        const float* logits, int64_t ls_level, int64_t ls_q, int32_t C,
-                        const int64_t* labels, float w_mask, float w_class, float w_dice,
-                        float* cost, float* cmask, float* cdice, float* nmat, float* ssum,
-                        float* logp, void* ws, int64_t ws_bytes, usc_stream_t s);
+                        int32_t Q, int32_t T, int32_t max_targets, const uint32_t* bits,
+                        const int32_t* cnt, const float* logits, int64_t ls_level, int64_t ls_q,
+                        int32_t C, const int64_t* labels, float w_mask, float w_class,
+                        float w_dice, float* cost, float* cmask, float* cdice, float* nmat,
+                        float* ssum, float* logp, void* ws, int64_t ws_bytes, usc_stream_t s);
+int usc_criterion_drop_counts(const float* const* masks, int32_t L, int32_t ld, int32_t S,
+                              int32_t Q, int32_t T, int32_t max_targets, const uint32_t* bits,
+                              const int64_t* src, const int64_t* tid, int32_t* counts,
+                              usc_stream_t s);
 int usc_criterion_losses(const float* cmask, const float* cdice, const float* logp,
                          const int64_t* src, const int64_t* tid, const int64_t* labels,
-                         const float* class_w, int32_t L, int32_t Q, int32_t T, int32_t C,
-                         int32_t noobj, int32_t* tcls, float* part, usc_stream_t s);
+                         const float* class_w, int32_t L, int32_t Q, int32_t T,
+                         int32_t max_targets, int32_t C, int32_t noobj, int32_t* tcls, float* part,
+                         const int32_t* counts, const int32_t* cnt, float thresh, float* wts,
+                         usc_stream_t s);
 int usc_criterion_table(const float* parts, int32_t B, int32_t L, float* table,
                         float* den_tot, usc_stream_t s);
 int usc_criterion_backward(const float* const* masks, float* const* dmasks, int32_t L,
-                           int32_t ld, int32_t S, int32_t Q, int32_t T, const uint32_t* bits,
-                           const int32_t* cnt, const int64_t* src, const int64_t* tid,
-                           const float* nmat, const float* ssum, const float* logp,
-                           const int32_t* tcls, const float* class_w, const float* gtable,
-                           const float* den_tot, int32_t C, int64_t ls_level, int64_t ls_q,
-                           float* dlogits, usc_stream_t s);
-/* DropLoss inside the device criterion (reference models/criterion.py:194-200: a matched pair whose prediction
- * (x > 0) overlaps its target with IoU below the threshold gets weight 0 in loss_mask and loss_dice; the divisor stays
- * T).  Replaces the torch op chain `(fg * tm).sum(1) / (fg + tm).sum(1) >= thresh` on the gathered [T, S] masks.
- *   usc_criterion_drop_counts  after usc_lsap_batch: counts i32[2,L,T] = per matched pair (row order of src / tid)
- *                              I = |pred & target| and F = |pred|; integer sums, exact.  counts is zeroed here
- *   usc_criterion_losses_ex    usc_criterion_losses that also takes counts, cnt i32[T] (usc_criterion_target_bits) and
- *                              the threshold and writes wts f32[L,T] = 1 if U > 0 and f32(I) / f32(U) >= thresh else 0,
- *                              U = F + cnt - I, applied inside the same fixed-order sums.  counts = cnt = wts = NULL:
- *                              exactly usc_criterion_losses
- *   usc_criterion_backward_ex  usc_criterion_backward that also takes wts: the dmasks column of a pair with weight 0
- *                              is exactly 0.  wts = NULL: exactly usc_criterion_backward */
-int usc_criterion_drop_counts(const float* const* masks, int32_t L, int32_t ld, int32_t S,
-                              int32_t Q, int32_t T, const uint32_t* bits, const int64_t* src,
-                              const int64_t* tid, int32_t* counts, usc_stream_t s);
-int usc_criterion_losses_ex(const float* cmask, const float* cdice, const float* logp,
-                            const int64_t* src, const int64_t* tid, const int64_t* labels,
-                            const float* class_w, int32_t L, int32_t Q, int32_t T, int32_t C,
-                            int32_t noobj, int32_t* tcls, float* part, const int32_t* counts,
-                            const int32_t* cnt, float thresh, float* wts, usc_stream_t s);
-int usc_criterion_backward_ex(const float* const* masks, float* const* dmasks, int32_t L,
-                              int32_t ld, int32_t S, int32_t Q, int32_t T, const uint32_t* bits,
-                              const int32_t* cnt, const int64_t* src, const int64_t* tid,
-                              const float* nmat, const float* ssum, const float* logp,
-                              const int32_t* tcls, const float* class_w, const float* gtable,
-                              const float* den_tot, int32_t C, int64_t ls_level, int64_t ls_q,
-                              float* dlogits, const float* wts, usc_stream_t s);
-/* The device criterion for 33 .. 128 targets per scene (1 <= T <= 128, T <= Q <= 128, L <= 16; opt-in through
- * SetCriterion(device_max_targets=...)).  Same arguments and results as the functions they are named after, with the
- * target bits W = ceil(T / 32) words wide and word-major: bits u32[W, S], word w = the bits of the targets
- * 32w .. 32w+31 in the one-word layout.  Replace, for such scenes, the torch-operator path of
- * SetCriterion.match_all_levels / _batched_losses (one device->host copy of the cost matrices and a scipy solve per
- * level and scene).
- *   usc_criterion_target_bits_wide  usc_criterion_target_bits writing W words per row; cnt i32[T] as there
- *   usc_criterion_costs_wide        usc_criterion_costs once per word, one word after the other on the stream: word w
- *                                   fills the columns 32w .. of the [L,Q,T] outputs (2 W launches; the workspace of
- *                                   usc_criterion_ws_bytes(L, S, T) is the 32-target one, reused per word).  The
- *                                   entries of a pair are the bits usc_criterion_costs gives for that pair
- *   usc_criterion_drop_counts_wide  usc_criterion_drop_counts; a pair's target bit is word tid >> 5, bit tid & 31
- *   usc_criterion_losses_wide       usc_criterion_losses_ex (counts = cnt = wts = NULL: no DropLoss) over <= 128 pairs
- *   usc_criterion_backward_wide     usc_criterion_backward_ex (wts = NULL: no DropLoss) */
-int usc_criterion_target_bits_wide(const uint8_t* tm, int32_t T, int32_t S, uint32_t* bits,
-                                   int32_t* cnt, usc_stream_t s);
-int usc_criterion_costs_wide(const float* const* masks, int32_t L, int32_t ld, int32_t S,
-                             int32_t Q, int32_t T, const uint32_t* bits, const int32_t* cnt,
-                             const float* logits, int64_t ls_level, int64_t ls_q, int32_t C,
-                             const int64_t* labels, float w_mask, float w_class, float w_dice,
-                             float* cost, float* cmask, float* cdice, float* nmat, float* ssum,
-                             float* logp, void* ws, int64_t ws_bytes, usc_stream_t s);
-int usc_criterion_drop_counts_wide(const float* const* masks, int32_t L, int32_t ld, int32_t S,
-                                   int32_t Q, int32_t T, const uint32_t* bits,
-                                   const int64_t* src, const int64_t* tid, int32_t* counts,
-                                   usc_stream_t s);
-int usc_criterion_losses_wide(const float* cmask, const float* cdice, const float* logp,
-                              const int64_t* src, const int64_t* tid, const int64_t* labels,
-                              const float* class_w, int32_t L, int32_t Q, int32_t T, int32_t C,
-                              int32_t noobj, int32_t* tcls, float* part, const int32_t* counts,
-                              const int32_t* cnt, float thresh, float* wts, usc_stream_t s);
-int usc_criterion_backward_wide(const float* const* masks, float* const* dmasks, int32_t L,
-                                int32_t ld, int32_t S, int32_t Q, int32_t T,
-                                const uint32_t* bits, const int32_t* cnt, const int64_t* src,
-                                const int64_t* tid, const float* nmat, const float* ssum,
-                                const float* logp, const int32_t* tcls, const float* class_w,
-                                const float* gtable, const float* den_tot, int32_t C,
-                                int64_t ls_level, int64_t ls_q, float* dlogits, const float* wts,
-                                usc_stream_t s);
+                           int32_t ld, int32_t S, int32_t Q, int32_t T, int32_t max_targets,
+                           const uint32_t* bits, const int32_t* cnt, const int64_t* src,
+                           const int64_t* tid, const float* nmat, const float* ssum,
+                           const float* logp, const int32_t* tcls, const float* class_w,
+                           const float* gtable, const float* den_tot, int32_t C, int64_t ls_level,
+                           int64_t ls_q, float* dlogits, const float* wts, usc_stream_t s);
 
 /* Linear layer on a handful of rows (the 100 decoder queries):
  *   y[M,N] = x[M,K] W[N,K]^T + b[N]   (b may be NULL);  N, K multiples of 32.

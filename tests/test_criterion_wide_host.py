@@ -44,13 +44,16 @@ def test_the_trainer_hands_the_config_value_through():
 
 
 def test_the_wide_entry_points_check_their_arguments_without_a_device():
-    """Argument validation happens before any HIP call: 1 <= T <= 128 for the wide functions, <= 32 for the others."""
+    """Argument validation happens before any HIP call: 1 <= T <= max_targets, and max_targets itself in 32 .. 128."""
     from unscene3d_amd import _lib
-    assert _lib.lib.usc_criterion_target_bits_wide(None, 129, 10, None, None, None) != 0
-    assert "usc_criterion_target_bits_wide" in _lib.last_error() and "1..128" in _lib.last_error()
-    assert _lib.lib.usc_criterion_target_bits_wide(None, 0, 10, None, None, None) != 0
-    assert _lib.lib.usc_criterion_target_bits(None, 33, 10, None, None, None) != 0
+    assert _lib.lib.usc_criterion_target_bits(None, 129, 128, 10, None, None, None) != 0
+    assert "usc_criterion_target_bits" in _lib.last_error() and "1..128" in _lib.last_error()
+    assert _lib.lib.usc_criterion_target_bits(None, 0, 128, 10, None, None, None) != 0
+    assert _lib.lib.usc_criterion_target_bits(None, 33, 32, 10, None, None, None) != 0
     assert "1..32" in _lib.last_error()
+    for m in (31, 129):
+        assert _lib.lib.usc_criterion_target_bits(None, 1, m, 10, None, None, None) != 0
+        assert "usc_criterion_target_bits" in _lib.last_error() and "32..128" in _lib.last_error()
     # the workspace is reused per 32-target word: above 32 targets it is the 32-target size
     ws = _lib.lib.usc_criterion_ws_bytes
     assert ws(13, 3000, 33) == ws(13, 3000, 128) == ws(13, 3000, 32) > ws(13, 3000, 16)

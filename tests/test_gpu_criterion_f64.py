@@ -100,11 +100,11 @@ def _same_bits(a, b):
 _POISON = {torch.float32: float("nan"), torch.int32: -1, torch.uint8: 0xFF}          # 0xFF bytes: NaN as float32
 
 
-def device_entry_points(case, dev, pad=0.0, thresh=None):
+def device_entry_points(case, dev, pad=0.0, thresh=None, max_targets=32):
     """criterion_device.scene_forward -> table -> scene_backward, the functions _FusedCriterion.forward / backward call,
     every intermediate kept (CPU tensors).  thresh: the DropLoss threshold (None: no DropLoss, no `counts` / `wts`).
     Outputs and the workspace start out as NaN / -1, so an element a kernel does not write shows.  pad: the value of the
-    table columns Q <= col < ld."""
+    table columns Q <= col < ld.  max_targets: handed to scene_forward / scene_backward."""
     from unscene3d_amd import criterion_device as D
     L, B, Q, NC = case["L"], case["B"], case["Q"], case["C"]
 
@@ -127,14 +127,15 @@ def device_entry_points(case, dev, pad=0.0, thresh=None):
         tm8 = case["tm"][b].to(dev).contiguous().view(torch.uint8)
         labels = case["labels"][b].to(dev).contiguous()
         states.append(D.scene_forward(tabs[b], tm8, labels, logits, b, weights, class_w, NC - 1, parts[b], thresh,
-                                      alloc=poisoned))
+                                      alloc=poisoned, max_targets=max_targets))
     table, den_tot = D.table(parts, alloc=poisoned)
     dlogits = poisoned((L, B, Q, NC), torch.float32)
     scenes = []
     for b, st in enumerate(states):
         assert (st.S, st.T, st.ld) == (case["S"][b], case["T"][b], case["ld"])
         sc = {k: v for k, v in st._asdict().items() if torch.is_tensor(v)}
-        sc["dmasks"] = D.scene_backward(st, tabs[b], b, class_w, g, den_tot, dlogits, alloc=poisoned)
+        sc["dmasks"] = D.scene_backward(st, tabs[b], b, class_w, g, den_tot, dlogits, alloc=poisoned,
+                                        max_targets=max_targets)
         scenes.append(sc)
     torch.cuda.synchronize()
     return dict(scenes=[{k: v.cpu() for k, v in sc.items()} for sc in scenes], parts=parts.cpu(), table=table.cpu(),

@@ -1,14 +1,15 @@
-"""The device set criterion with 33 .. 128 targets per scene (csrc/criterion.hip: the usc_criterion_*_wide entry points,
-driven by criterion_device.py when SetCriterion is given `device_max_targets` above 32).
+"""The device set criterion with 33 .. 128 targets per scene (csrc/criterion.hip: the usc_criterion_* functions with
+`max_targets` above 32, which criterion_device.py passes when SetCriterion is given `device_max_targets` above 32).
 
 The yardsticks are the ones of the <= 32-target path and are imported, not restated: criterion_cases.make_case builds the
 cases, oracle/criterion_ref.py (and tests/droploss_ref.py with DropLoss) is the float64 oracle, and every bounded
 quantity goes through test_gpu_criterion_f64.Judge:  err(dev, o64) <= 4 err(o32, o64) + floor  with that file's floors.
 The wide path adds no longer sum than the <= 128-term float64 pair sum of crit_loss, so the rule is used as it stands.
 
-Exact, with no tolerance: a pair's cost entries do not depend on the other targets (the wide outputs are the bits of the
-existing entry points on each 32-target word alone), device_max_targets changes nothing up to 32 targets, the assignment
-is scipy's on the device's own float32 cost matrix, unmatched / dropped / padding gradient columns are +0.
+Exact, with no tolerance: a pair's cost entries do not depend on the other targets (the outputs under max_targets = 128
+are the bits of a max_targets = 32 run on each 32-target word alone), device_max_targets changes nothing up to 32
+targets, the assignment is scipy's on the device's own float32 cost matrix, unmatched / dropped / padding gradient
+columns are +0.
 
 Shapes: word boundaries T in {33, 64, 65, 96, 97, 128} with a partial last word, the 32-row chunk S in {31, 33, 609},
 Q in {64, 100, 128} with ld = Q and 128, L in {1, 13}, up to three ragged scenes with a <= 32-target scene next to a wide
@@ -60,46 +61,6 @@ def _make(shape, drop=False):
     return case
 
 
-def wide_entry_points(case, dev, pad=0.0, thresh=None, max_targets=128):
-    """test_gpu_criterion_f64.device_entry_points with `max_targets` handed to criterion_device: scene_forward -> table
-    -> scene_backward on poisoned outputs (NaN / -1, so that an element no kernel writes shows), everything kept."""
-    from unscene3d_amd import criterion_device as D
-    L, B, Q, NC = case["L"], case["B"], case["Q"], case["C"]
-
-    def poisoned(shape, dtype):
-        return torch.full(shape, F._POISON[dtype], dtype=dtype, device=dev)
-    logits = torch.stack(case["logits"]).to(dev).contiguous()
-    class_w = torch.ones(NC, dtype=torch.float32)
-    class_w[-1] = case["eos_coef"]
-    class_w = class_w.to(dev)
-    g = CC.gtable(case).to(dev).reshape(-1).contiguous()
-    weights = tuple(CC.COST_WEIGHTS[k] for k in ("cost_mask", "cost_class", "cost_dice"))
-    parts = poisoned((B, L, 4), torch.float32)
-    tabs, states = [], []
-    for b in range(B):
-        tabs.append([])
-        for l in range(L):
-            t = case["masks"][l][b].clone()
-            t[:, Q:] = pad
-            tabs[b].append(t.to(dev).contiguous())
-        tm8 = case["tm"][b].to(dev).contiguous().view(torch.uint8)
-        labels = case["labels"][b].to(dev).contiguous()
-        states.append(D.scene_forward(tabs[b], tm8, labels, logits, b, weights, class_w, NC - 1, parts[b], thresh,
-                                      alloc=poisoned, max_targets=max_targets))
-    table, den_tot = D.table(parts, alloc=poisoned)
-    dlogits = poisoned((L, B, Q, NC), torch.float32)
-    scenes = []
-    for b, st in enumerate(states):
-        assert (st.S, st.T, st.ld) == (case["S"][b], case["T"][b], case["ld"])
-        sc = {k: v for k, v in st._asdict().items() if torch.is_tensor(v)}
-        sc["dmasks"] = D.scene_backward(st, tabs[b], b, class_w, g, den_tot, dlogits, alloc=poisoned,
-                                        max_targets=max_targets)
-        scenes.append(sc)
-    torch.cuda.synchronize()
-    return dict(scenes=[{k: v.cpu() for k, v in sc.items()} for sc in scenes], parts=parts.cpu(), table=table.cpu(),
-                den_tot=den_tot.cpu(), dlogits=dlogits.cpu())
-
-
 def _sub_case(case, lo, hi):
     """Scene 0 of a one-scene case with only its targets lo .. hi-1."""
     return dict(case, T=[hi - lo], tm=[case["tm"][0][lo:hi]], labels=[case["labels"][0][lo:hi]])
@@ -117,11 +78,11 @@ def _want_bits(tm):
 
 # ---- 1. a pair's entries do not depend on the other targets ---------------------------------------------------------
 @pytest.mark.parametrize("Q,T", [(64, 40), (128, 65)])
-def test_words_are_the_existing_entry_points_on_32_targets_each(device, Q, T):
-    """cost / cmask / cdice / nmat of the wide entry points, columns 32w .. 32w+31 = the EXISTING entry points on those
-    targets alone (the last word as a problem of T - 32w targets), bit for bit; ssum and logp are the existing ones."""
+def test_words_are_a_32_target_run_on_32_targets_each(device, Q, T):
+    """cost / cmask / cdice / nmat of a max_targets = 128 run, columns 32w .. 32w+31 = a max_targets = 32 run on those
+    targets alone (the last word as a problem of T - 32w targets), bit for bit; ssum and logp are that run's too."""
     case = _make(("random", 2, Q, 3, "Q", 0.1, [(33, T)], 1))
-    wide = wide_entry_points(case, device)["scenes"][0]
+    wide = F.device_entry_points(case, device, max_targets=128)["scenes"][0]
     assert wide["bits"].shape == ((T + 31) // 32, 33)
     assert np.array_equal(wide["bits"].numpy().view(np.uint32), _want_bits(case["tm"][0].numpy()))
     assert np.array_equal(wide["cnt"].numpy(), case["tm"][0].numpy().sum(1).astype(np.int32))
@@ -129,7 +90,7 @@ def test_words_are_the_existing_entry_points_on_32_targets_each(device, Q, T):
         hi = min(lo + 32, T)
         sub = _sub_case(case, lo, hi)
         assert hi - lo <= 32 and hi - lo <= Q
-        old = F.device_entry_points(sub, device)["scenes"][0]               # max_targets = 32: the existing functions
+        old = F.device_entry_points(sub, device, max_targets=32)["scenes"][0]
         for k in ("cost", "cmask", "cdice", "nmat"):
             assert wide[k].shape == (2, Q, T)
             assert F._bits(wide[k][:, :, lo:hi]) == F._bits(old[k]), (k, lo, hi)
@@ -178,7 +139,7 @@ def entry(request, device):
     shape, drop = WIDE_CASES[request.param]
     case = _make(shape, drop)
     assert max(case["T"]) > 32
-    run = wide_entry_points(case, device, thresh=DROP_THRESH if drop else None)
+    run = F.device_entry_points(case, device, thresh=DROP_THRESH if drop else None, max_targets=128)
     forced = [[(sc["src"][l], sc["tid"][l]) for sc in run["scenes"]] for l in range(case["L"])]
     return case, drop, run, _oracle(case, torch.float32, forced, drop), _oracle(case, torch.float64, forced, drop)
 
@@ -286,9 +247,9 @@ def test_unmatched_dropped_and_padding_columns_are_exact_zeros(device):
     case = _make(("random", 2, 100, 3, "128", 0.1, [(33, 97)], 1), True)
     Q, ld = case["Q"], case["ld"]
     assert Q < ld
-    a = wide_entry_points(case, device, pad=0.0, thresh=DROP_THRESH)
-    b = wide_entry_points(case, device, pad=float("nan"), thresh=DROP_THRESH)
-    c = wide_entry_points(case, device, pad=7.0, thresh=DROP_THRESH)        # foreground, were it read
+    a = F.device_entry_points(case, device, pad=0.0, thresh=DROP_THRESH, max_targets=128)
+    b = F.device_entry_points(case, device, pad=float("nan"), thresh=DROP_THRESH, max_targets=128)
+    c = F.device_entry_points(case, device, pad=7.0, thresh=DROP_THRESH, max_targets=128)     # foreground, were it read
     assert F._same_bits(a, b) and F._same_bits(a, c)
     sc = b["scenes"][0]
     kept = dropped = 0
@@ -303,7 +264,7 @@ def test_unmatched_dropped_and_padding_columns_are_exact_zeros(device):
     print(f"  [{case['name']}] {kept} pairs kept, {dropped} dropped")
     assert kept > 0 and dropped > 0, "the case is meant to have both kinds of pair"
     # without DropLoss: unmatched and padding columns
-    p = wide_entry_points(case, device, pad=float("nan"))["scenes"][0]
+    p = F.device_entry_points(case, device, pad=float("nan"), max_targets=128)["scenes"][0]
     for l in range(case["L"]):
         zero_cols = np.setdiff1d(np.arange(ld), p["src"][l].numpy())
         assert not np.ascontiguousarray(p["dmasks"][l].numpy()[:, zero_cols]).view(np.uint32).any(), l
@@ -329,28 +290,36 @@ def test_lsap_shapes_of_the_wide_criterion_equal_scipy(device, nr, nc):
 
 
 # ---- 6. bounds ------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("Q,T", [(64, 0), (128, 129), (40, 41)])
-def test_wide_entry_points_reject_sizes_outside_their_bounds(device, Q, T):
-    """T = 0, T = 129, T > Q: an error code and a message that names the bounds, before anything is launched."""
-    from unscene3d_amd._lib import last_error, lib
-    L, S, C = 2, 33, 3
+def _bound_calls(device, L, S, Q, T, C, max_targets):
+    """(name -> a call of that function, the zeroed buffers the calls point into: large enough for every size used
+    below, though nothing may launch)."""
+    from unscene3d_amd._lib import lib
     n = max(T, 1)
     z32 = torch.zeros(4 * 128 * 33 + L * 128 * 130, dtype=torch.float32, device=device)      # every float argument
     zi = torch.zeros(4 * 128 * 33, dtype=torch.int64, device=device)                          # every integer argument
     ws = torch.zeros(max(int(lib.usc_criterion_ws_bytes(L, S, min(n, 128))), 256), dtype=torch.uint8, device=device)
     ptrs = (ctypes.c_void_p * L)(*[z32.data_ptr()] * L)
-    f, i = z32.data_ptr(), zi.data_ptr()
-    calls = {
-        "usc_criterion_costs_wide": lambda: lib.usc_criterion_costs_wide(
-            ptrs, L, 128, S, Q, T, i, i, f, Q * C, C, C, i, 5.0, 2.0, 2.0, f, f, f, f, f, f, ws.data_ptr(), ws.numel(), None),
-        "usc_criterion_drop_counts_wide": lambda: lib.usc_criterion_drop_counts_wide(ptrs, L, 128, S, Q, T, i, i, i, i, None),
-        "usc_criterion_losses_wide": lambda: lib.usc_criterion_losses_wide(
-            f, f, f, i, i, i, f, L, Q, T, C, C - 1, i, f, None, None, 0.0, None, None),
-        "usc_criterion_backward_wide": lambda: lib.usc_criterion_backward_wide(
-            ptrs, ptrs, L, 128, S, Q, T, i, i, i, i, f, f, f, i, f, f, f, C, Q * C, C, f, None, None),
-    }
-    if T <= Q:                                                            # this one has no Q to compare with
-        calls["usc_criterion_target_bits_wide"] = lambda: lib.usc_criterion_target_bits_wide(i, T, S, i, i, None)
+    f, i, m = z32.data_ptr(), zi.data_ptr(), max_targets
+    return {
+        "usc_criterion_target_bits": lambda: lib.usc_criterion_target_bits(i, T, m, S, i, i, None),
+        "usc_criterion_costs": lambda: lib.usc_criterion_costs(
+            ptrs, L, 128, S, Q, T, m, i, i, f, Q * C, C, C, i, 5.0, 2.0, 2.0, f, f, f, f, f, f, ws.data_ptr(), ws.numel(), None),
+        "usc_criterion_drop_counts": lambda: lib.usc_criterion_drop_counts(ptrs, L, 128, S, Q, T, m, i, i, i, i, None),
+        "usc_criterion_losses": lambda: lib.usc_criterion_losses(
+            f, f, f, i, i, i, f, L, Q, T, m, C, C - 1, i, f, None, None, 0.0, None, None),
+        "usc_criterion_backward": lambda: lib.usc_criterion_backward(
+            ptrs, ptrs, L, 128, S, Q, T, m, i, i, i, i, f, f, f, i, f, f, f, C, Q * C, C, f, None, None),
+    }, (z32, zi, ws)
+
+
+@pytest.mark.parametrize("Q,T", [(64, 0), (128, 129), (40, 41)])
+def test_wide_entry_points_reject_sizes_outside_their_bounds(device, Q, T):
+    """max_targets = 128 and T = 0, T = 129, T > Q: an error code and a message that names the function and the bound,
+    before anything is launched."""
+    from unscene3d_amd._lib import last_error
+    calls, _buffers = _bound_calls(device, 2, 33, Q, T, 3, 128)
+    if T > Q:                                                             # this one has no Q to compare with
+        del calls["usc_criterion_target_bits"]
     for name, call in calls.items():
         assert call() != 0, name
         msg = last_error()
@@ -359,14 +328,40 @@ def test_wide_entry_points_reject_sizes_outside_their_bounds(device, Q, T):
 
 
 def test_the_existing_entry_points_keep_rejecting_more_than_32_targets(device):
+    """max_targets = 32 (the default training path) refuses a 33-target scene in the library and in the driver; a
+    max_targets outside 32 .. 128 is refused by all five functions.  33 targets, S = 33, Q = 64, L = 1: the smallest
+    shape that crosses the word boundary."""
+    from unscene3d_amd import criterion_device as D
     from unscene3d_amd._lib import last_error, lib
     z = torch.zeros(64 * 64, dtype=torch.int64, device=device)
-    assert lib.usc_criterion_target_bits(z.data_ptr(), 33, 33, z.data_ptr(), z.data_ptr(), None) != 0
+    assert lib.usc_criterion_target_bits(z.data_ptr(), 33, 32, 33, z.data_ptr(), z.data_ptr(), None) != 0
     assert "1..32" in last_error()
     ptrs = (ctypes.c_void_p * 1)(z.data_ptr())
-    assert lib.usc_criterion_drop_counts(ptrs, 1, 64, 33, 64, 33, z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(),
-                                         None) != 0
+    assert lib.usc_criterion_drop_counts(ptrs, 1, 64, 33, 64, 33, 32, z.data_ptr(), z.data_ptr(), z.data_ptr(),
+                                         z.data_ptr(), None) != 0
     assert "1..32" in last_error()
+    for m in (31, 129):
+        calls, _buffers = _bound_calls(device, 1, 33, 64, 33, 3, m)
+        for name, call in calls.items():
+            assert call() != 0, (name, m)
+            assert name in last_error(), (name, m, last_error())
+    torch.cuda.synchronize()
+    # the driver: ValueError before any allocation or launch
+    case = _make(("random", 1, 64, 3, "Q", 0.1, [(33, 33)], 0))
+    allocated = []
+
+    def alloc(shape, dtype):
+        allocated.append(shape)
+        return torch.empty(shape, dtype=dtype, device=device)
+    tabs = [case["masks"][0][0].to(device).contiguous()]
+    tm8 = case["tm"][0].to(device).contiguous().view(torch.uint8)
+    logits = torch.stack(case["logits"]).to(device).contiguous()
+    part = torch.full((1, 4), float("nan"), device=device)
+    with pytest.raises(ValueError, match="33 targets, the caller allows 32"):
+        D.scene_forward(tabs, tm8, case["labels"][0].to(device), logits, 0, (5.0, 2.0, 2.0),
+                        torch.ones(3, device=device), 2, part, alloc=alloc, max_targets=32)
+    torch.cuda.synchronize()
+    assert not allocated and bool(torch.isnan(part).all())
 
 
 def test_set_criterion_rejects_device_max_targets_above_128():

@@ -1,5 +1,5 @@
-"""DropLoss inside the device set criterion (csrc/criterion.hip: usc_criterion_drop_counts, usc_criterion_losses_ex,
-usc_criterion_backward_ex, driven by criterion_device.py under models/criterion.py::_FusedCriterion when `use_droploss`
+"""DropLoss inside the device set criterion (csrc/criterion.hip: usc_criterion_drop_counts and the DropLoss arguments of
+usc_criterion_losses and usc_criterion_backward, driven by criterion_device.py under models/criterion.py::_FusedCriterion when `use_droploss`
 is set) against the weighted float64 restatement of tests/droploss_ref.py, which tests/test_droploss_host.py pins on the
 reference's golden.
 

@@ -223,7 +223,7 @@ using namespace usc;
 extern "C" {
 
 const char* usc_last_error(void) { return g_err; }
-int usc_abi_version(void) { return 2; }   // 2: usc_attn_bwd takes mask_bits_in_ws (round 3)
+int usc_abi_version(void) { return 3; }   // 3: five usc_criterion_* functions that take max_targets (no _ex / _wide)
 
 int usc_device_count(void) {
   int n = 0;

@@ -399,15 +399,14 @@ int usc_lsap_batch(const float* cost, int32_t n_prob, int32_t nr, int32_t nc, in
 //                  with integer atomics (exact, order-free).  crit_loss<true> turns them into the 0 / 1 pair weights
 //                  w = [U > 0 and f32(I) / f32(U) >= thresh], U = F + |target| - I, and leaves dropped pairs out of the
 //                  same fixed-order sums; crit_bwd_masks<true> writes their columns as exact zeros
-// Every sum has a fixed order; the target masks travel as one bit per (row, target) (T <= 32).
-//
-// 33 .. 128 targets (the usc_criterion_*_wide entry points): the bits become W = ceil(T / 32) words per row, stored
-// word-major (bits u32[W, S]: word w is a contiguous u32[S] in exactly the layout above, for the targets 32w .. 32w+31).
+// Every sum has a fixed order; the target masks travel as one bit per (row, target): W = ceil(T / 32) words per row,
+// stored word-major (bits u32[W, S]: word w is a contiguous u32[S] for the targets 32w .. 32w+31; up to 32 targets that
+// is a plain u32[S]).
 // The cost pair crit_partial<TMAX> + crit_cost<TMAX> runs once per word, one word after the other on the stream and over
 // the same workspace: word w reads bits + w S, labels + 32w and cnt + 32w, handles min(32, T - 32w) targets and writes
-// the columns 32w .. of the [L, Q, T] outputs at row stride T.  The per-pair arithmetic is the one of the <= 32 path, so
-// a pair's cost does not depend on how many other targets the scene has; ssum / logp do not depend on the word and are
-// rewritten with the same bits by every word.  No TMAX above 32: 3 TMAX accumulators per lane are 96 registers already.
+// the columns 32w .. of the [L, Q, T] outputs at row stride T.  A pair's cost therefore does not depend on how many
+// other targets the scene has; ssum / logp do not depend on the word and are rewritten with the same bits by every
+// word.  No TMAX above 32: 3 TMAX accumulators per lane are 96 registers already.
 // Everything after the costs looks a target's bit up as word tid >> 5, bit tid & 31.
 namespace usc {
 namespace {
@@ -734,43 +733,39 @@ int64_t usc_criterion_ws_bytes(int32_t L, int32_t S, int32_t T) {
   return usc::align_up((int64_t)L * nchunk * (3 * usc::tmax_of(T) + 2) * usc::kCritCols * 4, 256);
 }
 
-// Every entry point exists twice: the <= 32-target one (one word of target bits per row) and its _wide twin for up to
-// 128 targets (W = ceil(T / 32) words, word-major).  Both run the same kernels; `tcap` is the entry point's bound.
-static int crit_target_bits(const uint8_t* tm, int32_t T, int32_t S, uint32_t* bits, int32_t* cnt, usc_stream_t s,
-                            int tcap, const char* name) {
-  USC_REQUIRE(T >= 1 && T <= tcap && S >= 1, "%s: needs 1..%d targets", name, tcap);
-  USC_REQUIRE(tm && bits && cnt, "%s: null argument", name);
+// max_targets (32 .. 128) is the caller's bound on T: a scene above it is refused here, before any launch.  Up to 32
+// targets the bits are one word per row; above, W = ceil(T / 32) words, word-major, through the same kernels.
+
+int usc_criterion_target_bits(const uint8_t* tm, int32_t T, int32_t max_targets, int32_t S, uint32_t* bits, int32_t* cnt,
+                              usc_stream_t s) {
+  USC_REQUIRE(max_targets >= 32 && max_targets <= 128, "usc_criterion_target_bits: max_targets %d is outside 32..128",
+              (int)max_targets);
+  USC_REQUIRE(T >= 1 && T <= max_targets && S >= 1, "usc_criterion_target_bits: needs 1..%d targets", (int)max_targets);
+  USC_REQUIRE(tm && bits && cnt, "usc_criterion_target_bits: null argument");
   hipStream_t st = usc::as_stream(s);
   (void)hipMemsetAsync(cnt, 0, (size_t)T * 4, st);
   hipLaunchKernelGGL(usc::crit_target_bits_kernel, dim3((unsigned)usc::ceil_div(S, 256), (unsigned)usc::ceil_div(T, 32)),
                      dim3(256), 0, st, tm, (int)T, (int)S, bits, cnt);
-  USC_CHECK_LAUNCH(name);
+  USC_CHECK_LAUNCH("usc_criterion_target_bits");
   return USC_OK;
 }
 
-int usc_criterion_target_bits(const uint8_t* tm, int32_t T, int32_t S, uint32_t* bits, int32_t* cnt, usc_stream_t s) {
-  return crit_target_bits(tm, T, S, bits, cnt, s, 32, "usc_criterion_target_bits");
-}
-
-int usc_criterion_target_bits_wide(const uint8_t* tm, int32_t T, int32_t S, uint32_t* bits, int32_t* cnt,
-                                   usc_stream_t s) {
-  return crit_target_bits(tm, T, S, bits, cnt, s, 128, "usc_criterion_target_bits_wide");
-}
-
-static int crit_costs(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
-                      const uint32_t* bits, const int32_t* cnt, const float* logits, int64_t ls_level, int64_t ls_q,
-                      int32_t C, const int64_t* labels, float w_mask, float w_class, float w_dice, float* cost,
-                      float* cmask, float* cdice, float* nmat, float* ssum, float* logp, void* ws, int64_t ws_bytes,
-                      usc_stream_t s, int tcap, const char* name) {
+int usc_criterion_costs(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
+                        int32_t max_targets, const uint32_t* bits, const int32_t* cnt, const float* logits,
+                        int64_t ls_level, int64_t ls_q, int32_t C, const int64_t* labels, float w_mask, float w_class,
+                        float w_dice, float* cost, float* cmask, float* cdice, float* nmat, float* ssum, float* logp,
+                        void* ws, int64_t ws_bytes, usc_stream_t s) {
   using namespace usc;
-  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && T >= 1 && T <= tcap &&
-                  (tcap == 32 || T <= Q) && S >= 1 && C >= 1,
-              "%s: needs <= 16 levels, <= 128 queries, 1..%d targets%s", name, tcap,
-              tcap == 32 ? "" : ", not more targets than queries");
+  USC_REQUIRE(max_targets >= 32 && max_targets <= 128, "usc_criterion_costs: max_targets %d is outside 32..128",
+              (int)max_targets);
+  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && T >= 1 && T <= max_targets &&
+                  (T <= 32 || T <= Q) && S >= 1 && C >= 1,
+              "usc_criterion_costs: needs <= 16 levels, <= 128 queries, 1..%d targets, above 32 not more than queries",
+              (int)max_targets);
   USC_REQUIRE(masks && bits && cnt && logits && labels && cost && cmask && cdice && nmat && ssum && logp && ws &&
-                  ws_bytes >= usc_criterion_ws_bytes(L, S, T), "%s: bad argument", name);
+                  ws_bytes >= usc_criterion_ws_bytes(L, S, T), "usc_criterion_costs: bad argument");
   CritLevels lv{};
-  for (int l = 0; l < L; ++l) { USC_REQUIRE(masks[l], "%s: null level", name); lv.x[l] = masks[l]; }
+  for (int l = 0; l < L; ++l) { USC_REQUIRE(masks[l], "usc_criterion_costs: null level"); lv.x[l] = masks[l]; }
   const int nchunk = (int)ceil_div(S, 32);
   hipStream_t st = as_stream(s);
   // one 32-target word after the other, over the same workspace (stream order keeps word w + 1 behind word w)
@@ -785,69 +780,45 @@ static int crit_costs(const float* const* masks, int32_t L, int32_t ld, int32_t 
       default: launch_cost<32>(lv, L, ld, S, Q, wbits, nchunk, (float*)ws, ca, st); break;
     }
   }
-  USC_CHECK_LAUNCH(name);
-  return USC_OK;
-}
-
-int usc_criterion_costs(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
-                        const uint32_t* bits, const int32_t* cnt, const float* logits, int64_t ls_level, int64_t ls_q,
-                        int32_t C, const int64_t* labels, float w_mask, float w_class, float w_dice, float* cost,
-                        float* cmask, float* cdice, float* nmat, float* ssum, float* logp, void* ws, int64_t ws_bytes,
-                        usc_stream_t s) {
-  return crit_costs(masks, L, ld, S, Q, T, bits, cnt, logits, ls_level, ls_q, C, labels, w_mask, w_class, w_dice, cost,
-                    cmask, cdice, nmat, ssum, logp, ws, ws_bytes, s, 32, "usc_criterion_costs");
-}
-
-int usc_criterion_costs_wide(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
-                             const uint32_t* bits, const int32_t* cnt, const float* logits, int64_t ls_level,
-                             int64_t ls_q, int32_t C, const int64_t* labels, float w_mask, float w_class, float w_dice,
-                             float* cost, float* cmask, float* cdice, float* nmat, float* ssum, float* logp, void* ws,
-                             int64_t ws_bytes, usc_stream_t s) {
-  return crit_costs(masks, L, ld, S, Q, T, bits, cnt, logits, ls_level, ls_q, C, labels, w_mask, w_class, w_dice, cost,
-                    cmask, cdice, nmat, ssum, logp, ws, ws_bytes, s, 128, "usc_criterion_costs_wide");
-}
-
-static int crit_drop_counts(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
-                            const uint32_t* bits, const int64_t* src, const int64_t* tid, int32_t* counts,
-                            usc_stream_t s, int tcap, const char* name) {
-  using namespace usc;
-  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && T >= 1 && T <= tcap && T <= Q && S >= 1,
-              "%s: needs <= 16 levels, <= 128 queries, 1..%d targets", name, tcap);
-  USC_REQUIRE(masks && bits && src && tid && counts, "%s: null argument", name);
-  CritLevels lv{};
-  for (int l = 0; l < L; ++l) { USC_REQUIRE(masks[l], "%s: null level", name); lv.x[l] = masks[l]; }
-  hipStream_t st = as_stream(s);
-  (void)hipMemsetAsync(counts, 0, (size_t)2 * L * T * 4, st);
-  hipLaunchKernelGGL(crit_drop_counts_kernel, dim3((unsigned)ceil_div(S, 32), L), dim3(128), 0, st, lv, (int)ld, (int)S,
-                     (int)Q, (int)T, (int)L, bits, src, tid, counts);
-  USC_CHECK_LAUNCH(name);
+  USC_CHECK_LAUNCH("usc_criterion_costs");
   return USC_OK;
 }
 
 int usc_criterion_drop_counts(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
-                              const uint32_t* bits, const int64_t* src, const int64_t* tid, int32_t* counts,
-                              usc_stream_t s) {
-  return crit_drop_counts(masks, L, ld, S, Q, T, bits, src, tid, counts, s, 32, "usc_criterion_drop_counts");
-}
-
-int usc_criterion_drop_counts_wide(const float* const* masks, int32_t L, int32_t ld, int32_t S, int32_t Q, int32_t T,
-                                   const uint32_t* bits, const int64_t* src, const int64_t* tid, int32_t* counts,
-                                   usc_stream_t s) {
-  return crit_drop_counts(masks, L, ld, S, Q, T, bits, src, tid, counts, s, 128, "usc_criterion_drop_counts_wide");
-}
-
-static int crit_losses(const float* cmask, const float* cdice, const float* logp, const int64_t* src,
-                       const int64_t* tid, const int64_t* labels, const float* class_w, int32_t L, int32_t Q,
-                       int32_t T, int32_t C, int32_t noobj, int32_t* tcls, float* part, const int32_t* counts,
-                       const int32_t* cnt, float thresh, float* wts, usc_stream_t s, int tcap, const char* name) {
+                              int32_t max_targets, const uint32_t* bits, const int64_t* src, const int64_t* tid,
+                              int32_t* counts, usc_stream_t s) {
   using namespace usc;
-  USC_REQUIRE(L >= 1 && (tcap == 32 || L <= kCritMaxLevels) && Q >= 1 && Q <= kCritCols && T >= 1 && T <= tcap &&
-                  T <= Q && C >= 1 && noobj >= 0 && noobj < C,
-              "%s: bad sizes (needs%s <= 128 queries, 1..%d targets, not more than queries)", name,
-              tcap == 32 ? "" : " <= 16 levels,", tcap);
-  USC_REQUIRE(cmask && cdice && logp && src && tid && labels && class_w && tcls && part, "%s: null argument", name);
+  USC_REQUIRE(max_targets >= 32 && max_targets <= 128, "usc_criterion_drop_counts: max_targets %d is outside 32..128",
+              (int)max_targets);
+  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && T >= 1 && T <= max_targets &&
+                  T <= Q && S >= 1,
+              "usc_criterion_drop_counts: needs <= 16 levels, <= 128 queries, 1..%d targets", (int)max_targets);
+  USC_REQUIRE(masks && bits && src && tid && counts, "usc_criterion_drop_counts: null argument");
+  CritLevels lv{};
+  for (int l = 0; l < L; ++l) { USC_REQUIRE(masks[l], "usc_criterion_drop_counts: null level"); lv.x[l] = masks[l]; }
+  hipStream_t st = as_stream(s);
+  (void)hipMemsetAsync(counts, 0, (size_t)2 * L * T * 4, st);
+  hipLaunchKernelGGL(crit_drop_counts_kernel, dim3((unsigned)ceil_div(S, 32), L), dim3(128), 0, st, lv, (int)ld, (int)S,
+                     (int)Q, (int)T, (int)L, bits, src, tid, counts);
+  USC_CHECK_LAUNCH("usc_criterion_drop_counts");
+  return USC_OK;
+}
+
+int usc_criterion_losses(const float* cmask, const float* cdice, const float* logp, const int64_t* src, const int64_t* tid,
+                         const int64_t* labels, const float* class_w, int32_t L, int32_t Q, int32_t T,
+                         int32_t max_targets, int32_t C, int32_t noobj, int32_t* tcls, float* part,
+                         const int32_t* counts, const int32_t* cnt, float thresh, float* wts, usc_stream_t s) {
+  using namespace usc;
+  USC_REQUIRE(max_targets >= 32 && max_targets <= 128, "usc_criterion_losses: max_targets %d is outside 32..128",
+              (int)max_targets);
+  USC_REQUIRE(L >= 1 && Q >= 1 && Q <= kCritCols && T >= 1 && T <= max_targets && T <= Q && C >= 1 && noobj >= 0 &&
+                  noobj < C,
+              "usc_criterion_losses: bad sizes (needs <= 128 queries, 1..%d targets, not more than queries)",
+              (int)max_targets);
+  USC_REQUIRE(cmask && cdice && logp && src && tid && labels && class_w && tcls && part,
+              "usc_criterion_losses: null argument");
   USC_REQUIRE((counts && cnt && wts) || (!counts && !cnt && !wts),
-              "%s: counts, cnt and wts go together (all three, or none for no DropLoss)", name);
+              "usc_criterion_losses: counts, cnt and wts go together (all three, or none for no DropLoss)");
   if (wts)
     hipLaunchKernelGGL(crit_loss_kernel<true>, dim3(L), dim3(128), 0, as_stream(s), cmask, cdice, logp, src, tid, labels,
                        class_w, (int)Q, (int)T, (int)C, (int)noobj, tcls, part, counts, cnt, thresh, wts);
@@ -855,31 +826,8 @@ static int crit_losses(const float* cmask, const float* cdice, const float* logp
     hipLaunchKernelGGL(crit_loss_kernel<false>, dim3(L), dim3(128), 0, as_stream(s), cmask, cdice, logp, src, tid, labels,
                        class_w, (int)Q, (int)T, (int)C, (int)noobj, tcls, part, (const int32_t*)nullptr,
                        (const int32_t*)nullptr, 0.f, (float*)nullptr);
-  USC_CHECK_LAUNCH(name);
+  USC_CHECK_LAUNCH("usc_criterion_losses");
   return USC_OK;
-}
-
-int usc_criterion_losses_ex(const float* cmask, const float* cdice, const float* logp, const int64_t* src,
-                            const int64_t* tid, const int64_t* labels, const float* class_w, int32_t L, int32_t Q,
-                            int32_t T, int32_t C, int32_t noobj, int32_t* tcls, float* part, const int32_t* counts,
-                            const int32_t* cnt, float thresh, float* wts, usc_stream_t s) {
-  return crit_losses(cmask, cdice, logp, src, tid, labels, class_w, L, Q, T, C, noobj, tcls, part, counts, cnt, thresh,
-                     wts, s, 32, "usc_criterion_losses");
-}
-
-int usc_criterion_losses(const float* cmask, const float* cdice, const float* logp, const int64_t* src, const int64_t* tid,
-                         const int64_t* labels, const float* class_w, int32_t L, int32_t Q, int32_t T, int32_t C,
-                         int32_t noobj, int32_t* tcls, float* part, usc_stream_t s) {
-  return usc_criterion_losses_ex(cmask, cdice, logp, src, tid, labels, class_w, L, Q, T, C, noobj, tcls, part, nullptr,
-                                 nullptr, 0.f, nullptr, s);
-}
-
-int usc_criterion_losses_wide(const float* cmask, const float* cdice, const float* logp, const int64_t* src,
-                              const int64_t* tid, const int64_t* labels, const float* class_w, int32_t L, int32_t Q,
-                              int32_t T, int32_t C, int32_t noobj, int32_t* tcls, float* part, const int32_t* counts,
-                              const int32_t* cnt, float thresh, float* wts, usc_stream_t s) {
-  return crit_losses(cmask, cdice, logp, src, tid, labels, class_w, L, Q, T, C, noobj, tcls, part, counts, cnt, thresh,
-                     wts, s, 128, "usc_criterion_losses_wide");
 }
 
 int usc_criterion_table(const float* parts, int32_t B, int32_t L, float* table, float* den_tot, usc_stream_t s) {
@@ -891,21 +839,23 @@ int usc_criterion_table(const float* parts, int32_t B, int32_t L, float* table, 
   return USC_OK;
 }
 
-static int crit_backward(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S, int32_t Q,
-                         int32_t T, const uint32_t* bits, const int32_t* cnt, const int64_t* src, const int64_t* tid,
-                         const float* nmat, const float* ssum, const float* logp, const int32_t* tcls,
-                         const float* class_w, const float* gtable, const float* den_tot, int32_t C, int64_t ls_level,
-                         int64_t ls_q, float* dlogits, const float* wts, usc_stream_t s, int tcap, const char* name) {
+int usc_criterion_backward(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S, int32_t Q,
+                           int32_t T, int32_t max_targets, const uint32_t* bits, const int32_t* cnt, const int64_t* src,
+                           const int64_t* tid, const float* nmat, const float* ssum, const float* logp,
+                           const int32_t* tcls, const float* class_w, const float* gtable, const float* den_tot,
+                           int32_t C, int64_t ls_level, int64_t ls_q, float* dlogits, const float* wts, usc_stream_t s) {
   using namespace usc;
+  USC_REQUIRE(max_targets >= 32 && max_targets <= 128, "usc_criterion_backward: max_targets %d is outside 32..128",
+              (int)max_targets);
   USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && ld <= kCritCols && T >= 1 &&
-                  T <= tcap && (tcap == 32 || T <= Q) && S >= 1 && C >= 1,
-              "%s: bad sizes (needs <= 16 levels, <= 128 queries and columns, 1..%d targets%s)", name, tcap,
-              tcap == 32 ? "" : ", not more than queries");
+                  T <= max_targets && (T <= 32 || T <= Q) && S >= 1 && C >= 1,
+              "usc_criterion_backward: bad sizes (needs <= 16 levels, <= 128 queries and columns, 1..%d targets, above 32 "
+              "not more than queries)", (int)max_targets);
   USC_REQUIRE(masks && dmasks && bits && cnt && src && tid && nmat && ssum && logp && tcls && class_w && gtable &&
-                  den_tot && dlogits, "%s: null argument", name);
+                  den_tot && dlogits, "usc_criterion_backward: null argument");
   CritBwdArgs a{};
   for (int l = 0; l < L; ++l) {
-    USC_REQUIRE(masks[l] && dmasks[l], "%s: null level", name);
+    USC_REQUIRE(masks[l] && dmasks[l], "usc_criterion_backward: null level");
     a.lv.x[l] = masks[l];
     a.lv.dx[l] = dmasks[l];
   }
@@ -916,36 +866,8 @@ static int crit_backward(const float* const* masks, float* const* dmasks, int32_
   else hipLaunchKernelGGL(crit_bwd_masks_kernel<false>, dim3(a.nchunk, L), dim3(128), 0, st, a);
   hipLaunchKernelGGL(crit_bwd_logits_kernel, dim3(L), dim3(128), 0, st, logp, tcls, class_w, gtable, den_tot, (int)Q, (int)C,
                      ls_level, ls_q, dlogits);
-  USC_CHECK_LAUNCH(name);
+  USC_CHECK_LAUNCH("usc_criterion_backward");
   return USC_OK;
-}
-
-int usc_criterion_backward_ex(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S, int32_t Q,
-                              int32_t T, const uint32_t* bits, const int32_t* cnt, const int64_t* src, const int64_t* tid,
-                              const float* nmat, const float* ssum, const float* logp, const int32_t* tcls,
-                              const float* class_w, const float* gtable, const float* den_tot, int32_t C, int64_t ls_level,
-                              int64_t ls_q, float* dlogits, const float* wts, usc_stream_t s) {
-  return crit_backward(masks, dmasks, L, ld, S, Q, T, bits, cnt, src, tid, nmat, ssum, logp, tcls, class_w, gtable,
-                       den_tot, C, ls_level, ls_q, dlogits, wts, s, 32, "usc_criterion_backward");
-}
-
-int usc_criterion_backward(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S, int32_t Q,
-                           int32_t T, const uint32_t* bits, const int32_t* cnt, const int64_t* src, const int64_t* tid,
-                           const float* nmat, const float* ssum, const float* logp, const int32_t* tcls,
-                           const float* class_w, const float* gtable, const float* den_tot, int32_t C, int64_t ls_level,
-                           int64_t ls_q, float* dlogits, usc_stream_t s) {
-  return usc_criterion_backward_ex(masks, dmasks, L, ld, S, Q, T, bits, cnt, src, tid, nmat, ssum, logp, tcls, class_w,
-                                   gtable, den_tot, C, ls_level, ls_q, dlogits, nullptr, s);
-}
-
-int usc_criterion_backward_wide(const float* const* masks, float* const* dmasks, int32_t L, int32_t ld, int32_t S,
-                                int32_t Q, int32_t T, const uint32_t* bits, const int32_t* cnt, const int64_t* src,
-                                const int64_t* tid, const float* nmat, const float* ssum, const float* logp,
-                                const int32_t* tcls, const float* class_w, const float* gtable, const float* den_tot,
-                                int32_t C, int64_t ls_level, int64_t ls_q, float* dlogits, const float* wts,
-                                usc_stream_t s) {
-  return crit_backward(masks, dmasks, L, ld, S, Q, T, bits, cnt, src, tid, nmat, ssum, logp, tcls, class_w, gtable,
-                       den_tot, C, ls_level, ls_q, dlogits, wts, s, 128, "usc_criterion_backward_wide");
 }
 
 }  // extern "C"

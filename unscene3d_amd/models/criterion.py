@@ -10,8 +10,8 @@ reference line by line.  `SetCriterion.forward` takes one of three paths:
   inputs: USC3D_FUSED_CRITERION is not 0, labels + masks losses on all points without the noise-robust loss
   (`_plain_losses`), float32 HIP predictions with 1-16 levels and at most 128 queries, and per scene 1-32 targets whose
   masks and labels are on the device.  `SetCriterion(device_max_targets=N)`, 32 <= N <= 128 (config:
-  `loss.device_max_targets`), raises the 32 to min(N, queries): such scenes run the wide entry points of
-  criterion_device.py (one pass of the cost kernels per 32 targets).
+  `loss.device_max_targets`), raises the 32 to min(N, queries): such scenes take one pass of the cost
+  kernels per 32 targets (criterion_device.py).
 * batched operators: `match_all_levels` builds all levels' cost matrices with torch operators and copies them to the host
   in ONE transfer (the reference syncs 13*B times), scipy solves them, `_batched_losses` computes all levels at once.
   Runs for `_plain_losses` inputs the device path does not take (CPU tensors, more than `device_max_targets` targets,
@@ -117,8 +117,8 @@ class SetCriterion(nn.Module):
                  importance_sample_ratio, class_weights, directions="xyz", use_droploss=False,
                  droploss_iou_thresh=0.1, device_max_targets=32):
         super().__init__()
-        # the most targets per scene the device criterion takes (32: one word of target bits per row; up to 128: the
-        # wide entry points, opt-in).  Scenes above it, or above the number of queries, take the operator path
+        # the most targets per scene the device criterion takes (32: one word of target bits per row; up to 128, opt-in:
+        # up to four).  Scenes above it, or above the number of queries, take the operator path
         if isinstance(device_max_targets, bool) or not isinstance(device_max_targets, int) \
                 or not 32 <= device_max_targets <= 128:
             raise ValueError(f"SetCriterion: device_max_targets must be an integer in 32 .. 128, not {device_max_targets!r}")
