@@ -639,7 +639,7 @@ int usc_scatter_rows_unique_add(const float* src, int32_t c, const int64_t* idx,
 /* The decoder's key sampling of one pass (reference models/mask3d.py:306-346: three row gathers by the sampled
  * indices, `attn[attn.sum(1) == K] = False`, `attn |= padding`), two launches:
  *   out_feats[b,k,:] = feats[idx[b*K+k],:]   out_pos likewise (pos may be NULL)   f32, c and p multiples of 4
- *   out_mask[b,k,:]  = mask[idx[b*K+k],:] (bool bytes [n,q], q <= 128), then
+ *   out_mask[b,k,:]  = mask[idx[b*K+k],:] (bool bytes [n,q], q <= 256), then
  *     - a query column that is masked in ALL K gathered rows of its scene is cleared in the scene's real rows,
  *     - rows k >= n_valid[b] (padding; their idx repeats a real row) are fully masked.
  * n_valid: HOST array i32[n_scenes] (n_scenes <= 16).  ws: usc_sample_keys_ws_bytes().
@@ -685,13 +685,21 @@ int usc_segment_max_nonzero(const float* feats, int32_t d,
                             usc_stream_t s);
 
 /* Masked cross attention of the mask decoder, all heads at once:
- *   o = softmax(q k^T / sqrt(16) + mask) v   per (batch, head), head dim 16, L <= 128 queries,
+ *   o = softmax(q k^T / sqrt(16) + mask) v   per (batch, head), head dim 16, L <= usc_attn_max_queries() = 256,
  * q, o f32[L,B,E], k, v f32[S,B,E] (sequence-first, E = 16*H), mask u8[B,S,L] (non-zero =
  * masked, shared by the heads).  No [heads, L, S] tensor is materialised: the forward is split
- * over keys (partial (o, max, sum) per split + a combine pass) and saves lse f32[B*H,128]; the
- * backward recomputes the probabilities and reduces dq partials in a fixed order.
+ * over keys (partial (o, max, sum) per split + a combine pass) and saves lse f32[B*H, usc_attn_lse_stride(L)]; the
+ * backward recomputes the probabilities and reduces dq partials in a fixed order (no float atomics: two calls on
+ * the same inputs give the same bits).
+ * Queries come in groups of 128: L <= 128 runs the one-group kernels (4 mask words per key, lse stride 128);
+ * 129 <= L <= 256 the two-group instantiations (8 mask words per key, lse stride 256, a query-group grid dimension
+ * in the forward, all 8 query tiles walked per key chunk in the backward).  usc_attn_ws_bytes depends on L only
+ * through the group count.
  * Replaces nn.MultiheadAttention's attention core in CrossAttentionLayer
  * (models/mask3d.py:547-605; memory_mask built at :341-348). */
+int32_t usc_attn_max_queries(void);
+/* row stride of lse for L queries (cross and self attention): 128 for L <= 128, 256 above */
+int32_t usc_attn_lse_stride(int32_t L);
 int64_t usc_attn_ws_bytes(int32_t L, int32_t S, int32_t B, int32_t H);
 int usc_attn_fwd(const float* q, const float* k, const float* v,
                  const uint8_t* mask, int32_t L, int32_t S, int32_t B, int32_t H,
@@ -704,10 +712,11 @@ int usc_attn_bwd(const float* q, const float* k, const float* v,
                  int32_t mask_bits_in_ws /* ws = the forward call's workspace, packed mask still at its start */,
                  void* ws, int64_t ws_bytes, usc_stream_t s);
 
-/* Self attention of the decoder queries (S = L <= 128 keys, no mask, head dim 16): q, k, v, o, dO, dq, dk, dv
- * f32[L,B,E] sequence-first, lse f32[B*H,128].  ONE launch each way (forward: one workgroup per (batch, head);
- * backward: per (batch, head) one workgroup per query tile for dq and one per key chunk for dk / dv); no partial
- * sum leaves a workgroup and every sum has a fixed order (bit-reproducible under any load, no atomics).
+/* Self attention of the decoder queries (S = L <= 256 keys, no mask, head dim 16): q, k, v, o, dO, dq, dk, dv
+ * f32[L,B,E] sequence-first, lse f32[B*H, usc_attn_lse_stride(L)].  ONE launch each way (forward: one workgroup per
+ * (batch, head), two above 128 queries; backward: per (batch, head) one workgroup per query tile for dq and one per
+ * key chunk for dk / dv); no partial sum leaves a workgroup and every sum has a fixed order (bit-reproducible under
+ * any load, no atomics).
  * Replaces nn.MultiheadAttention's attention core in SelfAttentionLayer (models/mask3d.py:491-545). */
 int usc_self_attn_fwd(const float* q, const float* k, const float* v, int32_t L,
                       int32_t B, int32_t H, int32_t E, float* o, float* lse,

@@ -1,5 +1,6 @@
-"""Developer aid: fused masked cross attention vs the two-GEMM + softmax path (fwd+bwd device time)."""
-import os, sys
+"""Developer aid: fused masked cross attention vs the two-GEMM + softmax path (fwd+bwd device time).
+--queries N: the query count (default 100; 129..256 run the two-group kernels)."""
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from unscene3d_amd import ops
@@ -12,9 +13,14 @@ def t(fn, n=30):
     for _ in range(n): fn()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n * 1e3
-H, hd, L, B = 8, 16, 100, 1
+ap = argparse.ArgumentParser()
+ap.add_argument("--queries", type=int, default=100)
+ap.add_argument("--keys", type=int, nargs="*", default=[200, 800, 3200, 12800])
+args = ap.parse_args()
+H, hd, L, B = 8, 16, args.queries, 1
 E = H * hd
-for S in (200, 800, 3200, 12800):
+print(f"{L} queries")
+for S in args.keys:
     q = torch.randn(L, B, E, device=dev, requires_grad=True); k = torch.randn(S, B, E, device=dev, requires_grad=True)
     v = torch.randn(S, B, E, device=dev, requires_grad=True); do = torch.randn(L, B, E, device=dev)
     mask = torch.rand(B, S, L, device=dev) > 0.5; mask[:, 0] = False

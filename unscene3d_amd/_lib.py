@@ -171,6 +171,8 @@ SIGNATURES = {
     "usc_adamw_step": (C.c_int, [_p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _p]),
     "usc_adamw_step_scaled": (C.c_int, [_p, _p, _p, _p, _i64, _f32, _i32, _f32, _f32, _f32, _f32, _f32, _i64, _p]),
     "usc_elastic_displace": (C.c_int, [_p, _i32, _i64, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _f64, _p, _p]),
+    "usc_attn_max_queries": (_i32, []),
+    "usc_attn_lse_stride": (_i32, [_i32]),
     "usc_attn_ws_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "usc_attn_fwd": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _p]),
     "usc_attn_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _i64, _p]),

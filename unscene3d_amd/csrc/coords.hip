@@ -223,7 +223,7 @@ using namespace usc;
 extern "C" {
 
 const char* usc_last_error(void) { return g_err; }
-int usc_abi_version(void) { return 3; }   // 3: five usc_criterion_* functions that take max_targets (no _ex / _wide)
+int usc_abi_version(void) { return 4; }   // 4: usc_attn_max_queries / usc_attn_lse_stride; attention and key sampling take <= 256 queries
 
 int usc_device_count(void) {
   int n = 0;

@@ -336,8 +336,11 @@ static int launch_colstats_partials(const StatArgs& a, void* ws, int64_t ws_byte
 //   sample_fix_kernel    same grid: every workgroup ANDs the scene's partials (words, 8 groups of lanes) and clears
 //                        the all-masked columns in its own real rows — at random init several queries are masked
 //                        everywhere on the fine levels, so the clearing must not be left to one workgroup
+// Both are templates over NQ, the number of groups of 128 mask columns: NQ = 1 (q <= 128) is the code they always were;
+// NQ = 2 (129 <= q <= 256, attention.hip's second query group) gives a lane the mask bytes lane, +64, +128, +192 and
+// the fix kernel 64 words (4 groups of 64 lanes instead of 8 of 32).
 constexpr int kSampleRows = 16;       // rows per workgroup (4 waves x 4 rows)
-constexpr int kSampleMaxQ = 128;
+constexpr int kSampleMaxQ = 256;
 constexpr int kSampleMaxScenes = 16;
 struct SampleArgs {
   const float* feats; const unsigned char* mask; const float* pos; const int64_t* idx;
@@ -346,8 +349,9 @@ struct SampleArgs {
   int n_valid[kSampleMaxScenes];
 };
 
+template <int NQ>
 __global__ __launch_bounds__(256) void sample_keys_kernel(SampleArgs a) {
-  __shared__ unsigned char acc[4][kSampleMaxQ];
+  __shared__ unsigned char acc[4][128 * NQ];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.y, k0 = blockIdx.x * kSampleRows + wave * 4;
   const int c4 = a.c >> 2, p4 = a.p >> 2;
@@ -362,9 +366,9 @@ __global__ __launch_bounds__(256) void sample_keys_kernel(SampleArgs a) {
     src[r] = a.idx[(int64_t)b * a.K + k];
   }
   float4 f0[4], f1[4], q0[4], q1[4];
-  unsigned char ma[4], mb[4];
+  unsigned char ma[4], mb[4], mc[NQ > 1 ? 4 : 1], md[NQ > 1 ? 4 : 1];
   const bool fa = lane < c4, fb = lane + 64 < c4, pa = has_pos && lane < p4, pb = has_pos && lane + 64 < p4;
-  const bool qa = lane < a.q, qb = lane + 64 < a.q;
+  const bool qa = lane < a.q, qb = lane + 64 < a.q, qc = NQ > 1 && lane + 128 < a.q, qd = NQ > 1 && lane + 192 < a.q;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const float4* f = reinterpret_cast<const float4*>(a.feats + src[r] * a.c);
@@ -376,8 +380,13 @@ __global__ __launch_bounds__(256) void sample_keys_kernel(SampleArgs a) {
     q1[r] = pb ? ps[lane + 64] : make_float4(0.f, 0.f, 0.f, 0.f);
     ma[r] = qa ? (ms[lane] ? 1 : 0) : 1;
     mb[r] = qb ? (ms[lane + 64] ? 1 : 0) : 1;
+    if (NQ > 1) {
+      mc[r] = qc ? (ms[lane + 128] ? 1 : 0) : 1;
+      md[r] = qd ? (ms[lane + 192] ? 1 : 0) : 1;
+    }
   }
   unsigned char m0 = 1, m1 = 1;       // AND of this wave's rows, bytes lane and lane + 64
+  unsigned char m2 = 1, m3 = 1;       // (NQ = 2) bytes lane + 128 and lane + 192
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const bool live = k0 + r < a.K;
@@ -394,9 +403,19 @@ __global__ __launch_bounds__(256) void sample_keys_kernel(SampleArgs a) {
     if (live && qb) mo[lane + 64] = pad ? 1 : mb[r];
     m0 &= live ? ma[r] : (unsigned char)1;
     m1 &= live ? mb[r] : (unsigned char)1;
+    if (NQ > 1) {
+      if (live && qc) mo[lane + 128] = pad ? 1 : mc[r];
+      if (live && qd) mo[lane + 192] = pad ? 1 : md[r];
+      m2 &= live ? mc[r] : (unsigned char)1;
+      m3 &= live ? md[r] : (unsigned char)1;
+    }
   }
   acc[wave][lane] = m0;
   acc[wave][lane + 64] = m1;
+  if (NQ > 1) {
+    acc[wave][lane + 128] = m2;
+    acc[wave][lane + 192] = m3;
+  }
   __syncthreads();
   if (threadIdx.x < a.qs) {
     const int t = threadIdx.x;
@@ -404,15 +423,17 @@ __global__ __launch_bounds__(256) void sample_keys_kernel(SampleArgs a) {
   }
 }
 
+template <int NQ>
 __global__ __launch_bounds__(256) void sample_fix_kernel(SampleArgs a) {
-  __shared__ unsigned int red[8][kSampleMaxQ / 4];
-  __shared__ unsigned char all_masked[kSampleMaxQ];
+  constexpr int NW = 32 * NQ, NGRP = 256 / NW;   // words of a mask row, groups of lanes that share the partials
+  __shared__ unsigned int red[NGRP][NW];
+  __shared__ unsigned char all_masked[128 * NQ];
   const int b = blockIdx.y, t = threadIdx.x;
-  const int w = t & 31, g = t >> 5, qw = a.qs >> 2;
+  const int w = t & (NW - 1), g = t / NW, qw = a.qs >> 2;
   unsigned int v = 0xFFFFFFFFu;
   if (w < qw) {
     const unsigned int* pp = reinterpret_cast<const unsigned int*>(a.part + (int64_t)b * a.nblk * a.qs) + w;
-    for (int j = g; j < a.nblk; j += 8) v &= pp[(int64_t)j * qw];
+    for (int j = g; j < a.nblk; j += NGRP) v &= pp[(int64_t)j * qw];
   }
   red[g][w] = v;
   __syncthreads();
@@ -420,7 +441,7 @@ __global__ __launch_bounds__(256) void sample_fix_kernel(SampleArgs a) {
   if (t < qw) {
     unsigned int r = red[0][t];
 #pragma unroll
-    for (int j = 1; j < 8; ++j) r &= red[j][t];
+    for (int j = 1; j < NGRP; ++j) r &= red[j][t];
     r &= 0x01010101u;
     reinterpret_cast<unsigned int*>(all_masked)[t] = r;
     // bytes past q in the last word come from the (all-ones) padding of part: ignore them
@@ -1400,7 +1421,7 @@ int usc_sample_keys(const float* feats, int32_t c, const uint8_t* mask, int32_t 
   USC_REQUIRE(n_scenes >= 1 && n_scenes <= usc::kSampleMaxScenes && K >= 1 && c >= 0 && c % 4 == 0 && q >= 0 &&
                   c <= 512 && q <= usc::kSampleMaxQ && (pos == nullptr || (p >= 4 && p % 4 == 0 && p <= 512)) &&
                   (c > 0 || q > 0),
-              "usc_sample_keys: unsupported sizes (scenes <= 16, queries <= 128, channel counts multiples of 4 up to 512)");
+              "usc_sample_keys: unsupported sizes (scenes <= 16, queries <= 256, channel counts multiples of 4 up to 512)");
   USC_REQUIRE(idx && n_valid && (c == 0 || (feats && out_feats)) && (q == 0 || (mask && out_mask && ws)) &&
                   (pos == nullptr || out_pos),
               "usc_sample_keys: null pointer");
@@ -1418,9 +1439,14 @@ int usc_sample_keys(const float* feats, int32_t c, const uint8_t* mask, int32_t 
     USC_REQUIRE(n_valid[b] >= 1, "usc_sample_keys: a scene without rows");
     a.n_valid[b] = n_valid[b];
   }
-  hipLaunchKernelGGL(usc::sample_keys_kernel, dim3((unsigned)a.nblk, (unsigned)n_scenes), dim3(256), 0, as_stream(s), a);
-  if (q > 0)
-    hipLaunchKernelGGL(usc::sample_fix_kernel, dim3((unsigned)a.nblk, (unsigned)n_scenes), dim3(256), 0, as_stream(s), a);
+  const dim3 grid((unsigned)a.nblk, (unsigned)n_scenes);
+  if (q <= 128) {
+    hipLaunchKernelGGL(usc::sample_keys_kernel<1>, grid, dim3(256), 0, as_stream(s), a);
+    if (q > 0) hipLaunchKernelGGL(usc::sample_fix_kernel<1>, grid, dim3(256), 0, as_stream(s), a);
+  } else {
+    hipLaunchKernelGGL(usc::sample_keys_kernel<2>, grid, dim3(256), 0, as_stream(s), a);
+    hipLaunchKernelGGL(usc::sample_fix_kernel<2>, grid, dim3(256), 0, as_stream(s), a);
+  }
   USC_CHECK_LAUNCH("usc_sample_keys");
   return USC_OK;
 }

@@ -406,7 +406,7 @@ class Mask3D(nn.Module):
                 feats_l = aux[hlevel].F
                 fused = (plan["gidx"] is not None and feats_l.is_cuda
                          and feats_l.dtype == torch.float32 and n_scenes <= 16 and feats_l.shape[1] % 4 == 0
-                         and self.num_queries <= 128)
+                         and self.num_queries <= fused_attn_max_queries())
 
                 # ---- query-independent half (side stream): rows of the level's features -> keys, values
                 # (the non-fused gather indexes per-scene slices that a compute-stream kernel may only just have produced —
@@ -444,7 +444,7 @@ class Mask3D(nn.Module):
                     queries, mask_features, mask_segments, len(aux) - hlevel - 1, ret_attn_mask=True,
                     point2segment=p2s_arg, coords=coords, defer_class=True, normed=normed)
                 decomposed_attn = attn_mask.decomposed_features
-                if fused and attn_mask.F.dtype == torch.bool and attn_mask.F.shape[1] <= 128:
+                if fused and attn_mask.F.dtype == torch.bool and attn_mask.F.shape[1] <= fused_attn_max_queries():
                     # the mask rows, the all-masked-query rule (reference :346) and the padding mask (:343): two launches
                     batched_attn = ops.sample_keys(None, attn_mask.F.contiguous(), None, plan["gidx"], n_scenes,
                                                    curr_sample_size, n_valid,
@@ -705,12 +705,12 @@ def multihead_attention(mha: nn.MultiheadAttention, query, key, value, attn_mask
     else:
         q, k, v = ops.in_proj(query, key, value, mha.in_proj_weight, mha.in_proj_bias, pos_q=pos_q, pos_k=pos_k)
     done = (lambda o: (o, res)) if residual else (lambda o: o)
-    if mask_bsl is not None and hd == 16 and L <= 128:
+    if mask_bsl is not None and hd == 16 and L <= fused_attn_max_queries():
         # `mask_bsl` = the decoder's bool[B, S, L] mask (same for every head): fused HIP kernels, no score tensor
         out = ops.masked_cross_attention(q, k, v, mask_bsl, H)
         return done(ops.linear(out, mha.out_proj.weight, mha.out_proj.bias))
-    if mask_bsl is None and attn_mask is None and hd == 16 and L == S and L <= 128:
-        # the decoder's self attention (100 queries): one HIP launch each way instead of the library's fused kernels
+    if mask_bsl is None and attn_mask is None and hd == 16 and L == S and L <= fused_attn_max_queries():
+        # the decoder's self attention (100 queries; up to 256): one HIP launch each way instead of the library's fused kernels
         out = ops.self_attention(q, k, v, H)
         return done(ops.linear(out, mha.out_proj.weight, mha.out_proj.bias))
     if mask_bsl is not None:
@@ -797,6 +797,17 @@ def set_kv_side_stream(on: bool):
         torch.cuda.synchronize()
     _KV_SIDE_STREAM = bool(on)
 _FUSED_ATTN_MASK = os.environ.get("USC3D_FUSED_ATTN_MASK", "1") != "0"
+# A/B switch: 0 sends 129 to 256 queries (the reference's export recipe runs num_queries=150) through the plain-operator
+# branches of the key sampling and of multihead_attention, as before the kernels took a second group of 128 queries;
+# no effect at <= 128 queries
+_FUSED_ATTN_WIDE = os.environ.get("USC3D_FUSED_ATTN_WIDE", "1") != "0"
+
+
+def fused_attn_max_queries() -> int:
+    """Most queries for which the decoder takes the fused attention and key-sampling kernels: the library's limit
+    (ops.ATTN_MAX_QUERIES = usc_attn_max_queries()), or one group of 128 with USC3D_FUSED_ATTN_WIDE=0.  The device set
+    criterion and decoder graph capture above 128 queries are not part of this."""
+    return ops.ATTN_MAX_QUERIES if _FUSED_ATTN_WIDE else min(128, ops.ATTN_MAX_QUERIES)
 
 
 _PAD_CACHE = {}
@@ -939,11 +950,13 @@ class CrossAttentionLayer(nn.Module):
 
 def _attention_on_projected(q, k, v, mask_bsl, H, dropout_p, training):
     """softmax(q k^T / sqrt(hd) + mask) v on already projected q [L,B,E], k / v [S,B,E] (sequence-first), mask bool[B,S,L]
-    (True = masked): the fused HIP kernels for head dim 16 and <= 128 queries, else plain tensor ops."""
+    (True = masked): the fused HIP kernels for head dim 16 and <= fused_attn_max_queries() queries, else plain tensor
+    ops."""
     L, B, E = q.shape
     S = k.shape[0]
     hd = E // H
-    if q.is_cuda and q.dtype == torch.float32 and hd == 16 and L <= 128 and mask_bsl is not None and dropout_p == 0.0:
+    if (q.is_cuda and q.dtype == torch.float32 and hd == 16 and L <= fused_attn_max_queries() and mask_bsl is not None
+            and dropout_p == 0.0):
         return ops.masked_cross_attention(q, k.contiguous(), v.contiguous(), mask_bsl, H)
     qh = q.reshape(L, B * H, hd).transpose(0, 1).reshape(B, H, L, hd)
     kh = k.reshape(S, B * H, hd).transpose(0, 1).reshape(B, H, S, hd)

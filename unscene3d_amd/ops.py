@@ -889,7 +889,7 @@ def sample_keys(feats, mask, pos, idx, n_scenes, K, n_valid, outs=None, unique=F
     """The cross-attention keys of one decoder pass (reference models/mask3d.py:306-346) in two launches:
     rows `idx` (i64[n_scenes*K], batch-wide row numbers) of the level's features f32[n,c], thresholded attention
     masks bool[n,Q] and positional encodings f32[n,p] (or None) -> ([B,K,c], bool[B,K,Q], [B,K,p]) — feats None: the
-    masks only (-> bool[B,K,Q]); mask None: the features (and positions) only, in one launch; a query column
+    masks only (-> bool[B,K,Q], Q <= 256); mask None: the features (and positions) only, in one launch; a query column
     masked in all K rows of its scene is cleared; rows k >= n_valid[b] (padding) are fully masked.
     outs: the caller's three buffers (e.g. the inputs of a captured pass).  Gradient: features only (scatter;
     `unique` as in gather_rows; valid_unique: only the first n_valid[b] keys of every scene are distinct and the padding
@@ -907,6 +907,8 @@ def sample_keys(feats, mask, pos, idx, n_scenes, K, n_valid, outs=None, unique=F
     _chk(idx, torch.int64, "idx")
     if idx.shape[0] != n_scenes * K or len(n_valid) != n_scenes:
         raise RuntimeError("sample_keys: inconsistent sizes")
+    if mask is not None and mask.shape[1] > ATTN_MAX_QUERIES:
+        raise RuntimeError(f"sample_keys: the mask rows take <= {ATTN_MAX_QUERIES} queries")
     return _SampleKeys.apply(feats, mask, pos, idx, int(n_scenes), int(K), list(n_valid), outs, unique, sink,
                              valid_unique)
 
@@ -1563,6 +1565,9 @@ def in_proj(xq, xk, xv, W, b, pos_q=None, pos_k=None, residual=False):
     return _InProj.apply(xq, xk, xv, W, b, pos_q, pos_k, residual)
 
 
+ATTN_MAX_QUERIES = int(lib.usc_attn_max_queries())    # queries the fused attention and key-sampling kernels take (256)
+
+
 class _MaskedCrossAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, mask, num_heads):
@@ -1571,7 +1576,7 @@ class _MaskedCrossAttention(torch.autograd.Function):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         m8 = mask.contiguous().view(torch.uint8)
         o = torch.empty_like(q)
-        lse = torch.empty((B * num_heads, 128), dtype=torch.float32, device=q.device)
+        lse = torch.empty((B * num_heads, lib.usc_attn_lse_stride(L)), dtype=torch.float32, device=q.device)
         wsb = lib.usc_attn_ws_bytes(L, S, B, num_heads)
         ws = _ws(wsb, q.device)
         check(lib.usc_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(m8), L, S, B, num_heads, E, _ptr(o), _ptr(lse), _ptr(ws),
@@ -1597,8 +1602,9 @@ def masked_cross_attention(q, k, v, mask_bsl, num_heads):
     """softmax(q k^T / 4 + mask) v per head for head dim 16: q [L,B,E], k/v [S,B,E] (f32, sequence-first),
     mask_bsl bool[B,S,L] with True = masked (the decoder's `batched_attn`, shared by all heads) -> [L,B,E]."""
     L, B, E = q.shape
-    if E != 16 * num_heads or L > 128 or mask_bsl.dtype != torch.bool or tuple(mask_bsl.shape) != (B, k.shape[0], L):
-        raise RuntimeError("masked_cross_attention: needs head dim 16, <= 128 queries and a bool[B,S,L] mask")
+    if (E != 16 * num_heads or L > ATTN_MAX_QUERIES or mask_bsl.dtype != torch.bool
+            or tuple(mask_bsl.shape) != (B, k.shape[0], L)):
+        raise RuntimeError(f"masked_cross_attention: needs head dim 16, <= {ATTN_MAX_QUERIES} queries and a bool[B,S,L] mask")
     return _MaskedCrossAttention.apply(q, k, v, mask_bsl, num_heads)
 
 
@@ -1608,7 +1614,7 @@ class _SelfAttention(torch.autograd.Function):
         L, B, E = q.shape
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         o = torch.empty_like(q)
-        lse = torch.empty((B * num_heads, 128), dtype=torch.float32, device=q.device)
+        lse = torch.empty((B * num_heads, lib.usc_attn_lse_stride(L)), dtype=torch.float32, device=q.device)
         check(lib.usc_self_attn_fwd(_ptr(q), _ptr(k), _ptr(v), L, B, num_heads, E, _ptr(o), _ptr(lse), _stream()),
               "usc_self_attn_fwd")
         ctx.save_for_backward(q, k, v, o, lse)
@@ -1629,11 +1635,11 @@ class _SelfAttention(torch.autograd.Function):
 
 def self_attention(q, k, v, num_heads):
     """softmax(q k^T / 4) v per head for head dim 16, no mask: q, k, v f32[L,B,E] (sequence-first) with the same
-    L <= 128 — the attention core of the decoder's SelfAttentionLayer (reference models/mask3d.py:491-545), one
+    L <= 256 — the attention core of the decoder's SelfAttentionLayer (reference models/mask3d.py:491-545), one
     launch each way, bit-reproducible."""
     L, B, E = q.shape
-    if E != 16 * num_heads or L > 128 or k.shape != q.shape or v.shape != q.shape:
-        raise RuntimeError("self_attention: needs head dim 16, <= 128 queries and q, k, v of one shape")
+    if E != 16 * num_heads or L > ATTN_MAX_QUERIES or k.shape != q.shape or v.shape != q.shape:
+        raise RuntimeError(f"self_attention: needs head dim 16, <= {ATTN_MAX_QUERIES} queries and q, k, v of one shape")
     for t, name in ((q, "q"), (k, "k"), (v, "v")):
         if not t.is_cuda or t.dtype != torch.float32:
             raise RuntimeError(f"self_attention: {name} must be an f32 HIP tensor")
