@@ -1184,6 +1184,26 @@ int usc_mask_gt_overlap(const uint8_t* masks, int64_t n, int32_t k, int64_t ld,
                         const int32_t* slot, int32_t nslots, int32_t* counts,
                         usc_stream_t s);
 
+/* ------------------------------------------------------------------------
+ * ViT image-encoder attention (models/encoders_2d/dino.py through
+ * third_party/dino_vit/extractor.py: DINO ViT-S/8 at stride 4, 2 962 tokens
+ * per 192x256 frame).  Unmasked, non-causal, forward only, head dim 64:
+ *   o = softmax(scale * q k^T) v   per (batch, head)
+ * qkv f32[B, T, 3, H, 64]: the rows nn.Linear(384, 1152) writes, read in place;
+ * o f32[B, T, H*64]: head-major columns, what attn.proj reads.  Both 16-byte
+ * aligned.  B, T, H >= 1, B*H <= 65535; T up to 2^30 (keys are streamed,
+ * the scores never reach memory: no limit from the kernel's structure).
+ * precision 0: f32 operands (v_mfma_f32_32x32x2_f32); 1: q, k, v and the
+ * probabilities rounded to bf16, nearest even as usc_cast_bf16
+ * (v_mfma_f32_32x32x16_bf16).  Accumulators and the running max / sum are f32
+ * in both.  No atomics, fixed summation order: bit-identical from run to run.
+ * Replaces `attn = (q @ k.transpose(-2, -1)) * scale; softmax; attn @ v` of
+ * the ViT's Attention.forward and the permutes around it.
+ * ---------------------------------------------------------------------- */
+int32_t usc_vit_attn_head_dim(void); /* 64 */
+int usc_vit_attn_fwd(const float* qkv, int32_t B, int32_t T, int32_t H, float scale,
+                     int32_t precision, float* o, usc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

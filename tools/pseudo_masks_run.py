@@ -10,9 +10,11 @@ Replicas only: rank r of W takes the scenes r, r+W, ... and nev
     python -m torch.distributed.run --nproc-per-node 8 tools/pseudo_masks_run.py --scenes DIR --out OUT
     python tools/pseudo_masks_run.py --synthetic 6 --out /tmp/pm                   # self-contained demo scenes
 
-Scene files (`DIR/*.npz`, one per scene; the 2D/3D encoders — DINO ViT, CSC Res16UNet — are stock networks whose
-weights this offline build cannot fetch, so their per-voxel outputs are an input here; `encode_scene_feats_2d/_3d`
-of unscene3d_amd.pseudo_masks.pipeline produce them from frames / a backbone when the weights are at hand):
+Scene files (`DIR/*.npz`, one per scene; this tool does not read frames, so the encoders' per-voxel outputs are an
+input here.  Both encoders are in the package — the DINO ViT-S/8 image encoder as
+unscene3d_amd.models.encoders_2d.DinoNet, the CSC Res16UNet as models.res16unet — and `encode_scene_feats_2d/_3d` of
+unscene3d_amd.pseudo_masks.pipeline produce these arrays from frames / a backbone; their published weights are files the
+user brings):
     coords            int[N,3] or [N,4]   voxel coordinates (b,x,y,z or x,y,z)
     feats_2d, feats_3d f32[N,d]            per-voxel features of one or both modalities (all-zero rows = not seen)
     segment_ids       int[N]              over-segmentation id per voxel (felzenszwalb_cpp.segment_mesh + 1-NN)

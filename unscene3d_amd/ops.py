@@ -1035,6 +1035,26 @@ def mask_gt_overlap(masks: torch.Tensor, slot: torch.Tensor, nslots: int) -> tor
     return counts
 
 
+VIT_ATTN_PRECISIONS = {"f32": 0, "bf16": 1}
+
+
+def vit_attention(qkv: torch.Tensor, B: int, T: int, H: int, scale: float, precision: str = "f32") -> torch.Tensor:
+    """softmax(scale * q k^T) v per (batch, head) of the ViT image encoder (csrc/vit_attention.hip): qkv f32
+    [B, T, 3, H, 64] as nn.Linear(384, 1152) writes it -> o f32 [B, T, H*64], head-major.  precision "f32" or "bf16"
+    (q, k, v and the probabilities rounded to bf16; f32 accumulation).  The scores never reach memory."""
+    require_device()
+    _chk(qkv, torch.float32, "qkv")
+    if precision not in VIT_ATTN_PRECISIONS:
+        raise RuntimeError(f"precision must be 'f32' or 'bf16', got {precision!r}")
+    d = lib.usc_vit_attn_head_dim()
+    if qkv.numel() != B * T * 3 * H * d:
+        raise RuntimeError(f"qkv must hold [B={B}, T={T}, 3, H={H}, {d}] values, got {list(qkv.shape)}")
+    o = torch.empty((B, T, H * d), dtype=torch.float32, device=qkv.device)
+    check(lib.usc_vit_attn_fwd(_ptr(qkv), B, T, H, float(scale), VIT_ATTN_PRECISIONS[precision], _ptr(o), _stream()),
+          "usc_vit_attn_fwd")
+    return o
+
+
 def cc_eps(xyz: torch.Tensor, eps: float, max_rounds: int = 256) -> torch.Tensor:
     """Connected components of the eps-ball graph == DBSCAN(eps, min_samples=1).labels_ (first-seen order)."""
     require_device()

@@ -27,7 +27,8 @@ def encode_scene_feats_3d(model, sinput, resolution_scale=2, precision="f32"):
 def encode_scene_feats_2d(model, images, camera_poses, color_intrinsics, coords, projecter, attention=False):
     """Image branch of `encode_scene_feats` (unscene3d_pseudo_main.py:287-330).
 
-    model(img[1,1,c,h,w]) -> (key_features, query_features), each [1,1,H,W,C] (the 2D backbone is the caller's);
+    model(img[1,1,c,h,w]) -> (key_features, query_features), each [1,1,H,W,C] (the 2D backbone is the caller's, e.g.
+    models.encoders_2d.DinoNet);
     images [1,n_frames,c,h,w], camera_poses [1,n_frames,4,4], color_intrinsics [1,4]; coords int[n,4];
     projecter: `Project2DFeaturesCUDA`.  One ray cast per frame serves both feature maps; every frame's features
     are reduced per voxel and folded into the running mean in one kernel (`fuse_frame`).
