@@ -1204,6 +1204,37 @@ int32_t usc_vit_attn_head_dim(void); /* 64 */
 int usc_vit_attn_fwd(const float* qkv, int32_t B, int32_t T, int32_t H, float scale,
                      int32_t precision, float* o, usc_stream_t s);
 
+/* ------------------------------------------------------------------------
+ * Instance targets of the supervised collate (datasets/utils.py:529-613,
+ * get_instance_masks) from one label table labels i64[n, ld]: column 0 the
+ * semantic label, column 1 the instance id (any int64), optionally a column of
+ * contiguous segment ids.  ids i64[u]: the distinct instance ids, ascending.
+ * n in 0..2^31-2.  Integers only: bit-identical from run to run.
+ *
+ * usc_instance_index: rank i32[n] = index of the row's id in ids (-1: not in
+ *   the list); count i32[u] = rows per id; first i32[u] = its first row
+ *   (INT32_MAX for an id without rows).  All three written in full.
+ * usc_instance_select: walks ids in ascending order; drops id -1, ids without
+ *   rows and ids whose label labels[first, 0] is one of filter i64[nf]; the
+ *   others take slots 0..T-1 in that order.  slot i32[u] (-1: dropped),
+ *   labels_out i64[>= T]: max(label - label_offset, 0); *n_kept = T (device).
+ * usc_instance_masks: masks u8[t, n], masks[j, r] = (slot[rank[r]] == j), every
+ *   byte written exactly once (no memset needed), any base alignment.  With
+ *   segment_mask u8[t, n_segments] (zeroed by the caller; may be NULL) it sets
+ *   segment_mask[j, seg[r * seg_ld]] = 1 for every row r of target j; segment
+ *   ids outside [0, n_segments) are skipped.  t = 0, n = 0 and n_segments = 0
+ *   launch nothing.
+ * ---------------------------------------------------------------------- */
+int usc_instance_index(const int64_t* labels, int64_t n, int32_t ld, const int64_t* ids, int32_t u,
+                       int32_t* rank, int32_t* count, int32_t* first, usc_stream_t s);
+int usc_instance_select(const int64_t* labels, int64_t n, int32_t ld, const int64_t* ids, int32_t u,
+                        const int32_t* count, const int32_t* first, const int64_t* filter, int32_t nf,
+                        int64_t label_offset, int32_t* slot, int64_t* labels_out, int32_t* n_kept,
+                        usc_stream_t s);
+int usc_instance_masks(const int32_t* rank, int64_t n, const int32_t* slot, int32_t u, int32_t t,
+                       uint8_t* masks, const int64_t* seg, int32_t seg_ld, int64_t n_segments,
+                       uint8_t* segment_mask, usc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,12 +1,13 @@
 """Run the training loop (`unscene3d_amd.trainer.TrainLoop`) on synthetic scenes and print one JSON line.
 
     python tools/train.py --synthetic 8 --voxels 150000 --steps 40 [--force-dist] [--no-early-optimizer]
-                          [--resume PATH] [--out DIR] [--no-shuffle]
+                          [--resume PATH] [--out DIR] [--no-shuffle] [--supervised]
 
 --synthetic N: the N rotated scenes of `bench.py`'s default workload (sizes spread over +-2 % of --voxels, the largest
 first).  One rank per process: under a launcher (RANK / WORLD_SIZE / LOCAL_RANK set) every process is one rank; this
 tool does not spawn ranks.  ms_per_step is measured over the steps after the loop prepared its steady state, between
-two device synchronisations."""
+two device synchronisations.  --supervised: the same scenes with ground-truth label tables (`SyntheticLabelledDataset`)
+through `VoxelizeCollate` (filter_out_classes=[0, 1], label_offset=2), num_targets=19, loss.device_max_targets=128."""
 import argparse
 import json
 import os
@@ -35,11 +36,13 @@ def main():
     ap.add_argument("--no-shuffle", action="store_true")
     ap.add_argument("--dist-backend", default="nccl")
     ap.add_argument("--resume", default=None, metavar="PATH")
+    ap.add_argument("--supervised", action="store_true", help="ground-truth label tables through VoxelizeCollate")
     ap.add_argument("--out", default=None, metavar="DIR", help="write DIR/last.ckpt at the end")
     a = ap.parse_args()
 
     from unscene3d_amd.config import apply_overrides, default_config
-    from unscene3d_amd.datasets.synthetic import SyntheticFreeMaskDataset
+    from unscene3d_amd.datasets.synthetic import SyntheticFreeMaskDataset, SyntheticLabelledDataset
+    from unscene3d_amd.datasets.utils import VoxelizeCollate
     from unscene3d_amd.trainer import InstanceSegmentation, TrainLoop
     from unscene3d_amd.trainer.loop import pin_to_device_numa
 
@@ -56,7 +59,9 @@ def main():
         dist.init_process_group(a.dist_backend, rank=rank, world_size=world,
                                 **({"device_id": dev} if a.dist_backend == "nccl" else {}))
 
-    cfg = apply_overrides(default_config(), ["general.num_targets=3", f"data.batch_size={world}"])
+    overrides = ["general.num_targets=19", "loss.device_max_targets=128"] if a.supervised else ["general.num_targets=3"]
+    cfg = apply_overrides(default_config(), overrides + [f"data.batch_size={world}"])
+    dataset = SyntheticLabelledDataset if a.supervised else SyntheticFreeMaskDataset
     torch.manual_seed(1234)
     module = InstanceSegmentation(cfg).to(dev).train()
     n = max(1, a.synthetic) * world
@@ -64,10 +69,13 @@ def main():
     for j in range(n):
         scale = 1.0 if n == 1 else 1.0 + a.spread - 2 * a.spread * ((j * 5) % n) / max(1, n - 1)
         seed = 2000 if j == 0 else 2000 + 16 * j
-        scenes.append(SyntheticFreeMaskDataset(n_scenes=1, target_voxels=int(a.voxels * scale), seed=seed)[0])
+        scenes.append(dataset(n_scenes=1, target_voxels=int(a.voxels * scale), seed=seed)[0])
     kw = dict(device=dev, world=world, rank=rank, force_dist=a.force_dist, early_optimizer=not a.no_early_optimizer,
               write_back_grad=a.write_back_grad, total_steps=100000, steady_after=a.steady_after, resident=True,
               shuffle=not a.no_shuffle, seed=2000)
+    if a.supervised:
+        kw["collate"] = VoxelizeCollate(ignore_label=255, voxel_size=cfg.data.voxel_size, mode="train",
+                                        filter_out_classes=[0, 1], label_offset=2, device=str(dev))
     loop = TrainLoop.resume(a.resume, module, cfg, scenes, **kw) if a.resume else TrainLoop(module, cfg, scenes, **kw)
     with loop:
         first = loop.global_step
@@ -93,7 +101,8 @@ def main():
         line = {"steps": loop.global_step - first, "skipped": loop.skipped, "timed_steps": timed,
                 "ms_per_step": (1e3 * dt / timed) if timed > 0 else None,
                 "ms_per_step_p10_p50_p90": ([round(float(np.percentile(per, q)), 3) for q in (10, 50, 90)] if per else None),
-                "early_optimizer": loop.early, "world": world, "force_dist": bool(a.force_dist),
+                "early_optimizer": loop.early, "supervised": bool(a.supervised), "world": world,
+                "force_dist": bool(a.force_dist),
                 "buckets_started_during_backward": loop.reducer.started_during_backward if loop.reducer else None,
                 "losses_step": rep["step"] if rep else None, "losses": rep["losses"] if rep else None,
                 "library": _lib.lib.usc_build_info().decode()}

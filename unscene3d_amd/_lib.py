@@ -216,6 +216,9 @@ SIGNATURES = {
     "usc_mask_gt_overlap": (C.c_int, [_p, _i64, _i32, _i64, _p, _i32, _p, _p]),
     "usc_vit_attn_head_dim": (_i32, []),
     "usc_vit_attn_fwd": (C.c_int, [_p, _i32, _i32, _i32, _f32, _i32, _p, _p]),
+    "usc_instance_index": (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _p]),
+    "usc_instance_select": (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _i32, _i64, _p, _p, _p, _p]),
+    "usc_instance_masks": (C.c_int, [_p, _i64, _p, _i32, _i32, _p, _p, _i32, _i64, _p, _p]),
 }
 
 

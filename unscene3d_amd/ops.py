@@ -1035,6 +1035,44 @@ def mask_gt_overlap(masks: torch.Tensor, slot: torch.Tensor, nslots: int) -> tor
     return counts
 
 
+def instance_targets(labels: torch.Tensor, num_segments=None, filter_out_classes=(), label_offset: int = 0, alloc=None):
+    """Instance targets of one label table (csrc/targets.hip; reference datasets/utils.py:529-613): labels i64 [N, ld],
+    column 0 the semantic label, column 1 the instance id, and — when `num_segments` is given — column 2 a segment id
+    in [0, num_segments).  -> (labels i64 [T], masks bool [T, N], segment_mask bool [T, num_segments] or None): one
+    target per instance id other than -1 whose label (column 0 of its first row) is not in `filter_out_classes`, in
+    ascending id order; labels = max(label - label_offset, 0).  The distinct ids come from torch.unique; the
+    decisions are made on the device and T is the one value read back (for the allocation).
+    alloc(shape, dtype, zero) -> device tensor: where the outputs and the work arrays come from (tests pass one that
+    surrounds every array with guard bytes)."""
+    require_device()
+    _chk(labels, torch.int64, "labels")
+    if labels.dim() != 2 or labels.shape[1] < (2 if num_segments is None else 3):
+        raise RuntimeError("labels must be [N, >= 2] (with segments: [N, >= 3])")
+    dev = labels.device
+    if alloc is None:
+        def alloc(shape, dtype, zero):
+            return (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=dev)
+    n, ld = labels.shape
+    ids = torch.unique(labels[:, 1]).contiguous()
+    u = int(ids.shape[0])
+    rank, count, first = alloc((n,), torch.int32, False), alloc((u,), torch.int32, False), alloc((u,), torch.int32, False)
+    slot, lab, kept = alloc((u,), torch.int32, False), alloc((u,), torch.int64, False), alloc((1,), torch.int32, False)
+    flt = torch.tensor([int(c) for c in filter_out_classes], dtype=torch.int64, device=dev)
+    st = _stream()
+    check(lib.usc_instance_index(_ptr(labels), n, ld, _ptr(ids), u, _ptr(rank), _ptr(count), _ptr(first), st),
+          "usc_instance_index")
+    check(lib.usc_instance_select(_ptr(labels), n, ld, _ptr(ids), u, _ptr(count), _ptr(first), _ptr(flt),
+                                  int(flt.shape[0]), int(label_offset), _ptr(slot), _ptr(lab), _ptr(kept), st),
+          "usc_instance_select")
+    t = int(kept.item())                                     # the one read-back of a table
+    masks = alloc((t, n), torch.uint8, False)
+    seg_mask = None if num_segments is None else alloc((t, int(num_segments)), torch.uint8, True)
+    check(lib.usc_instance_masks(_ptr(rank), n, _ptr(slot), u, t, _ptr(masks), _ptr(labels[:, 2:]) if seg_mask is not None
+                                 else None, ld, 0 if seg_mask is None else int(num_segments), _ptr(seg_mask), st),
+          "usc_instance_masks")
+    return lab[:t], masks.view(torch.bool), None if seg_mask is None else seg_mask.view(torch.bool)
+
+
 VIT_ATTN_PRECISIONS = {"f32": 0, "bf16": 1}
 
 

@@ -162,7 +162,34 @@ def make_scene(seed: int, target_voxels: int = 150_000, points_per_cell: float =
     return {
         "xyz": pts.astype(np.float64), "colors": colors, "segment_ids": segment_ids, "masks": masks,
         "segment_connectivity": conn, "n_objects": n_obj, "n_segments": S, "n_voxels_estimate": nv,
+        "objects": objs, "faces": faces,
     }
+
+
+def make_label_table(scene, seed: int = 0, num_classes: int = 20, parts: int = 1, unlabeled: float = 0.01):
+    """Ground-truth table i32[P, 3] = [semantic label, instance id, segment id] of a `make_scene` scene, as the supervised
+    reader yields it.  Every object is one instance (`parts` > 1 splits the furniture into up to `parts` instances by
+    face, for scenes with more instances); the ids are gapped (7 + 13 k) and assigned by a seeded permutation, so they
+    are not in row or object order.  Floor = class 0 and walls = class 1 (`filter_out_classes=[0, 1]` removes them),
+    furniture draws a class in [2, num_classes) per object.  A fraction `unlabeled` of the points gets instance -1 and
+    label 255, and the smallest furniture instance gets label 255."""
+    rng = np.random.default_rng(seed + 104729)
+    objs, faces = scene["objects"], scene["faces"]
+    key = objs * 8 + np.where(objs >= 5, faces % max(1, int(parts)), 0)
+    uniq, inst = np.unique(key, return_inverse=True)
+    inst = inst.reshape(-1)
+    ids = 7 + 13 * rng.permutation(uniq.shape[0])
+    cls_of_obj = rng.integers(2, num_classes, scene["n_objects"])
+    cls_of_obj[0], cls_of_obj[1:5] = 0, 1
+    cls = cls_of_obj[uniq // 8]
+    furniture = np.nonzero(uniq // 8 >= 5)[0]
+    if furniture.size:
+        sizes = np.bincount(inst, minlength=uniq.shape[0])
+        cls[furniture[np.argmin(sizes[furniture])]] = 255
+    table = np.stack([cls[inst], ids[inst], scene["segment_ids"]], 1)
+    drop = rng.random(objs.shape[0]) < unlabeled
+    table[drop, 0], table[drop, 1] = 255, -1
+    return table.astype(np.int32)
 
 
 def make_segment_scene(seed: int, side: int = 25, dims=(384, 96), n_objects: int = 16, noise=(0.3, 1.2)):

@@ -81,13 +81,14 @@ class TrainLoop:
     cfg.trainer.max_epochs).  early_optimizer=False: one AdamW launch at the end of the step (under a reducer: the
     reducer averages, as before).  resident=True keeps the raw scene arrays in device memory (the collate reads them
     from there).  val_scenes + val_gt_ids ({scene name: ids}) switch the validation pass on; out_dir receives
-    `last-epoch.ckpt` / `best.ckpt`."""
+    `last-epoch.ckpt` / `best.ckpt`.  collate: the train-mode collate function (default `FreeMaskVoxelizeCollate`;
+    `datasets.utils.VoxelizeCollate(mode="train", …)` for scenes with ground-truth label tables)."""
 
     def __init__(self, module, cfg, scenes, *, device, world=1, rank=0, force_dist=False, early_optimizer=True,
                  overlap_allreduce=True, write_back_grad=False, batch_size=1, seed=0, shuffle=True, sizes=None,
                  bucket_window=8, total_steps=None, epochs=None, steady_after=2, steps_in_flight=None, prefetch_depth=2,
                  prefetch_thread=True, decoder_graphs=True, resident=False, spatial_sort=0, val_scenes=None,
-                 val_gt_ids=None, out_dir=None):
+                 val_gt_ids=None, out_dir=None, collate=None):
         from .. import ops
         from ..datasets.prefetch import ScenePrefetcher
         from ..datasets.utils import FreeMaskVoxelizeCollate
@@ -134,8 +135,8 @@ class TrainLoop:
         self._resident = {} if resident else None
         if decoder_graphs:
             module.model.enable_decoder_graphs(batch_size=self.batch_size, device=dev)
-        self.collate = FreeMaskVoxelizeCollate(ignore_label=255, voxel_size=cfg.data.voxel_size, mode="train",
-                                               device=str(dev), spatial_sort=spatial_sort)
+        self.collate = collate if collate is not None else FreeMaskVoxelizeCollate(
+            ignore_label=255, voxel_size=cfg.data.voxel_size, mode="train", device=str(dev), spatial_sort=spatial_sort)
 
         # ---- gradient exchange, optimizer in the backward pass
         self.reducer = None
