@@ -274,6 +274,58 @@ int usc_spconv_gather_gemm_bf16(const uint16_t* in, int64_t n_in, int32_t cin,
                                 const float* bias, float* out, int32_t accumulate,
                                 void* ws, int64_t ws_bytes, usc_stream_t s);
 
+/* ------------------------------------------------------------------------
+ * Split-bf16 matrix-core convolution at f32-grade accuracy (opt-in training
+ * precision, unscene3d_amd.training_precision("bf16x2" | "bf16x3")): each f32
+ * operand is P bf16 planes x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1)
+ * (round to nearest even, f32 subtractions), and the plane products (i, j) with
+ * i + j < P are summed in f32 on v_mfma_f32_32x32x16_bf16.  Dropped terms:
+ * <= 2^-23 |x||w| per product for P = 3, <= 3 * 2^-16 |x||w| for P = 2.
+ * Stands for the forward and the input gradient of MinkowskiConvolution
+ * (ME 0.5.4 src/convolution_kernel.cu; models/modules/common.py:125-188,
+ * models/res16unet.py:224-297) under that opt-in; the weight gradient stays on
+ * the f32 kernels.
+ * ---------------------------------------------------------------------- */
+/* in f32[rows,c] -> out bf16[rows][P][c] (the planes of one row are contiguous:
+ * what the split conv gathers).  P is 2 or 3.  A value whose first plane is
+ * not finite keeps it and gets zero in the other planes (inf stays inf).  in
+ * 16-byte, out 8-byte aligned.  Replaces the input read of the ME conv
+ * forward / backward (models/modules/common.py:125-188). */
+int usc_split_bf16_rows(const float* in, int64_t rows, int32_t c, int32_t P,
+                        uint16_t* out, usc_stream_t s);
+/* The same for a flat array, any n: out bf16[P][n] (one row of n values). */
+int usc_split_bf16(const float* in, int64_t n, int32_t P, uint16_t* out,
+                   usc_stream_t s);
+/* Weights f32[K,cin,cout] -> P bf16 planes, each in the B-fragment order of
+ * usc_spconv_pack_w_bf16, one plane after the other (P*K*cin*cout values).
+ * transposed = 1 packs the mirrored transpose the input gradient needs,
+ * W'[k][n][c] = W[K-1-k][c][n] (K == 1: the plain transpose), the convention of
+ * usc_weight_transpose(mirror); the operand shape is then cout -> cin.  The
+ * operand's input width must be a multiple of 16, its output width of 32.
+ * Replaces ME's kernel parameter as the conv forward / backward reads it
+ * (models/modules/common.py:125-188). */
+int usc_spconv_pack_w_split(const float* W, int32_t K, int32_t cin, int32_t cout,
+                            int32_t P, int32_t transposed, uint16_t* Wp,
+                            usc_stream_t s);
+/* Scratch bytes usc_spconv_gather_gemm_split needs (0: none), or -1 when the
+ * shape is not covered (P not 2 or 3, cin % 16, cout % 32, K > 64, ...). */
+int64_t usc_spconv_gather_gemm_split_ws_bytes(int64_t n_out, int32_t cin,
+                                              int32_t cout, int32_t K, int32_t P);
+/* out[o,:] (= or += when accumulate) sum_k sum_{i+j<P} x_i[nbr[k*n_out+o],:] @ W_j[k] (+ bias)
+ * with in bf16[n_in][P][cin] (usc_split_bf16_rows), Wp from
+ * usc_spconv_pack_w_split; nbr -1 = no neighbour, nbr NULL = K==1 identity
+ * rows.  One lane sums each output element over k, channel step and product
+ * in a fixed order: no atomics, no split-K, bit-identical from run to run.
+ * Replaces the same ME calls as usc_spconv_gather_gemm for the stride-1 conv
+ * forward and, on the transposed pack, its input gradient
+ * (MinkowskiConvolution forward / backward, models/modules/common.py:125-188). */
+int usc_spconv_gather_gemm_split(const uint16_t* in, int64_t n_in, int32_t cin,
+                                 const uint16_t* Wp, int32_t K, int32_t cout,
+                                 int32_t P, const int32_t* nbr, int64_t n_out,
+                                 const float* bias, float* out,
+                                 int32_t accumulate, void* ws, int64_t ws_bytes,
+                                 usc_stream_t s);
+
 /* Scratch bytes for usc_spconv_wgrad. */
 int64_t usc_spconv_wgrad_ws_bytes(int32_t K, int32_t cin, int32_t cout);
 /* Weight gradient:  dW[k] = sum_{p in list k}  a[a_idx[p],:]^T  b[b_idx[p],:]
@@ -458,6 +510,43 @@ int usc_conv_bn_act_forward_bf16(const usc_kmap* m, int32_t kind,
                                  float* out, void* ws, int64_t ws_bytes,
                                  usc_stream_t s);
 
+/* usc_conv_bn_act_forward / _backward of a stride-1 (USC_CONV_SAME) unit with the
+ * convolution's forward and input gradient in split bf16 (P = 2 or 3 planes,
+ * usc_spconv_gather_gemm_split).  Forward: x is split and W packed into the
+ * scratch on the caller's stream on EVERY call (no cache: an optimizer may write
+ * W in place between, or inside, passes), then the unit's f32 batch norm,
+ * residual and ReLU run as in usc_conv_bn_act_forward (tile form included; the
+ * convolution leaves no slices).  Backward: batch norm backward as in
+ * usc_conv_bn_act_backward, then dy is split, W packed transposed and dx
+ * computed over the map's table (dx_accumulate honoured); where the transposed
+ * shape is not covered (cin % 32 != 0) the input gradient runs on the f32
+ * kernels.  The weight gradient is exactly usc_conv_bn_act_backward's: f32
+ * kernels, lane, hold / release.  The forward returns an error for shapes
+ * usc_spconv_gather_gemm_split_ws_bytes does not cover, and both return one,
+ * before anything is launched, when the scratch is too short (the backward:
+ * shorter than usc_unit_split_ws_bytes).  Replaces ME's
+ * MinkowskiConvolution forward / backward + MinkowskiBatchNorm
+ * (models/modules/common.py:125-188, models/modules/resnet_block.py:48-64) under
+ * the split training precision. */
+int64_t usc_unit_split_ws_bytes(const usc_kmap* m, int32_t kind, int32_t cin,
+                                int32_t cout, int32_t P);
+int usc_conv_bn_act_forward_split(const usc_kmap* m, int32_t kind,
+                                  const float* x, int32_t cin, const float* W,
+                                  int32_t cout, int32_t P, const usc_bn* bn,
+                                  const float* residual, int32_t relu, float* y,
+                                  float* stats, float* out, void* ws,
+                                  int64_t ws_bytes, usc_stream_t s);
+int usc_conv_bn_act_backward_split(const usc_kmap* m, int32_t kind,
+                                   const float* x, int32_t cin, const float* W,
+                                   int32_t cout, int32_t P, const usc_bn* bn,
+                                   const float* y, const float* stats,
+                                   const float* out_relu, const float* dout,
+                                   float* dy, float* dres, float* dx,
+                                   int32_t dx_accumulate, float* dW,
+                                   int32_t dW_accumulate, float* dgamma,
+                                   float* dbeta, int32_t dbn_accumulate,
+                                   void* ws, int64_t ws_bytes, usc_stream_t s);
+
 /* ------------------------------------------------------------------------
  * Step programs: the issue loop of a whole network stage behind ONE call.
  * The reference walks Res16UNetBase.forward (models/res16unet.py:224-297) module by module from the interpreter, and
@@ -476,6 +565,8 @@ int usc_conv_bn_act_forward_bf16(const usc_kmap* m, int32_t kind,
  *   USC_STEP_ADD      : dst[0 .. n) += a[0 .. n)   (n counts floats)
  *   USC_STEP_UNIT_FWD_BF16 : usc_conv_bn_act_forward_bf16(map, kind, x, cin, W (read as the packed bf16 weights),
  *                       cout, bn, residual, relu, y, stats, out)
+ * A USC_STEP_UNIT_FWD / USC_STEP_UNIT_BWD step with split_planes = 2 or 3 calls usc_conv_bn_act_forward_split /
+ * usc_conv_bn_act_backward_split with P = split_planes instead (0: the f32 unit).
  * ---------------------------------------------------------------------- */
 enum usc_step_op { USC_STEP_UNIT_FWD = 0, USC_STEP_UNIT_BWD = 1, USC_STEP_CAT = 2, USC_STEP_SPLIT = 3, USC_STEP_ADD = 4,
                    USC_STEP_UNIT_FWD_BF16 = 5 };
@@ -503,6 +594,7 @@ typedef struct usc_step {
   float* dst2;
   int64_t n;
   int32_t ca, cb;
+  int32_t split_planes, reserved;
 } usc_step;
 /* sizeof(usc_step) as the library was compiled: a binding checks its own mirror of the structure against it. */
 int32_t usc_step_size(void);

@@ -1,0 +1,631 @@
+"""Opt-in split-bf16 training convolutions (csrc/spconv_split.hip, unscene3d_amd/precision.py) on the MI355X.
+
+Kernels: the split and the packs against the numpy planes bit for bit; the gather-GEMM against a float64 sum of exactly
+the kept plane products (tests/bf16_split_ref.py) — every product is exact, so only the f32 accumulation differs:
+|y - y_ref| <= 2^-20 * sum |x||w|, the allowance of test_gpu_bf16_conv.py.  A coherent-operand case shows that a dropped
+product cannot hide below that allowance."""
+import numpy as np
+import pytest
+import torch
+
+from bf16_split_ref import kept_pairs, split_bits, split_conv_ref, split_conv_vjp_ref, split_planes
+from oracle import sparse_ref as R
+
+pytestmark = pytest.mark.gpu
+
+BOUND = 2.0 ** -20                       # f32 accumulation allowance (BOUND of test_gpu_bf16_conv.py)
+SHAPES = [(16, 32), (48, 96), (80, 64), (96, 96), (128, 96)]
+ROWS = [1, 33, 257, 600]
+
+
+def _bits(t):
+    return t.view(torch.int16).cpu().numpy().view(np.uint16)
+
+
+def _scene_table(n, seed):
+    """Neighbour table i32[27, n] of a small random voxel scene: a dense random cluster first, then isolated voxels
+    (about a sixth of the rows; with n > 256 the last 256-row block holds isolated rows only, so every offset but the
+    centre is one no row of that block has)."""
+    rng = np.random.default_rng(seed)
+    n_iso = n // 6 if n > 1 else 0
+    if n > 256:
+        n_iso = max(n_iso, n - (n - 1) // 256 * 256)
+    n_dense = n - n_iso
+    side = max(2, int(np.ceil((n_dense / 0.3) ** (1 / 3))))
+    cells = rng.choice(side ** 3, size=n_dense, replace=False)
+    dense = np.stack([cells // (side * side), (cells // side) % side, cells % side], 1)
+    iso = np.stack([np.full(n_iso, 1000), 5 * np.arange(n_iso), np.zeros(n_iso, np.int64)], 1)
+    xyz = np.concatenate([dense, iso], 0)
+    coords4 = np.concatenate([np.zeros((n, 1), np.int64), xyz], 1).astype(np.int32)
+    return R.kernel_map_cube(coords4, 1, 3).astype(np.int32)
+
+
+@pytest.fixture(scope="module")
+def tables():
+    return {n: _scene_table(n, 100 + n) for n in ROWS}
+
+
+def test_tables_have_missing_neighbours_and_an_offset_a_block_lacks(tables):
+    for n, nbr in tables.items():
+        assert nbr.shape == (27, n) and (nbr[13] == np.arange(n)).all()
+        if n > 1:
+            has = (nbr >= 0).sum(0)
+            assert has.min() < 27 and has.max() > 1                       # rows with missing neighbours, rows with some
+        if n == 1 or n > 256:
+            last = nbr[:, (n - 1) // 256 * 256:]
+            assert ((last >= 0).sum(1) == 0).any()                        # an offset no row of the last block has
+    assert any(((t[:, :256] >= 0).sum(1) > 0).all() for t in tables.values())    # ... and a block that has them all
+
+
+# ---------------------------------------------------------------------------------------------------------- 1. the split
+@pytest.mark.parametrize("P", [2, 3])
+def test_split_kernel_bits_equal_the_numpy_planes(device, P):
+    from unscene3d_amd import ops
+    rng = np.random.default_rng(5)
+    for n in (1, 3, 4, 7, 1027):
+        a = rng.standard_normal(n).astype(np.float32)
+        special = np.array([0.0, -0.0, -1.5, 2.0 ** -120, -1.3 * 2.0 ** -120, np.inf, -np.inf, 3.4e38, 1.0 + 2.0 ** -9 + 2.0 ** -18],
+                           np.float32)
+        a[:min(n, special.size)] = special[:n]
+        if n > 16:
+            a[16:n // 2] *= np.exp2(rng.integers(-20, 21, n // 2 - 16)).astype(np.float32)
+        want = split_bits(a, P)                                            # [P, n]
+        guard = 8
+        buf = torch.full((P * n + 2 * guard,), -7.0, dtype=torch.bfloat16, device=device)
+        from unscene3d_amd._lib import check, lib
+        x = torch.from_numpy(a).to(device)
+        # an 8-byte aligned output inside the guarded buffer
+        check(lib.usc_split_bf16(x.data_ptr(), n, P, buf.data_ptr() + 2 * guard, ops._stream()), "usc_split_bf16")
+        got = _bits(buf)
+        assert np.array_equal(got[guard:guard + P * n].reshape(P, n), want), (P, n)
+        fill = _bits(torch.full((1,), -7.0, dtype=torch.bfloat16))[0]
+        assert (got[:guard] == fill).all() and (got[guard + P * n:] == fill).all()
+    # inf stays inf, no NaN appears; the row form interleaves the planes per row
+    rows, c = 5, 12
+    a = rng.standard_normal((rows, c)).astype(np.float32)
+    a[1, 3], a[4, 11] = np.inf, -np.inf
+    got = _bits(ops.split_bf16(torch.from_numpy(a).to(device), P))         # [rows, P, c]
+    assert np.array_equal(got, split_bits(a, P).transpose(1, 0, 2))
+    back = (got.astype(np.uint32) << 16).view(np.float32).astype(np.float64).sum(1)
+    assert not np.isnan(back).any() and back[1, 3] == np.inf and back[4, 11] == -np.inf
+
+
+@pytest.mark.parametrize("P", [2, 3])
+def test_weight_pack_planes_are_in_fragment_order(device, P):
+    """Plane 0 of the plain pack equals usc_spconv_pack_w_bf16; every plane equals that order applied to the numpy plane;
+    the transposed pack is the plain pack of the mirrored transpose."""
+    from unscene3d_amd import ops, precision
+    g = torch.Generator().manual_seed(2)
+    for K, cin, cout in ((1, 16, 32), (27, 48, 96), (8, 96, 64)):
+        W = torch.randn((K, cin, cout), generator=g)
+        got = _bits(ops.pack_w_split(W.to(device), P))
+        planes = split_planes(W.numpy(), P)
+        for p in range(P):
+            want = _bits(precision.pack_weights(torch.from_numpy(planes[p]).to(device)))
+            assert np.array_equal(got[p], want), (K, cin, cout, p)
+        if cin % 32 == 0 and cout % 16 == 0:
+            Wt = W.flip(0).transpose(1, 2).contiguous() if K > 1 else W.transpose(1, 2).contiguous()
+            assert np.array_equal(_bits(ops.pack_w_split(W.to(device), P, transposed=True)),
+                                  _bits(ops.pack_w_split(Wt.to(device), P)))
+    with pytest.raises(RuntimeError, match="multiple of"):
+        ops.pack_w_split(torch.zeros((27, 96, 48), device=device), P)
+    with pytest.raises(RuntimeError, match="P must be 2 or 3"):
+        ops.pack_w_split(torch.zeros((27, 96, 96), device=device), 4)
+
+
+# ------------------------------------------------------------------------------------ 2. the kernel against the oracle
+def _check(y, ref, mag, what, bound=BOUND):
+    err = np.abs(y.double().cpu().numpy() - ref)
+    lim = bound * mag + 1e-30
+    worst = float((err / lim).max())
+    assert (err <= lim).all(), (what, worst, float(err.max()))
+    return worst
+
+
+@pytest.mark.parametrize("K", [1, 27])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("P", [2, 3])
+def test_kernel_matches_float64_of_the_kept_plane_products(device, tables, P, shape, K):
+    from unscene3d_amd import ops
+    cin, cout = shape
+    g = torch.Generator().manual_seed(1000 * P + 10 * cin + cout + K)
+    worst = 0.0
+    for n in ROWS:
+        nbr_np = tables[n] if K == 27 else None
+        nbr = None if nbr_np is None else torch.from_numpy(nbr_np).to(device)
+        x = torch.randn((n, cin), generator=g)
+        W = torch.randn((K, cin, cout), generator=g) / (K * cin) ** 0.5
+        xs, Wp = ops.split_bf16(x.to(device), P), ops.pack_w_split(W.to(device), P)
+        guard = 3
+        buf = torch.full((n + 2 * guard, cout), 123.0, device=device)
+        y = buf[guard:guard + n]
+        ops.gather_gemm_split(xs, Wp, K, cout, nbr, n, out=y)
+        ref, mag = split_conv_ref(x.numpy(), W.numpy(), nbr_np, n, P)
+        worst = max(worst, _check(y, ref, mag, (P, shape, K, n)))
+        assert bool((buf[:guard] == 123.0).all()) and bool((buf[guard + n:] == 123.0).all())
+        y2 = ops.gather_gemm_split(xs, Wp, K, cout, nbr, n)
+        assert torch.equal(y2, y)                                          # two launches, the same bits
+        if n in (33, 600):                                                 # bias and accumulate
+            b = torch.randn(cout, generator=g)
+            acc = torch.randn((n, cout), generator=g)
+            y3 = acc.to(device)
+            ops.gather_gemm_split(xs, Wp, K, cout, nbr, n, bias=b.to(device), out=y3, accumulate=True)
+            ref3, mag3 = split_conv_ref(x.numpy(), W.numpy(), nbr_np, n, P, bias=b.numpy(), acc=acc.numpy())
+            worst = max(worst, _check(y3, ref3, mag3, (P, shape, K, n, "bias+acc")))
+            if nbr_np is not None:
+                lone = torch.from_numpy((nbr_np >= 0).sum(0) == 1)          # only the centre: x W[13] + bias + acc
+                assert bool(lone.any())
+    print(f"split P={P} {cin}->{cout} K={K}: worst |err| / (2^-20 sum|x||w|) = {worst:.3f}")
+
+
+# ---------------------------------------------------------------------------------- 3. a missing product must be seen
+@pytest.mark.parametrize("P", [2, 3])
+def test_a_dropped_product_cannot_hide(device, P):
+    """Coherent operands: every x equals a, every w equals b, K = 1, cin = 16.  a = 1 + 2^-9 + 2^-18 and b = 1.5 a have
+    three non-zero planes each (a: 1, 2^-9, 2^-18), every product is a multiple of 3 * 2^-19 and every partial sum stays
+    below 2^5: all of them are exact f32 values, so an f32 accumulation in ANY order returns the oracle exactly and the
+    tolerance applied to the kernel is one f32 epsilon of sum |x||w| (2^-23), not the 2^-20 of random operands.  Removing
+    any single kept pair moves the oracle by more than 8x that tolerance (shown first, on the CPU)."""
+    from unscene3d_amd import ops
+    a = np.float32(1.0 + 2.0 ** -9 + 2.0 ** -18)
+    b = np.float32(1.5) * a
+    n, cin, cout = 40, 16, 32
+    x = np.full((n, cin), a, np.float32)
+    W = np.full((1, cin, cout), b, np.float32)
+    assert (split_planes(x, 3) != 0).all() and (split_planes(W, 3) != 0).all()
+    assert (split_planes(x, 3).sum(0) == x).all() and (split_planes(W, 3).sum(0) == W).all()
+    ref, mag = split_conv_ref(x, W, None, n, P)
+    assert (ref * 2.0 ** 19 == np.round(ref * 2.0 ** 19)).all() and ref.max() < 32            # exact in f32
+    tol = 2.0 ** -23 * mag
+    for drop in kept_pairs(P):
+        less, _ = split_conv_ref(x, W, None, n, P, pairs=[q for q in kept_pairs(P) if q != drop])
+        assert (np.abs(less - ref) > 8 * tol).all(), drop
+    y = ops.gather_gemm_split(ops.split_bf16(torch.from_numpy(x).to(device), P),
+                              ops.pack_w_split(torch.from_numpy(W).to(device), P), 1, cout, None, n)
+    err = np.abs(y.double().cpu().numpy() - ref)
+    assert (err <= tol).all(), float((err / tol).max())
+
+
+# ------------------------------------------------------------------------------------------------ 4. the transposed pack
+@pytest.mark.parametrize("P", [2, 3])
+@pytest.mark.parametrize("shape", [(64, 96), (96, 96), (32, 48)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_transposed_pack_gives_the_input_gradient(device, tables, P, shape):
+    """dx = the float64 VJP of the split oracle (dy and W as planes, kept products) on an asymmetric scene: the kernel
+    over the same table with the mirrored-transpose pack, operand widths cout -> cin."""
+    from unscene3d_amd import ops
+    cin, cout = shape
+    n = 600
+    nbr_np = tables[n]
+    assert not np.array_equal(nbr_np, nbr_np[::-1])                        # the scene is not its own mirror image
+    g = torch.Generator().manual_seed(77 + P + cin)
+    dy = torch.randn((n, cout), generator=g)
+    W = torch.randn((27, cin, cout), generator=g) / (27 * cout) ** 0.5
+    dx = ops.gather_gemm_split(ops.split_bf16(dy.to(device), P), ops.pack_w_split(W.to(device), P, transposed=True), 27,
+                               cin, torch.from_numpy(nbr_np).to(device), n)
+    ref, mag = split_conv_vjp_ref(dy.numpy(), W.numpy(), nbr_np, n, P)
+    w = _check(dx, ref, mag, (P, shape))
+    print(f"split dgrad P={P} {cout}->{cin}: worst |err| / (2^-20 sum|dy||w|) = {w:.3f}")
+    # K = 1: the plain transpose
+    W1 = torch.randn((1, cin, cout), generator=g) / cout ** 0.5
+    dx1 = ops.gather_gemm_split(ops.split_bf16(dy.to(device), P), ops.pack_w_split(W1.to(device), P, transposed=True), 1,
+                                cin, None, n)
+    ref1, mag1 = split_conv_vjp_ref(dy.numpy(), W1.numpy(), None, n, P)
+    _check(dx1, ref1, mag1, (P, shape, "K=1"))
+
+
+# ------------------------------------------------------------------------------------------------------- 5. unit level
+TRUNC = {2: 3 * 2.0 ** -16, 3: 2.0 ** -23}          # dropped plane products, per product, relative to |x||w|
+
+
+def _unit_case(device, cin, cout, with_res, seed):
+    from unscene3d_amd import MinkowskiEngine as ME
+    n = 600
+    rng = np.random.default_rng(seed)
+    side = 13
+    cells = rng.choice(side ** 3, size=n, replace=False)
+    xyz = np.stack([cells // (side * side), (cells // side) % side, cells % side], 1)
+    coords4 = np.concatenate([np.zeros((n, 1), np.int64), xyz], 1).astype(np.int32)
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn((n, cin), generator=g).to(device)
+    st = ME.SparseTensor(features=x, coordinates=torch.from_numpy(coords4).to(device), device=device)
+    kmap = st.coordinate_manager.kmap_cube(st._ts(), 3)
+    W = (torch.randn((27, cin, cout), generator=g) / (27 * cin) ** 0.5).to(device)
+    bn = torch.nn.BatchNorm1d(cout, momentum=0.02).to(device).train()
+    with torch.no_grad():
+        bn.weight.copy_(torch.rand(cout, generator=g) + 0.5)
+        bn.bias.copy_(torch.randn(cout, generator=g) * 0.1)
+    res = torch.randn((n, cout), generator=g).to(device) if with_res else None
+    dout = torch.randn((n, cout), generator=g).to(device)
+    return st, x, kmap, W, bn, res, dout
+
+
+def _unit_fwd_bwd(units, x, W, bn, kmap, res, dout, planes, fwd=None):
+    """Per-operator path (units.unit_forward / unit_backward).  fwd: reuse this (y, stats, out) in the backward, so that
+    two precisions are fed the same x and dy."""
+    y, stats, out = units.unit_forward(x, W, bn, kmap, units.SAME, res, True, None, planes)
+    by, bstats, bout = (y, stats, out) if fwd is None else fwd
+    Wp, gp, bp = torch.nn.Parameter(W), torch.nn.Parameter(bn.weight.detach().clone()), torch.nn.Parameter(bn.bias.detach().clone())
+    dy = torch.empty_like(by)
+    dx, dres, dW, dg, db = units.unit_backward(x, W, bn, kmap, units.SAME, by, bstats, bout, dout, dy, res is not None, None,
+                                               False, True, Wp, gp, bp, planes=planes)
+    return dict(y=y, stats=stats, out=out, dy=dy, dx=dx, dres=dres, dW=dW, dg=dg, db=db)
+
+
+def _conv_mag(src, W, nbr, transposed):
+    """sum |src||w| of the conv (or of its input gradient over the mirrored transpose), float64 on the device."""
+    K = W.shape[0]
+    mag = torch.zeros((src.shape[0], W.shape[1] if transposed else W.shape[2]), dtype=torch.float64, device=src.device)
+    a = src.double().abs()
+    for k in range(K):
+        rows = nbr[k].long()
+        m = rows >= 0
+        Wk = W[K - 1 - k].double().abs().t() if transposed else W[k].double().abs()
+        mag[m] += a[rows[m]] @ Wk
+    return mag
+
+
+@pytest.mark.parametrize("with_res", [False, True], ids=["plain", "residual"])
+@pytest.mark.parametrize("shape", [(48, 96), (96, 96)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("P", [2, 3])
+def test_unit_forward_backward_against_the_f32_unit(device, P, shape, with_res):
+    """600 rows (tile-form batch norm, which finds the conv output finished), training-mode BN.  The conv output and dx
+    are within (dropped products + twice the f32 accumulation allowance) * sum |x||w| of the f32 unit's, element by
+    element; the batch norm / residual / ReLU after the conv is the unit's f32 one (checked against float64 on the split
+    conv output); dW equals the f32 unit's bit for bit when both are fed the same x and dy.  The 48 -> 96 unit's input
+    gradient is not covered by the kernel (48 output columns) and runs in f32: bit-equal there."""
+    from unscene3d_amd import units
+    cin, cout = shape
+    st, x, kmap, W, bn, res, dout = _unit_case(device, cin, cout, with_res, 31 + cin + P)
+    nbr = kmap.keep[0]
+    f32 = _unit_fwd_bwd(units, x, W, bn, kmap, res, dout, 0)
+    sp = _unit_fwd_bwd(units, x, W, bn, kmap, res, dout, P, fwd=(f32["y"], f32["stats"], f32["out"]))
+    lim = (TRUNC[P] + 2 * BOUND) * _conv_mag(x, W, nbr, False)
+    err = (sp["y"].double() - f32["y"].double()).abs()
+    assert bool((err <= lim).all()) and bool((err > 0).any()), float((err / lim).max())
+    print(f"unit P={P} {cin}->{cout}: forward worst fraction of the bound {float((err / lim).max()):.3f}")
+    # BN + residual + ReLU of the split conv output, float64
+    y64 = sp["y"].double()
+    mean, var = y64.mean(0), y64.var(0, unbiased=False)
+    o64 = (y64 - mean) / (var + bn.eps).sqrt() * bn.weight.detach().double() + bn.bias.detach().double()
+    if res is not None:
+        o64 = o64 + res.double()
+    o64 = o64.clamp(min=0)
+    assert float((sp["out"].double() - o64).abs().max()) <= 1e-5 * float(o64.abs().max())
+    # backward, fed the f32 forward's y / stats / out: the same dy -> dW to the bit, dx within the bound
+    assert torch.equal(sp["dy"], f32["dy"])
+    assert torch.equal(sp["dW"], f32["dW"]) and torch.equal(sp["dg"], f32["dg"]) and torch.equal(sp["db"], f32["db"])
+    if with_res:
+        assert torch.equal(sp["dres"], f32["dres"])
+    if cin % 32:
+        assert torch.equal(sp["dx"], f32["dx"])
+    else:
+        limx = (TRUNC[P] + 2 * BOUND) * _conv_mag(f32["dy"], W, nbr, True)
+        errx = (sp["dx"].double() - f32["dx"].double()).abs()
+        assert bool((errx <= limx).all()) and bool((errx > 0).any()), float((errx / limx).max())
+        print(f"unit P={P} {cin}->{cout}: dx worst fraction of the bound {float((errx / limx).max()):.3f}")
+
+
+def _program_unit(device, x, W, bn, kmap, res, dout, planes, dx_acc_init=None):
+    """The same unit as a two-step program (usc_program_run), forward then backward."""
+    import ctypes as C
+
+    from unscene3d_amd import ops, units
+    from unscene3d_amd._lib import STEP_UNIT_BWD, STEP_UNIT_FWD, Step, check, lib
+    n, cin = x.shape
+    cout = W.shape[2]
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=device)  # noqa: E731
+    y, out, stats, dy, dres, dx = new(n, cout), new(n, cout), new(4, cout), new(n, cout), new(n, cout), new(n, cin)
+    dW, dg, db = new(*W.shape), new(cout), new(cout)
+    if dx_acc_init is not None:
+        dx.copy_(dx_acc_init)
+    bdesc, _ = units._bn_desc(bn, True)
+    steps = (Step * 2)()
+    for st, op in zip(steps, (STEP_UNIT_FWD, STEP_UNIT_BWD)):
+        st.op, st.kind, st.cin, st.cout, st.relu, st.split_planes = op, units.SAME, cin, cout, 1, planes
+        st.map, st.bn = C.addressof(kmap.struct), C.addressof(bdesc)
+        st.x, st.W, st.y, st.stats, st.out = x.data_ptr(), W.data_ptr(), y.data_ptr(), stats.data_ptr(), out.data_ptr()
+        st.residual = None if res is None else res.data_ptr()
+    b = steps[1]
+    b.dout, b.dy, b.dres, b.dx = dout.data_ptr(), dy.data_ptr(), None if res is None else dres.data_ptr(), dx.data_ptr()
+    b.dx_accumulate = int(dx_acc_init is not None)
+    b.dW, b.dgamma, b.dbeta = dW.data_ptr(), dg.data_ptr(), db.data_ptr()
+    ws = units.workspace(lib.usc_program_ws_bytes(steps, 2), device)
+    check(lib.usc_program_run(steps, 0, 1, ws.data_ptr(), ws.numel(), ops._stream()), "usc_program_run")
+    check(lib.usc_program_run(steps, 1, 2, ws.data_ptr(), ws.numel(), ops._stream()), "usc_program_run")
+    torch.cuda.synchronize()
+    return dict(y=y, stats=stats, out=out, dy=dy, dx=dx, dres=dres if res is not None else None, dW=dW, dg=dg, db=db)
+
+
+@pytest.mark.parametrize("with_res", [False, True], ids=["plain", "residual"])
+@pytest.mark.parametrize("shape", [(48, 96), (96, 96)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("P", [2, 3])
+def test_unit_program_path_equals_the_per_operator_path(device, P, shape, with_res):
+    from unscene3d_amd import units
+    cin, cout = shape
+    st, x, kmap, W, bn, res, dout = _unit_case(device, cin, cout, with_res, 57 + cout + P)
+    a = _unit_fwd_bwd(units, x, W, bn, kmap, res, dout, P)
+    b = _program_unit(device, x, W, bn, kmap, res, dout, P)
+    for k in ("y", "stats", "out", "dy", "dx", "dW", "dg", "db") + (("dres",) if with_res else ()):
+        assert torch.equal(a[k], b[k]), k
+    # dx_accumulate is honoured: dx = init + the same product, to rounding of one addition
+    init = torch.randn_like(a["dx"])
+    c = _program_unit(device, x, W, bn, kmap, res, dout, P, dx_acc_init=init)
+    tol = 2.0 ** -22 * (init.abs() + a["dx"].abs()) + 1e-30
+    assert bool(((c["dx"] - (init + a["dx"])).abs() <= tol).all())
+
+
+@pytest.mark.parametrize("P", [2, 3])
+def test_unit_short_workspace_is_an_error_and_nothing_past_it_is_written(device, P):
+    from unscene3d_amd import ops, units
+    from unscene3d_amd._lib import last_error, lib
+    cin, cout = 96, 96
+    st, x, kmap, W, bn, res, dout = _unit_case(device, cin, cout, False, 3)
+    need = lib.usc_unit_split_ws_bytes(kmap.ref, units.SAME, cin, cout, P)
+    assert need > lib.usc_unit_ws_bytes(kmap.ref, units.SAME, cin, cout)
+    assert lib.usc_unit_split_ws_bytes(kmap.ref, units.DOWN, cin, cout, P) == -1
+    assert lib.usc_unit_split_ws_bytes(kmap.ref, units.SAME, cin, cout, 4) == -1
+    n = x.shape[0]
+    y, out, stats = torch.empty((n, cout), device=device), torch.empty((n, cout), device=device), torch.empty((4, cout), device=device)
+    dy, dx = torch.empty((n, cout), device=device), torch.empty((n, cin), device=device)
+    dW, dg, db = torch.empty_like(W), torch.empty(cout, device=device), torch.empty(cout, device=device)
+    _, bref = units._bn_desc(bn, True)
+    planes_bytes = n * cin * P * 2
+    for short in (4096, planes_bytes + 4096, planes_bytes + P * 27 * cin * cout * 2 - 512):
+        buf = torch.full((need + 4096,), 0x5A, dtype=torch.uint8, device=device)
+        rc = lib.usc_conv_bn_act_forward_split(kmap.ref, units.SAME, x.data_ptr(), cin, W.data_ptr(), cout, P, bref, None, 1,
+                                               y.data_ptr(), stats.data_ptr(), out.data_ptr(), buf.data_ptr(), short,
+                                               ops._stream())
+        assert rc != 0 and "workspace too small" in last_error(), (short, last_error())
+        rc = lib.usc_conv_bn_act_backward_split(kmap.ref, units.SAME, x.data_ptr(), cin, W.data_ptr(), cout, P, bref,
+                                                y.data_ptr(), stats.data_ptr(), None, dout.data_ptr(), dy.data_ptr(), None,
+                                                dx.data_ptr(), 0, dW.data_ptr(), 0, dg.data_ptr(), db.data_ptr(), 0,
+                                                buf.data_ptr(), short, ops._stream())
+        assert rc != 0 and "workspace too small" in last_error(), (short, last_error())
+        torch.cuda.synchronize()
+        assert bool((buf[short:] == 0x5A).all()), short
+    # the stated size is enough
+    buf = torch.empty(need, dtype=torch.uint8, device=device)
+    assert lib.usc_conv_bn_act_forward_split(kmap.ref, units.SAME, x.data_ptr(), cin, W.data_ptr(), cout, P, bref, None, 1,
+                                             y.data_ptr(), stats.data_ptr(), out.data_ptr(), buf.data_ptr(), need,
+                                             ops._stream()) == 0
+    assert lib.usc_conv_bn_act_backward_split(kmap.ref, units.SAME, x.data_ptr(), cin, W.data_ptr(), cout, P, bref,
+                                              y.data_ptr(), stats.data_ptr(), None, dout.data_ptr(), dy.data_ptr(), None,
+                                              dx.data_ptr(), 0, dW.data_ptr(), 0, dg.data_ptr(), db.data_ptr(), 0,
+                                              buf.data_ptr(), need, ops._stream()) == 0
+    torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------------------------------------------------ 6. trunk
+REL_TOL = 1e-3                                       # the project's tolerance for fp32 features / losses
+
+
+def rel_err(a, b):
+    a, b = a.double().cpu(), b.double().cpu()
+    return float((a - b).norm() / b.norm().clamp(min=1e-30))
+
+
+@pytest.fixture
+def every_unit(monkeypatch):
+    """Policy constants at 0: every stride-1 K = 27 unit the kernel covers takes the split path.  -> the list the spy
+    appends the planes of every covered unit to."""
+    from unscene3d_amd import precision
+    monkeypatch.setattr(precision, "TRAIN_MIN_ROWS", 0)
+    monkeypatch.setattr(precision, "TRAIN_MIN_CIN", 0)
+    took = []
+    real = precision.train_planes
+
+    def spy(*a, **k):
+        p = real(*a, **k)
+        if p:
+            took.append(p)
+        return p
+    monkeypatch.setattr(precision, "train_planes", spy)
+    return took
+
+
+LEVEL_WEIGHTS = (0.5, 1.0, 1.5, 2.0, 0.25)
+
+
+def test_trunk_features_and_gradients_against_the_float64_oracle(device, monkeypatch, every_unit):
+    """Res16UNet34C, one ~12 k-voxel scene, forward + backward of sum_l w_l mean(level_l^2), every stride-1 K = 27 unit
+    but the 3-channel stem in split bf16.  Relative L2 of the five level outputs and of the parameter gradients against
+    the float64 oracle: bf16x3 at most 4x the f32 path's own error (computed here, against the same oracle), bf16x2 at
+    most REL_TOL.
+
+    The gradient is that of a piecewise-smooth function: every ReLU mask bit is a discrete decision, and a run that
+    decides one bit otherwise than the oracle differentiates another branch.  Measured on an MI355X on this very case, in
+    pure f32: perturbing the input colours by 1e-7 (relative) moves the features by 2e-6, flips 9 of the ~10 M mask bits
+    and moves the parameter gradients by 1.6e-4.  Against the oracle's own masks: f32 3 bits and 5.04e-6, bf16x3 7 bits and
+    1.95e-4, bf16x2 128 bits and 1.30e-2; with the run's masks imposed 4.97e-6, 5.92e-6, 1.19e-4 (what a bit costs
+    depends on the gradient that happens to arrive there).  So, as tests/test_gpu_step_parity.py does with its discrete
+    decisions, the test first holds each run's masks against the oracle's own (at most 1e-4 of the bits differ, and only
+    where the oracle's own value is within REL_TOL of zero on the layer's scale: decisions the tolerance leaves open), then
+    compares each split run with the float64 gradient under the run's masks.  The yardstick stays the f32 path against the
+    unmodified oracle; features are held to their gates against the unmodified oracle too.  Both sets of figures are
+    printed (DESIGN.md 3.21 has them).  The per-block path is used because it exposes every unit's output; it runs the
+    same C function per unit as the step program (test_unit_program_path_equals_the_per_operator_path)."""
+    import oracle.res16unet_ref as M
+    from types import SimpleNamespace as NS
+
+    from unscene3d_amd import MinkowskiEngine as ME
+    from unscene3d_amd import precision, program, training_precision, units
+    from unscene3d_amd.models.res16unet import Res16UNet34C
+    from unscene3d_amd.synthetic import make_scene
+    sc = make_scene(2301, target_voxels=12_000, tol=0.05)
+    ec = R.voxel_floor(sc["xyz"], 0.02)
+    eu, _ = R.sparse_quantize(ec)
+    coords4, feats = R.sparse_collate([ec[eu]], [sc["colors"][eu]])
+    torch.manual_seed(6)
+    model = Res16UNet34C(3, 20, NS(bn_momentum=0.02, conv1_kernel_size=3, dilations=[1, 1, 1, 1]), out_fpn=True)
+    model = model.to(device).train()
+    state = {k: v.clone() for k, v in model.state_dict().items()}
+    precision.FALLBACKS.clear()
+    monkeypatch.setattr(program, "ENABLED", False)
+    masks = []
+    real_forward = units.unit_forward
+
+    def recording_forward(x, W3, bn, kmap, kind, residual, relu, *rest):
+        r = real_forward(x, W3, bn, kmap, kind, residual, relu, *rest)
+        if relu:
+            masks.append((r[2] > 0).cpu())
+        return r
+    monkeypatch.setattr(units, "unit_forward", recording_forward)
+    res = {}
+    for prec in ("f32", "bf16x2", "bf16x3"):
+        model.load_state_dict(state)
+        for p in model.parameters():
+            p.grad = torch.zeros_like(p)
+        n0 = len(every_unit)
+        del masks[:]
+        x = ME.SparseTensor(features=torch.from_numpy(feats).to(device), coordinates=torch.from_numpy(coords4).to(device),
+                            device=device)
+        with training_precision(prec):
+            _, fmaps = model(x)
+        loss = sum(w * f.F.square().mean() for w, f in zip(LEVEL_WEIGHTS, fmaps))
+        loss.backward()
+        torch.cuda.synchronize()
+        took = every_unit[n0:]
+        assert (len(took) == 0) if prec == "f32" else (len(took) >= 32 and set(took) == {int(prec[-1])}), (prec, took)
+        res[prec] = ([f.F.detach().cpu() for f in fmaps],
+                     {n: p.grad.detach().cpu() for n, p in model.named_parameters() if not n.startswith("final.")},
+                     list(masks))
+    assert not precision.FALLBACKS
+
+    def oracle(run_masks=None):
+        """float64 forward + backward.  run_masks None: the oracle as it is; -> also its own ReLU masks and what went
+        into each ReLU.  Else the given masks are imposed, in the oracle's own order of ReLUs (stem, each strided conv, per
+        block conv1 then the block's output) — the order of the device's units that apply a ReLU."""
+        sd = {k: (v.detach().cpu().double().requires_grad_(True) if v.dtype.is_floating_point else v.detach().cpu())
+              for k, v in state.items()}
+        it = iter(run_masks or ())
+        own, pre = [], []
+        real_relu = torch.relu
+
+        def relu(t):
+            if run_masks is None:
+                pre.append(t.detach())
+                own.append(t.detach() > 0)
+                return real_relu(t)
+            m = next(it)
+            assert m.shape == t.shape, (m.shape, t.shape)
+            return t * m.to(t.dtype)
+        torch.relu = relu
+        try:
+            _, levels = M.res16unet_forward(sd, M.Pyramid(coords4), torch.from_numpy(feats).double(), Res16UNet34C.LAYERS)
+        finally:
+            torch.relu = real_relu
+        assert next(it, None) is None                   # every recorded mask was used
+        sum(w * f.square().mean() for w, f in zip(LEVEL_WEIGHTS, levels)).backward()
+        return [f.detach() for f in levels], {k: v.grad for k, v in sd.items() if v.dtype.is_floating_point}, own, pre
+
+    def errors(lv, grads, levels, g):
+        names = [n for n in grads if g.get(n) is not None and float(g[n].norm()) > 1e-12]
+        assert len(names) > 100
+        return [rel_err(a, b) for a, b in zip(lv, levels)] + \
+               [rel_err(torch.cat([grads[n].reshape(-1) for n in names]), torch.cat([g[n].reshape(-1) for n in names]))]
+
+    levels0, g0, own, pre = oracle()
+    bits = sum(m.numel() for m in own)
+    assert len(own) == len(res["f32"][2]) and bits > 5_000_000
+    plain, masked = {}, {}
+    for prec, (lv, grads, run_masks) in res.items():
+        # the run's discrete decisions against the oracle's own: few, and only where the oracle itself is at zero within
+        # the project's feature tolerance (a wrongly paired or wrongly ordered mask list would differ in ~half the bits)
+        flips, worst = 0, 0.0
+        for m_run, m_own, t in zip(run_masks, own, pre):
+            assert m_run.shape == m_own.shape
+            d = m_run != m_own
+            if bool(d.any()):
+                flips += int(d.sum())
+                worst = max(worst, float(t[d].abs().max() / t.square().mean().sqrt()))
+        assert flips <= 1e-4 * bits, (prec, flips, bits)
+        assert worst <= REL_TOL, (prec, worst)
+        plain[prec] = errors(lv, grads, levels0, g0)
+        levels, g, _, _ = oracle(run_masks)
+        masked[prec] = errors(lv, grads, levels, g)
+        print(f"trunk {prec}: {flips} of {bits} ReLU mask bits differ from the float64 oracle's own, largest oracle value "
+              f"there {worst:.1e} of the layer's rms")
+        for tag, e in (("oracle's own masks", plain[prec]), ("the run's masks   ", masked[prec])):
+            print(f"   rel L2 vs float64 with {tag}: levels s16..s1 " + " ".join(f"{v:.2e}" for v in e[:5]) +
+                  f", parameter gradients {e[5]:.2e}")
+    # the yardstick is the f32 path against the oracle as it is (the issue's words); each split run against the float64
+    # gradient of the function it evaluated
+    for j, (e32, e2, e3) in enumerate(zip(plain["f32"], masked["bf16x2"], masked["bf16x3"])):
+        assert e3 <= 4 * e32, (j, e3, e32)
+        assert e2 <= REL_TOL, (j, e2)
+    for j in range(5):                                  # the features need no imposed masks
+        assert plain["bf16x3"][j] <= 4 * plain["f32"][j] and plain["bf16x2"][j] <= REL_TOL
+    # the split path was really taken: its bits differ from the f32 path's
+    assert not torch.equal(res["bf16x3"][0][-1], res["f32"][0][-1])
+
+
+# ---------------------------------------------------------------------------------------------------- 7. training step
+def test_training_step_meets_the_oracle_under_bf16x3(device, monkeypatch, every_unit):
+    """The 2 x 12 k-voxel step of tests/test_gpu_step_parity.py (collate -> Mask3D forward -> Hungarian -> 52 losses ->
+    backward against the CPU restatement), unchanged and at its own loss and gradient thresholds, with
+    general.train_precision=bf16x3 and every covered unit in split bf16."""
+    import test_gpu_step_parity as SP
+    real = SP._setup
+    monkeypatch.setattr(SP, "_setup", lambda device, spatial_sort, overrides=():
+                        real(device, spatial_sort, (*overrides, "general.train_precision=bf16x3")))
+    SP.test_config3_full_mask3d_step_loss_and_gradient_parity(device, 5)
+    assert len(every_unit) >= 32 and set(every_unit) == {3}
+
+
+# --------------------------------------------------------------------------------------------- 8, 9. the training loop
+def _loop_run(device, steps, voxels, early, overrides=()):
+    """`steps` steps of TrainLoop as tests/train_loop_child.py builds it (bench.py's config, seed and scene)."""
+    import train_loop_child as child
+    from unscene3d_amd.config import apply_overrides
+    from unscene3d_amd.trainer import TrainLoop
+    cfg, module = child.build()
+    apply_overrides(cfg, list(overrides))
+    assert module.config is cfg
+    loop = TrainLoop(module, cfg, child.scene_list(1, voxels), device=device, early_optimizer=early, total_steps=100000,
+                     steady_after=0, resident=True, seed=7)
+    try:
+        totals, vecs = [], []
+        for _ in range(steps):
+            total = loop.step()
+            assert total is not None
+            totals.append(total.clone())
+            vecs.append(loop.last_losses.clone())
+        torch.cuda.synchronize()
+        ps, gs = child.sample_like_bench(loop.params)
+        return dict(params=loop.optimizer.flat_param.cpu().numpy().copy(), exp_avg=loop.optimizer.exp_avg.cpu().numpy().copy(),
+                    exp_avg_sq=loop.optimizer.exp_avg_sq.cpu().numpy().copy(), totals=torch.stack(totals).cpu().numpy(),
+                    losses=torch.stack(vecs).cpu().numpy(), params_sample=ps, early=loop.early)
+    finally:
+        loop.close()
+
+
+def test_early_optimizer_changes_no_bit_under_bf16x3(device, every_unit):
+    """Three TrainLoop steps with the optimizer inside the backward pass (parameters written while later units' input
+    gradients are still to come) and with one launch at the end of the step: the same parameters and moments, bit for
+    bit — the equality tests/test_gpu_train_loop.py holds the f32 loop to.  A weight pack that read its weights after
+    an in-backward optimizer write would break it."""
+    ov = ("general.train_precision=bf16x3",)
+    a = _loop_run(device, 3, 12_000, True, ov)
+    n_a = len(every_unit)
+    b = _loop_run(device, 3, 12_000, False, ov)
+    assert a["early"] == "final" and b["early"] is None
+    assert n_a >= 3 * 32 and len(every_unit) == 2 * n_a and set(every_unit) == {3}
+    for k in ("params", "exp_avg", "exp_avg_sq", "totals", "losses"):
+        assert a[k].shape == b[k].shape and np.array_equal(a[k], b[k]), k
+    assert np.isfinite(a["totals"]).all() and not np.array_equal(a["totals"][0], a["totals"][2])
+
+
+def test_default_precision_is_unchanged(device, monkeypatch):
+    """train_precision unset: nothing falls back, and losses and the seeded parameter sample of bench.py are bit-equal
+    to a run with the policy constants at "nothing covered" — and to an opted-in run in which no unit is covered."""
+    from unscene3d_amd import precision
+    precision.FALLBACKS.clear()
+    a = _loop_run(device, 2, 8_000, True)
+    assert not precision.FALLBACKS and precision.current_training() == "f32"
+    monkeypatch.setattr(precision, "TRAIN_MIN_ROWS", 1 << 62)
+    monkeypatch.setattr(precision, "TRAIN_MIN_CIN", 1 << 30)
+    b = _loop_run(device, 2, 8_000, True)
+    c = _loop_run(device, 2, 8_000, True, ("general.train_precision=bf16x3",))
+    for k in ("totals", "losses", "params_sample", "params"):
+        assert np.array_equal(a[k], b[k]) and np.array_equal(a[k], c[k]), k
+    assert not precision.FALLBACKS

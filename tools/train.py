@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--dist-backend", default="nccl")
     ap.add_argument("--resume", default=None, metavar="PATH")
     ap.add_argument("--supervised", action="store_true", help="ground-truth label tables through VoxelizeCollate")
+    ap.add_argument("--train-precision", default="f32", choices=("f32", "bf16x2", "bf16x3"),
+                    help="general.train_precision: the trunk's stride-1 convolutions in f32 or split bf16")
     ap.add_argument("--out", default=None, metavar="DIR", help="write DIR/last.ckpt at the end")
     a = ap.parse_args()
 
@@ -60,7 +62,7 @@ def main():
                                 **({"device_id": dev} if a.dist_backend == "nccl" else {}))
 
     overrides = ["general.num_targets=19", "loss.device_max_targets=128"] if a.supervised else ["general.num_targets=3"]
-    cfg = apply_overrides(default_config(), overrides + [f"data.batch_size={world}"])
+    cfg = apply_overrides(default_config(), overrides + [f"data.batch_size={world}", f"general.train_precision={a.train_precision}"])
     dataset = SyntheticLabelledDataset if a.supervised else SyntheticFreeMaskDataset
     torch.manual_seed(1234)
     module = InstanceSegmentation(cfg).to(dev).train()
@@ -102,6 +104,7 @@ def main():
                 "ms_per_step": (1e3 * dt / timed) if timed > 0 else None,
                 "ms_per_step_p10_p50_p90": ([round(float(np.percentile(per, q)), 3) for q in (10, 50, 90)] if per else None),
                 "early_optimizer": loop.early, "supervised": bool(a.supervised), "world": world,
+                "train_precision": a.train_precision,
                 "force_dist": bool(a.force_dist),
                 "buckets_started_during_backward": loop.reducer.started_during_backward if loop.reducer else None,
                 "losses_step": rep["step"] if rep else None, "losses": rep["losses"] if rep else None,

@@ -49,7 +49,8 @@ class Step(C.Structure):
                 ("map", _p), ("bn", _p),          # (addresses of a KMap / BNDesc: C.addressof)
                 ("x", _p), ("W", _p), ("residual", _p), ("y", _p), ("stats", _p), ("out", _p),
                 ("dout", _p), ("dy", _p), ("dres", _p), ("dx", _p), ("dW", _p), ("dgamma", _p), ("dbeta", _p),
-                ("a", _p), ("b", _p), ("dst", _p), ("dst2", _p), ("n", _i64), ("ca", _i32), ("cb", _i32)]
+                ("a", _p), ("b", _p), ("dst", _p), ("dst2", _p), ("n", _i64), ("ca", _i32), ("cb", _i32),
+                ("split_planes", _i32), ("reserved", _i32)]
 
 
 _sp = C.POINTER(Step)
@@ -94,6 +95,11 @@ SIGNATURES = {
     "usc_spconv_pack_w_bf16": (C.c_int, [_p, _i32, _i32, _i32, _p, _p]),
     "usc_spconv_gather_gemm_bf16_ws_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "usc_spconv_gather_gemm_bf16": (C.c_int, [_p, _i64, _i32, _p, _i32, _i32, _p, _i64, _p, _p, _i32, _p, _i64, _p]),
+    "usc_split_bf16_rows": (C.c_int, [_p, _i64, _i32, _i32, _p, _p]),
+    "usc_split_bf16": (C.c_int, [_p, _i64, _i32, _p, _p]),
+    "usc_spconv_pack_w_split": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    "usc_spconv_gather_gemm_split_ws_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32]),
+    "usc_spconv_gather_gemm_split": (C.c_int, [_p, _i64, _i32, _p, _i32, _i32, _i32, _p, _i64, _p, _p, _i32, _p, _i64, _p]),
     "usc_spconv_wgrad_ws_bytes": (_i64, [_i32, _i32, _i32]),
     "usc_spconv_wgrad": (C.c_int, [_p, _i32, _p, _i32, _i32, _p, _p, _p, _i64, _p, _i32, _p, _i64, _p]),
     "usc_spconv_wgrad_ws_bytes_rows": (_i64, [_i32, _i32, _i32, _i64]),
@@ -121,6 +127,10 @@ SIGNATURES = {
     "usc_conv_bn_act_forward": (C.c_int, [_kp, _i32, _p, _i32, _p, _i32, _bp, _p, _i32, _p, _p, _p, _p, _i64, _p]),
     "usc_unit_bf16_ws_bytes": (_i64, [_kp, _i32, _i32, _i32]),
     "usc_conv_bn_act_forward_bf16": (C.c_int, [_kp, _i32, _p, _i32, _p, _i32, _bp, _p, _i32, _p, _p, _p, _p, _i64, _p]),
+    "usc_unit_split_ws_bytes": (_i64, [_kp, _i32, _i32, _i32, _i32]),
+    "usc_conv_bn_act_forward_split": (C.c_int, [_kp, _i32, _p, _i32, _p, _i32, _i32, _bp, _p, _i32, _p, _p, _p, _p, _i64, _p]),
+    "usc_conv_bn_act_backward_split": (C.c_int, [_kp, _i32, _p, _i32, _p, _i32, _i32, _bp, _p, _p, _p, _p, _p, _p, _p, _i32, _p,
+                                                 _i32, _p, _p, _i32, _p, _i64, _p]),
     "usc_conv_bn_act_backward": (C.c_int, [_kp, _i32, _p, _i32, _p, _i32, _bp, _p, _p, _p, _p, _p, _p, _p, _i32, _p,
                                            _i32, _p, _p, _i32, _p, _i64, _p]),
     "usc_colstats_ws_bytes": (_i64, [_i64, _i32]),

@@ -25,8 +25,11 @@ def default_config():
                     "filter_out_instances": False, "scores_threshold": 0.1, "iou_threshold": 0.66,
                     "topk_per_image": 100, "save_for_freemask": False, "save_dir": "saved",
                     # trunk convolutions of eval_step / validation_step / the pseudo-mask 3D encoder: "f32" or "bf16"
-                    # (unscene3d_amd.inference_precision; training always runs f32)
-                    "eval_precision": "f32"},
+                    # (unscene3d_amd.inference_precision; never used with autograd)
+                    "eval_precision": "f32",
+                    # stride-1 trunk convolutions of training_step: "f32", or split bf16 at f32-grade accuracy,
+                    # "bf16x2" / "bf16x3" (unscene3d_amd.training_precision)
+                    "train_precision": "f32"},
         "data": {"voxel_size": 0.02, "in_channels": 3, "num_labels": 20, "add_raw_coordinates": True,
                  "add_colors": True, "add_normals": False, "ignore_label": 255, "batch_size": 8,
                  "test_mode": "validation"},          # conf/data/indoor.yaml:9 ("test": eval_step skips the criterion)
@@ -64,6 +67,9 @@ def apply_overrides(cfg, overrides):
         setattr(node, parts[-1], val)
     if getattr(cfg.general, "eval_precision", "f32") not in ("f32", "bf16"):
         raise ValueError(f"general.eval_precision must be 'f32' or 'bf16', not {cfg.general.eval_precision!r}")
+    if getattr(cfg.general, "train_precision", "f32") not in ("f32", "bf16x2", "bf16x3"):
+        raise ValueError("general.train_precision must be 'f32', 'bf16x2' or 'bf16x3', not "
+                         f"{cfg.general.train_precision!r}")
     # interpolations of the reference YAML (${general.num_targets}, ${general.train_on_segments}, …)
     cfg.model.num_classes = cfg.general.num_targets
     cfg.loss.num_classes = cfg.general.num_targets

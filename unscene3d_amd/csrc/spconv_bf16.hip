@@ -18,23 +18,12 @@
 // Reference: MinkowskiEngine 0.5.4 MinkowskiConvolution / MinkowskiConvolutionTranspose forward
 // (src/convolution_kernel.cu, models/res16unet.py:224-297) — under the opt-in inference precision only.
 #include "common.h"
+#include "bf16_frag.h"
 
 namespace usc {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-constexpr int kRowTiles = 2;            // 32-row tiles per wave
-constexpr int kBlockRows = 4 * 32 * kRowTiles;
 constexpr int kChunk = 4;               // 16-channel steps of weights staged in LDS at a time
-
-// round to nearest even; NaN stays a (quiet) NaN
-__device__ inline uint16_t f32_to_bf16_rne(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
 
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float4* __restrict__ in, uint2* __restrict__ out, int64_t n4) {
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n4; e += (int64_t)gridDim.x * 256) {
@@ -170,13 +159,6 @@ __global__ __launch_bounds__(256) void gather_gemm_bf16_kernel(const uint16_t* _
         }
       }
     }
-}
-
-// 32-column tiles per workgroup column group: the widest of 3, 2, 1 that divides cout / 32 (four tiles, 128 accumulator
-// registers, leave one wave per SIMD)
-inline int col_tiles(int cout) {
-  const int T = cout / 32;
-  return T % 3 == 0 ? 3 : T % 2 == 0 ? 2 : 1;
 }
 
 }  // namespace

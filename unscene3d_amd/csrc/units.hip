@@ -280,6 +280,36 @@ int usc_wgrad_lane_join(usc_stream_t s) {
   return USC_OK;
 }
 
+// ---- split-bf16 precision of a stride-1 unit (spconv_split.hip) --------------------------------------------------------
+// the input gradient is the same product over the mirrored transpose: operand shape cout -> cin
+static bool split_dgrad_ok(const usc_kmap* m, int cin, int cout, int planes) {
+  return usc_spconv_gather_gemm_split_ws_bytes(m->n_in, cout, cin, m->K, planes) >= 0;
+}
+// scratch of one split product: the operand's planes, the packed weight planes, the kernel's own
+static int64_t split_gemm_ws(const usc_kmap* m, int64_t n_src, int c_src, int c_dst, int planes) {
+  const int64_t g = usc_spconv_gather_gemm_split_ws_bytes(m->n_out, c_src, c_dst, m->K, planes);
+  return align_up(n_src * c_src * planes * 2, 256) + align_up((int64_t)planes * m->K * c_src * c_dst * 2, 256) +
+         align_up(g > 0 ? g : 16, 256);
+}
+// dst[o] (+)= sum_k sum_{i+j<P} src_i[nbr[k][o]] W_j[k]   (transposed: over the mirrored transpose of W f32[K][cin][cout],
+// src has cout channels and dst cin).  src is split and W packed on every call, on the caller's stream.
+static int split_gemm(const usc_kmap* m, const float* src, int64_t n_src, int c_src, const float* W, int c_dst, int64_t n_dst,
+                      int planes, int transposed, float* dst, int accumulate, WsCursor cur, usc_stream_t s, const char* who) {
+  const int K = m->K;
+  const int64_t gb = usc_spconv_gather_gemm_split_ws_bytes(n_dst, c_src, c_dst, K, planes);
+  USC_REQUIRE(gb >= 0, "%s: shape not covered by the split kernel (P=%d, K=%d, %d -> %d channels)", who, planes, K, c_src, c_dst);
+  uint16_t* xs = (uint16_t*)cur.take(n_src * c_src * planes * 2);
+  uint16_t* wp = (uint16_t*)cur.take((int64_t)planes * K * c_src * c_dst * 2);
+  void* gws = gb > 0 ? cur.take(gb) : nullptr;
+  USC_REQUIRE(xs && wp && (gb == 0 || gws), "%s: workspace too small for the split precision (usc_unit_split_ws_bytes)", who);
+  int rc = usc_split_bf16_rows(src, n_src, c_src, planes, xs, s);
+  if (rc) return rc;
+  rc = transposed ? usc_spconv_pack_w_split(W, K, c_dst, c_src, planes, 1, wp, s)
+                  : usc_spconv_pack_w_split(W, K, c_src, c_dst, planes, 0, wp, s);
+  if (rc) return rc;
+  return usc_spconv_gather_gemm_split(xs, n_src, c_src, wp, K, c_dst, planes, m->nbr, n_dst, nullptr, dst, accumulate, gws, gb, s);
+}
+
 static void conv_ws_parts(const usc_kmap* m, int kind, int cin, int cout, int64_t* fwd, int64_t* dgrad, int64_t* wg) {
   const int K = m->K;
   const ConvShape sh = conv_shape(m, kind);
@@ -358,7 +388,7 @@ static bool tile_rows_ok(int64_t n, int c) { return tile_form_on() && n <= usc_b
 
 static int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
                               const float* dy, float* dx, int32_t dx_accumulate, float* dW, int32_t dW_accumulate, void* ws,
-                              int64_t ws_bytes, usc_stream_t s, Pending* out);
+                              int64_t ws_bytes, usc_stream_t s, Pending* out, int planes = 0);
 
 int usc_conv_backward(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
                       const float* dy, float* dx, int32_t dx_accumulate, float* dW, int32_t dW_accumulate, void* ws,
@@ -368,7 +398,7 @@ int usc_conv_backward(const usc_kmap* m, int32_t kind, const float* x, int32_t c
 
 static int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
                               const float* dy, float* dx, int32_t dx_accumulate, float* dW, int32_t dW_accumulate, void* ws,
-                              int64_t ws_bytes, usc_stream_t s, Pending* out) {
+                              int64_t ws_bytes, usc_stream_t s, Pending* out, int planes) {
   if (out) *out = Pending{};
   int rc = check_map(m, kind, cin, cout, "usc_conv_backward");
   if (rc) return rc;
@@ -419,7 +449,9 @@ static int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, i
   // slices may stay behind only when the consumer can take them (tile-form batch norm on the input map) and nothing in
   // this call overwrites them: the weight gradient then takes its scratch behind the input gradient's region
   Slices left;
-  const bool may_defer = out && dx && tile_rows_ok(sh.n_in, cin);
+  // split precision: the input gradient on the bf16 matrix cores where the transposed shape (cout -> cin) is covered
+  const bool split_dx = planes > 0 && kind == USC_CONV_SAME && split_dgrad_ok(m, cin, cout, planes);
+  const bool may_defer = !split_dx && out && dx && tile_rows_ok(sh.n_in, cin);
   if (may_defer) {
     int64_t f_, w_;
     conv_ws_parts(m, kind, cin, cout, &f_, &dgrad_bytes, &w_);
@@ -427,7 +459,9 @@ static int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, i
   }
   Slices* want = (may_defer && dgrad_bytes > 0) ? &left : nullptr;
   if (dx && sh.n_in > 0) {
-    if (kind == USC_CONV_SAME) {
+    if (split_dx) {
+      rc = split_gemm(m, dy, sh.n_out, cout, W, cin, sh.n_in, planes, 1, dx, dx_accumulate, cur, s, "usc_conv_backward");
+    } else if (kind == USC_CONV_SAME) {
       // stride-1 map: the mirrored offset reaches the rows that read row i; transpose folded where the kernel can
       rc = table_gemm(m, m->nbr, dy, sh.n_out, cout, W, K, cin, sh.n_in, nullptr, dx, dx_accumulate, 1, cur, s, want);
     } else if (kind == USC_CONV_DOWN) {
@@ -569,7 +603,7 @@ static int unit_backward_impl(const usc_kmap* m, int32_t kind, const float* x, i
                               const usc_bn* bn, const float* y, const float* stats, const float* out_relu,
                               const float* dout, float* dy, float* dres, float* dx, int32_t dx_accumulate, float* dW,
                               int32_t dW_accumulate, float* dgamma, float* dbeta, int32_t dbn_accumulate, void* ws,
-                              int64_t ws_bytes, usc_stream_t s, Pending* in, Pending* out);
+                              int64_t ws_bytes, usc_stream_t s, Pending* in, Pending* out, int planes = 0);
 
 int usc_conv_bn_act_backward(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
                              const usc_bn* bn, const float* y, const float* stats, const float* out_relu,
@@ -586,12 +620,17 @@ static int unit_backward_impl(const usc_kmap* m, int32_t kind, const float* x, i
                               const usc_bn* bn, const float* y, const float* stats, const float* out_relu,
                               const float* dout, float* dy, float* dres, float* dx, int32_t dx_accumulate, float* dW,
                               int32_t dW_accumulate, float* dgamma, float* dbeta, int32_t dbn_accumulate, void* ws,
-                              int64_t ws_bytes, usc_stream_t s, Pending* in, Pending* out) {
+                              int64_t ws_bytes, usc_stream_t s, Pending* in, Pending* out, int planes) {
   if (out) *out = Pending{};
   USC_REQUIRE(bn && bn->c == cout, "usc_conv_bn_act_backward: batch-norm width must equal the conv's output width");
   USC_REQUIRE(y && stats && dout && dy && dgamma && dbeta && bn->gamma, "usc_conv_bn_act_backward: null pointer");
   const ConvShape sh = conv_shape(m, kind);
   if (sh.n_out == 0) return USC_OK;
+  // split precision: the planes and packs are taken behind the batch norm backward; a short scratch is refused here,
+  // before anything is launched (dy, dgamma, dbeta untouched)
+  if (planes > 0)
+    USC_REQUIRE(ws && ws_bytes >= usc_unit_split_ws_bytes(m, kind, cin, cout, planes),
+                "usc_conv_bn_act_backward_split: workspace too small (usc_unit_split_ws_bytes)");
   WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
   const int64_t sb = usc_colstats_ws_bytes(sh.n_out, cout);
   void* sws = cur.take(sb);
@@ -615,7 +654,76 @@ static int unit_backward_impl(const usc_kmap* m, int32_t kind, const float* x, i
     rc = usc_bn_backward_dx(y, dout, out_relu, mean, invstd, bn->gamma, red, red + cout, dy, dres, sh.n_out, cout, s);
     if (rc) return rc;
   }
-  return conv_backward_impl(m, kind, x, cin, W, cout, dy, dx, dx_accumulate, dW, dW_accumulate, cur.rest(), cur.left(), s, out);
+  return conv_backward_impl(m, kind, x, cin, W, cout, dy, dx, dx_accumulate, dW, dW_accumulate, cur.rest(), cur.left(), s, out,
+                            planes);
+}
+
+static int check_split(const usc_kmap* m, int32_t kind, int32_t P, const char* who) {
+  USC_REQUIRE(m, "%s: null kernel map", who);
+  USC_REQUIRE(P == 2 || P == 3, "%s: P must be 2 or 3 (got %d)", who, P);
+  USC_REQUIRE(kind == USC_CONV_SAME, "%s: the split precision covers stride-1 units only", who);
+  return USC_OK;
+}
+
+int64_t usc_unit_split_ws_bytes(const usc_kmap* m, int32_t kind, int32_t cin, int32_t cout, int32_t P) {
+  if (!m) return 0;
+  if ((P != 2 && P != 3) || kind != USC_CONV_SAME) return -1;
+  if (usc_spconv_gather_gemm_split_ws_bytes(m->n_out, cin, cout, m->K, P) < 0) return -1;
+  // the f32 unit's need (batch-norm partials, weight gradient, an input gradient that stays f32) plus the larger of the
+  // forward's and the input gradient's planes and packs
+  const int64_t f = split_gemm_ws(m, m->n_in, cin, cout, P);
+  const int64_t b = split_dgrad_ok(m, cin, cout, P) ? split_gemm_ws(m, m->n_out, cout, cin, P) : 0;
+  return usc_unit_ws_bytes(m, kind, cin, cout) + (f > b ? f : b) + 256;
+}
+
+int usc_conv_bn_act_forward_split(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
+                                  int32_t P, const usc_bn* bn, const float* residual, int32_t relu, float* y, float* stats,
+                                  float* out, void* ws, int64_t ws_bytes, usc_stream_t s) {
+  int rc = check_split(m, kind, P, "usc_conv_bn_act_forward_split");
+  if (rc) return rc;
+  rc = check_map(m, kind, cin, cout, "usc_conv_bn_act_forward_split");
+  if (rc) return rc;
+  USC_REQUIRE(bn && bn->c == cout, "usc_conv_bn_act_forward_split: batch-norm width must equal the conv's output width");
+  USC_REQUIRE(y && stats && out && bn->gamma && bn->beta, "usc_conv_bn_act_forward_split: null pointer");
+  const ConvShape sh = conv_shape(m, kind);
+  USC_REQUIRE(usc_spconv_gather_gemm_split_ws_bytes(sh.n_out, cin, cout, m->K, P) >= 0,
+              "usc_conv_bn_act_forward_split: shape not covered (K=%d, %d -> %d channels)", m->K, cin, cout);
+  if (sh.n_out == 0) return USC_OK;
+  USC_REQUIRE(x && W, "usc_conv_bn_act_forward_split: null pointer");
+  WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
+  const int64_t sb = usc_colstats_ws_bytes(sh.n_out, cout);
+  void* sws = cur.take(sb);
+  USC_REQUIRE(sws, "usc_conv_bn_act_forward_split: workspace too small (usc_unit_split_ws_bytes)");
+  WsCursor conv{(char*)cur.rest(), cur.left(), 0};
+  rc = split_gemm(m, x, sh.n_in, cin, W, cout, sh.n_out, P, 0, y, 0, conv, s, "usc_conv_bn_act_forward_split");
+  if (rc) return rc;
+  float* mean = stats, *invstd = stats + cout, *scale = stats + 2 * cout, *shift = stats + 3 * cout;
+  // the same forms as usc_conv_bn_act_forward; the tile form finds y finished (no slices)
+  if (bn->training && tile_rows_ok(sh.n_out, cout) && sb >= usc_bn_tile_ws_bytes(cout))
+    return usc_bn_tile_forward(nullptr, 0, y, sh.n_out, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean,
+                               bn->running_var, bn->num_batches_tracked, mean, invstd, scale, shift, residual, relu, out, sws,
+                               sb, s);
+  if (bn->training) {
+    rc = usc_bn_forward_stats(y, sh.n_out, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean,
+                              bn->running_var, bn->num_batches_tracked, mean, invstd, scale, shift, sws, sb, s);
+  } else {
+    USC_REQUIRE(bn->running_mean && bn->running_var, "usc_conv_bn_act_forward_split: eval mode needs running statistics");
+    rc = usc_bn_eval_stats(bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->eps, cout, mean, invstd, scale,
+                           shift, s);
+  }
+  if (rc) return rc;
+  return usc_bn_apply(y, scale, shift, residual, relu, out, sh.n_out, cout, s);
+}
+
+int usc_conv_bn_act_backward_split(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
+                                   int32_t P, const usc_bn* bn, const float* y, const float* stats, const float* out_relu,
+                                   const float* dout, float* dy, float* dres, float* dx, int32_t dx_accumulate, float* dW,
+                                   int32_t dW_accumulate, float* dgamma, float* dbeta, int32_t dbn_accumulate, void* ws,
+                                   int64_t ws_bytes, usc_stream_t s) {
+  const int rc = check_split(m, kind, P, "usc_conv_bn_act_backward_split");
+  if (rc) return rc;
+  return unit_backward_impl(m, kind, x, cin, W, cout, bn, y, stats, out_relu, dout, dy, dres, dx, dx_accumulate, dW,
+                            dW_accumulate, dgamma, dbeta, dbn_accumulate, ws, ws_bytes, s, nullptr, nullptr, P);
 }
 
 int32_t usc_step_size(void) { return (int32_t)sizeof(usc_step); }
@@ -626,7 +734,11 @@ static int64_t program_half_bytes(const usc_step* steps, int32_t n_steps) {
   for (int i = 0; i < n_steps; ++i) {
     const usc_step& t = steps[i];
     if ((t.op == USC_STEP_UNIT_FWD || t.op == USC_STEP_UNIT_BWD) && t.map) {
-      const int64_t b = usc_unit_ws_bytes(t.map, t.kind, t.cin, t.cout);
+      int64_t b = usc_unit_ws_bytes(t.map, t.kind, t.cin, t.cout);
+      if (t.split_planes) {                        // (an uncovered shape is reported by the step itself)
+        const int64_t sb = usc_unit_split_ws_bytes(t.map, t.kind, t.cin, t.cout, t.split_planes);
+        if (sb > b) b = sb;
+      }
       if (b > need) need = b;
     } else if (t.op == USC_STEP_UNIT_FWD_BF16 && t.map) {
       const int64_t b = usc_unit_bf16_ws_bytes(t.map, t.kind, t.cin, t.cout);
@@ -660,6 +772,11 @@ int usc_program_run(const usc_step* steps, int32_t begin, int32_t end, void* ws_
     }
     switch (t.op) {
       case USC_STEP_UNIT_FWD:
+        if (t.split_planes) {
+          rc = usc_conv_bn_act_forward_split(t.map, t.kind, t.x, t.cin, t.W, t.cout, t.split_planes, t.bn, t.residual, t.relu,
+                                             t.y, t.stats, t.out, ws, ws_bytes, s);
+          break;
+        }
         rc = usc_conv_bn_act_forward(t.map, t.kind, t.x, t.cin, t.W, t.cout, t.bn, t.residual, t.relu, t.y, t.stats, t.out,
                                      ws, ws_bytes, s);
         break;
@@ -680,9 +797,11 @@ int usc_program_run(const usc_step* steps, int32_t begin, int32_t end, void* ws_
           if (rc) break;
         }
         Pending next;
+        if (t.split_planes) rc = check_split(t.map, t.kind, t.split_planes, "usc_program_run");
+        if (rc) break;
         rc = unit_backward_impl(t.map, t.kind, t.x, t.cin, t.W, t.cout, t.bn, t.y, t.stats, t.out, t.dout, t.dy, t.dres,
                                 t.dx, t.dx_accumulate, defer ? nullptr : t.dW, t.dW_accumulate, t.dgamma, t.dbeta,
-                                t.dbn_accumulate, ws, ws_bytes, s, &pend, two ? &next : nullptr);
+                                t.dbn_accumulate, ws, ws_bytes, s, &pend, two ? &next : nullptr, t.split_planes);
         if (!rc && pend.G > 0) rc = flush_pending(pend, s);       // (not consumed: cannot happen, kept for safety)
         pend = next;
         if (!rc && defer) {          // x and this step's own dy stay valid until the end of the call (caller's arenas)

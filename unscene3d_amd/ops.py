@@ -333,6 +333,55 @@ def gather_gemm_bf16(feats, Wp, K, cout, nbr, n_out, bias=None, out=None, accumu
     return out
 
 
+def split_bf16(x: torch.Tensor, planes: int) -> torch.Tensor:
+    """f32[rows, c] -> bf16[rows, planes, c]: x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1)
+    (usc_split_bf16_rows); a 1-d f32[n] gives bf16[planes, n] (usc_split_bf16)."""
+    _chk(x, torch.float32, "x")
+    if x.dim() == 1:
+        out = torch.empty((planes, x.shape[0]), dtype=torch.bfloat16, device=x.device)
+        check(lib.usc_split_bf16(_ptr(x), x.numel(), planes, _ptr(out), _stream()), "usc_split_bf16")
+        return out
+    rows, c = x.shape
+    out = torch.empty((rows, planes, c), dtype=torch.bfloat16, device=x.device)
+    check(lib.usc_split_bf16_rows(_ptr(x), rows, c, planes, _ptr(out), _stream()), "usc_split_bf16_rows")
+    return out
+
+
+def pack_w_split(W: torch.Tensor, planes: int, transposed: bool = False) -> torch.Tensor:
+    """f32[K, cin, cout] -> the split kernel's packed weight planes (usc_spconv_pack_w_split), bf16[planes, K*cin*cout];
+    transposed: the mirrored transpose the input gradient needs (operand shape cout -> cin)."""
+    _chk(W, torch.float32, "W")
+    K, cin, cout = W.shape
+    out = torch.empty((planes, K * cin * cout), dtype=torch.bfloat16, device=W.device)
+    check(lib.usc_spconv_pack_w_split(_ptr(W), K, cin, cout, planes, int(transposed), _ptr(out), _stream()),
+          "usc_spconv_pack_w_split")
+    return out
+
+
+def gather_gemm_split(xs, Wp, K, cout, nbr, n_out, bias=None, out=None, accumulate=False):
+    """out[o] (+)= sum_k sum_{i+j<P} x_i[nbr[k,o]] @ W_j[k] (+bias), f32 accumulate (csrc/spconv_split.hip).
+    xs bf16[n_in, P, cin] (split_bf16); Wp bf16[P, K*cin*cout] (pack_w_split); nbr i32[K, n_out] or None (identity)."""
+    _chk(xs, torch.bfloat16, "xs")
+    _chk(Wp, torch.bfloat16, "Wp")
+    n_in, planes, cin = xs.shape
+    if Wp.shape[0] != planes or Wp.shape[1] != K * cin * cout:
+        raise RuntimeError("gather_gemm_split: packed weights do not match P, K, cin, cout")
+    if nbr is not None:
+        _chk(nbr, torch.int32, "nbr")
+        if nbr.shape[0] != K or nbr.shape[1] != n_out:
+            raise RuntimeError("gather_gemm_split: neighbour table shape mismatch")
+    if out is None:
+        out = torch.empty((n_out, cout), dtype=torch.float32, device=xs.device)
+    if bias is not None:
+        _chk(bias, torch.float32, "bias")
+    wsb = lib.usc_spconv_gather_gemm_split_ws_bytes(n_out, cin, cout, K, planes)
+    ws = _ws(wsb, xs.device) if wsb > 0 else None
+    check(lib.usc_spconv_gather_gemm_split(_ptr(xs), n_in, cin, _ptr(Wp), K, cout, planes, _ptr(nbr), n_out, _ptr(bias),
+                                           _ptr(out), int(accumulate), _ptr(ws), max(wsb, 0), _stream()),
+          "usc_spconv_gather_gemm_split")
+    return out
+
+
 def pairs_gemm(feats, W, rows_in, rows_out, koff, P, n_out):
     """out[rows_out[p]] = feats[rows_in[p]] @ W[k(p)] — every out row written exactly once."""
     _chk(feats, torch.float32, "feats")

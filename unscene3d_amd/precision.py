@@ -1,4 +1,7 @@
-"""Inference precision of the backbone's convolutions: f32 (default) or bf16 matrix-core convolutions.
+"""Precision of the backbone's convolutions: inference in f32 (default) or bf16, training in f32 (default) or split bf16.
+
+Inference
+---------
 
     with unscene3d_amd.inference_precision("bf16"):
         with torch.no_grad():
@@ -15,6 +18,23 @@ Weights are packed into the kernel's bf16 operand order once per entry into the 
 with the same precision shares the packs).  The cache is NOT keyed on Tensor._version: the fused optimizer
 (optim.FlatAdamW) writes parameters in place through raw pointers, so the version counter never moves — enter the
 context again after an optimizer step (InstanceSegmentation.eval_step does, once per call).
+
+Training
+--------
+
+    with unscene3d_amd.training_precision("bf16x3"):
+        loss = model(x).F.square().mean()
+        loss.backward()
+
+Under "bf16x2" / "bf16x3" a stride-1 trunk convolution with more than one offset that runs WITH autograd, and that the
+policy below covers, computes its forward and its input gradient on the bf16 matrix cores at f32-grade accuracy
+(csrc/spconv_split.hip): each f32 operand is split into 2 or 3 bf16 planes and the plane products (i, j) with
+i + j < planes are summed in f32.  Three planes drop at most 2^-23 |x||w| per product (below f32's own rounding), two
+planes 3 * 2^-16 |x||w|.  Weight gradients, batch norm, residual and ReLU stay on the f32 kernels.  Nothing is cached:
+activations are split and weights packed inside every call, on its stream, so an optimizer that writes parameters in
+place (even inside the backward pass) is always ordered against them.  The setting is read when the forward pass is
+issued; the backward pass of a unit uses the planes its forward used.  The default "f32" changes nothing: not a launch,
+not a bit.
 """
 from __future__ import annotations
 
@@ -32,6 +52,15 @@ FALLBACKS = set()            # (K, cin, cout) of convolutions that ran in f32 un
 MIN_ROWS = 32768
 MIN_CIN = 96
 STRIDED = False              # the stride-2 and transposed convs (covered by the kernel; measured slower)
+# Training (split bf16): which stride-1, K > 1 units take the split kernel once a user has opted in (output rows and input
+# channels at least these).  Measured (tools/train_precision_bench.py, profiles/train_precision.json):
+# forward + input gradient of every stride-1 K = 27 unit shape of the bench scene is SLOWER than f32 in both split
+# precisions (148 k rows, 96 -> 96: 891 us f32, 1 176 us bf16x2, 2 374 us bf16x3; worse on the coarse levels), so by
+# default NOTHING is covered.  Tests force coverage (both at 0).
+TRAIN_PRECISIONS = ("f32", "bf16x2", "bf16x3")
+TRAIN_MIN_ROWS = 1 << 62
+TRAIN_MIN_CIN = 96
+_train = "f32"
 _current = "f32"
 _packs = None                # id(weight) -> (weight, data_ptr, packed bf16 tensor) of the open context
 
@@ -107,3 +136,57 @@ def unit_weights(W: torch.Tensor, stride1: bool = True, n_out: int = 1 << 62):
     if ent is None or ent[0] is not W or ent[1] != W.data_ptr():
         ent = _packs[id(W)] = (W, W.data_ptr(), pack_weights(W3))
     return ent[2]
+
+
+class training_precision:
+    """Context manager: the precision of trunk convolutions that run with autograd ("f32", "bf16x2" or "bf16x3")."""
+
+    def __init__(self, precision: str):
+        if precision not in TRAIN_PRECISIONS:
+            raise ValueError(f"training_precision: unknown precision {precision!r} (expected one of {TRAIN_PRECISIONS})")
+        self.precision = precision
+        self._saved = None
+
+    def __enter__(self):
+        global _train
+        self._saved = _train
+        _train = self.precision
+        return self
+
+    def __exit__(self, *exc):
+        global _train
+        _train = self._saved
+        self._saved = None
+        return False
+
+
+def current_training() -> str:
+    return _train
+
+
+def train_shape_ok(K: int, cin: int, cout: int, planes: int) -> bool:
+    from ._lib import lib
+    return lib.usc_spconv_gather_gemm_split_ws_bytes(0, cin, cout, K, planes) >= 0
+
+
+def train_planes(W: torch.Tensor, stride1: bool = True, n_out: int = 1 << 62) -> int:
+    """Planes (2 or 3) of the split precision one conv (W: f32[K, cin, cout] or [cin, cout]) runs in, or 0: the f32 path
+    (default precision, autograd off, not a stride-1 K > 1 conv, a unit below TRAIN_MIN_ROWS / TRAIN_MIN_CIN, or a shape
+    the kernel does not cover in the forward or in the input gradient — reported once unless it is the stem)."""
+    if _train == "f32" or not torch.is_grad_enabled():
+        return 0
+    planes = 3 if _train == "bf16x3" else 2
+    if not stride1 or W.dim() != 3 or W.shape[0] == 1:
+        return 0
+    K, cin, cout = W.shape
+    if n_out < TRAIN_MIN_ROWS or cin < TRAIN_MIN_CIN:
+        return 0
+    # both directions: the input gradient is the same product with the operand widths swapped (cout -> cin)
+    if not (train_shape_ok(K, cin, cout, planes) and train_shape_ok(K, cout, cin, planes)):
+        key = (int(K), int(cin), int(cout))
+        if cin >= 16 and key not in FALLBACKS:
+            FALLBACKS.add(key)
+            warnings.warn(f"{_train} training: a {cin} -> {cout} convolution with {K} offsets is not covered by the split "
+                          f"bf16 kernel; it runs in f32", RuntimeWarning, stacklevel=3)
+        return 0
+    return planes

@@ -230,7 +230,7 @@ def usable(model, x):
 
 class _Trunk(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, pl, cm, ts, bf16, feats, *params):
+    def forward(ctx, model, pl, cm, ts, bf16, split, feats, *params):
         dev = feats.device
         rows = [cm.coord_map(ts << l).n for l in range(pl.n_levels)]
         floats = sum(r * f for r, f in zip(rows, pl.act_floats)) + pl.stat_floats + (pl.n_act + 8) * _ALIGN
@@ -271,6 +271,8 @@ class _Trunk(torch.autograd.Function):
                 wp = bf16.get(id(op["conv"].kernel)) if bf16 else None
                 if wp is not None:                           # inference in bf16: packed weights (kept by `bf16`)
                     st.op, st.W = STEP_UNIT_FWD_BF16, wp.data_ptr()
+                if split:                                    # training in split bf16: planes of this unit (0: f32)
+                    st.split_planes = split.get(i, 0)
                 st.residual = ptr[op["res"]] if op["res"] is not None else None
                 st.y, st.stats, st.out = py, ps, po
                 stats_ptr.append(ps)
@@ -288,12 +290,12 @@ class _Trunk(torch.autograd.Function):
         ws = units.workspace(wsb, dev)
         check(lib.usc_program_run(steps, 0, len(pl.ops), ws.data_ptr(), ws.numel(), ops._stream()), "usc_program_run")
         outs = tuple(car.view(offs[b], rows[pl.bufs[b][0]], pl.bufs[b][1]) for b in pl.levels)
-        ctx.state = (model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows)
+        ctx.state = (model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows, split)
         return outs
 
     @staticmethod
     def backward(ctx, *gouts):
-        model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows = ctx.state
+        model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows, split = ctx.state
         dev = feats.device
         gar = _Pool(dev, max(rows[0] * 256, 1 << 20))
         lane = units._lane(dev)                  # weight-gradient lane (on by default): its launches read x and dy after
@@ -402,6 +404,8 @@ class _Trunk(torch.autograd.Function):
             st.dW, st.dW_accumulate, st.dgamma, st.dbeta, st.dbn_accumulate = tW.data_ptr(), 1, tg.data_ptr(), \
                 tb.data_ptr(), 1
             st.defer_wgrad = int(units.GROUP_WGRAD)
+            if split:                            # the planes this unit's forward ran in
+                st.split_planes = split.get(i, 0)
             cur_params.extend((conv.kernel, bn.weight, bn.bias))
             for f in (fres, fdx):
                 if f is not None:
@@ -449,7 +453,7 @@ class _Trunk(torch.autograd.Function):
             key = dev.index if dev.index is not None else torch.cuda.current_device()
             units.queue_lane_join(key)
         ctx.state = None
-        return (None, None, None, None, None, None) + (None,) * len(pl.params)
+        return (None, None, None, None, None, None, None) + (None,) * len(pl.params)
 
 
 def trunk(model, x):
@@ -470,4 +474,15 @@ def trunk(model, x):
                 wp = precision.unit_weights(op["conv"].kernel, op["kind"] == SAME, cm.coord_map(ts << op["lout"]).n)
                 if wp is not None:
                     bf16[id(op["conv"].kernel)] = wp
-    return list(_Trunk.apply(model, pl, cm, ts, bf16, feats, *pl.params))
+    # split-bf16 training (precision.py): index of the unit in the plan -> planes, decided here for the same reason; None
+    # when every unit runs in f32 (the default: the steps are then exactly the f32 program's)
+    split = None
+    if precision.current_training() != "f32" and torch.is_grad_enabled():
+        split = {}
+        for i, op in enumerate(pl.ops):
+            if op["t"] == "unit":
+                planes = precision.train_planes(op["conv"].kernel, op["kind"] == SAME, cm.coord_map(ts << op["lout"]).n)
+                if planes:
+                    split[i] = planes
+        split = split or None
+    return list(_Trunk.apply(model, pl, cm, ts, bf16, split, feats, *pl.params))

@@ -19,7 +19,7 @@ from ..evaluation import (FREEMASK, InstanceAPEvaluator, gt_boxes, load_gt_ids, 
 from ..models.criterion import SetCriterion
 from ..models.mask3d import SINGLE_POINT_ERROR
 from ..models.matcher import HungarianMatcher
-from ..precision import inference_precision
+from ..precision import inference_precision, training_precision
 
 
 def prepare_steady_state(device, main_factor: float = 1.75, side_bytes: int = 768 << 20, min_main_bytes: int = 3 << 30,
@@ -160,9 +160,12 @@ class InstanceSegmentation(nn.Module):
             x = ME.SparseTensor(coordinates=data.coordinates, features=feats, device=dev)
         try:
             ns = [t.get("num_segments") for t in target]
-            output = self.forward(x, point2segment=[t["point2segment"] for t in target],
-                                  raw_coordinates=raw_coordinates,
-                                  num_segments=None if any(n is None or n.is_cuda for n in ns) else ns)
+            # general.train_precision: the trunk's stride-1 convolutions in f32 or split bf16 (read when the forward pass
+            # is issued; a unit's backward uses the planes its forward used)
+            with training_precision(getattr(self.config.general, "train_precision", "f32")):
+                output = self.forward(x, point2segment=[t["point2segment"] for t in target],
+                                      raw_coordinates=raw_coordinates,
+                                      num_segments=None if any(n is None or n.is_cuda for n in ns) else ns)
         except RuntimeError as err:
             if err.args and err.args[0] == SINGLE_POINT_ERROR:
                 return None

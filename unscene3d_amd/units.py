@@ -330,9 +330,17 @@ def usable(x, conv, *more_convs):
 
 # --------------------------------------------------------------------------------------------------------------
 # one unit each way (plain functions: the autograd nodes below compose them)
-def unit_forward(x, W3, bn, kmap: KMapRef, kind, residual, relu, wp=None):
+def _split_ws_bytes(kmap, kind, cin, cout, planes):
+    b = lib.usc_unit_split_ws_bytes(kmap.ref, kind, cin, cout, planes)
+    if b < 0:
+        raise RuntimeError(f"split precision: a {cin} -> {cout} unit of kind {kind} with {planes} planes is not covered")
+    return b
+
+
+def unit_forward(x, W3, bn, kmap: KMapRef, kind, residual, relu, wp=None, planes=0):
     """-> (y conv output, stats f32[4,c], out).  W3 f32[K,cin,cout].  wp: the packed bf16 weights
-    (precision.unit_weights) -> the conv runs in bf16 (inference only), else f32."""
+    (precision.unit_weights) -> the conv runs in bf16 (inference only); planes 2 / 3 (precision.train_planes) -> in split
+    bf16 (usc_conv_bn_act_forward_split, the function a step program's marked step calls); else f32."""
     dev = x.device
     K, cin, cout = W3.shape
     n_out = kmap.n_in if kind == UP else kmap.n_out
@@ -347,6 +355,13 @@ def unit_forward(x, W3, bn, kmap: KMapRef, kind, residual, relu, wp=None):
                                                y.data_ptr(), stats.data_ptr(), out.data_ptr(), ws.data_ptr(),
                                                ws.numel(), ops._stream()), "usc_conv_bn_act_forward_bf16")
         return y, stats, out
+    if planes:
+        ws = workspace(_split_ws_bytes(kmap, kind, cin, cout, planes), dev)
+        check(lib.usc_conv_bn_act_forward_split(kmap.ref, kind, x.data_ptr(), cin, W3.data_ptr(), cout, planes, bref,
+                                                None if residual is None else residual.data_ptr(), int(relu),
+                                                y.data_ptr(), stats.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                                ws.numel(), ops._stream()), "usc_conv_bn_act_forward_split")
+        return y, stats, out
     wsb = lib.usc_unit_ws_bytes(kmap.ref, kind, cin, cout)
     ws = workspace(wsb, dev)
     check(lib.usc_conv_bn_act_forward(kmap.ref, kind, x.data_ptr(), cin, W3.data_ptr(), cout, bref,
@@ -357,9 +372,10 @@ def unit_forward(x, W3, bn, kmap: KMapRef, kind, residual, relu, wp=None):
 
 
 def unit_backward(x, W3, bn, kmap, kind, y, stats, out_relu, dout, dy_buf, want_dres, dx, dx_accumulate, need_dx,
-                  W_param, g_param, b_param, defer_ok=False):
+                  W_param, g_param, b_param, defer_ok=False, planes=0):
     """Backward of one unit.  dy_buf: scratch [n_out, cout] (may be shared between the units of a block — unless
     defer_ok: the weight gradient may then be queued for a grouped launch that reads dy_buf later).
+    planes 2 / 3: the input gradient in split bf16 (usc_conv_bn_act_backward_split), everything else as in f32.
     -> (dx or None, dres or None, dW, dgamma, dbeta) — the last three None when written into .grad in place."""
     dev = x.device
     K, cin, cout = W3.shape
@@ -376,16 +392,19 @@ def unit_backward(x, W3, bn, kmap, kind, y, stats, out_relu, dout, dy_buf, want_
     dg = tg if bn_in_place else torch.empty(cout, dtype=torch.float32, device=dev)
     db = tb if bn_in_place else torch.empty(cout, dtype=torch.float32, device=dev)
     _, bref = _bn_desc(bn, _training(bn))
-    wsb = lib.usc_unit_ws_bytes(kmap.ref, kind, cin, cout)
+    wsb = _split_ws_bytes(kmap, kind, cin, cout, planes) if planes else lib.usc_unit_ws_bytes(kmap.ref, kind, cin, cout)
     ws = workspace(wsb, dev)
     defer = defer_ok and _defer_wgrad(kmap, kind, cin, cout, tW is not None)
-    check(lib.usc_conv_bn_act_backward(kmap.ref, kind, x.data_ptr(), cin, W3.data_ptr(), cout, bref, y.data_ptr(),
-                                       stats.data_ptr(), None if out_relu is None else out_relu.data_ptr(),
-                                       dout.data_ptr(), dy_buf.data_ptr(), None if dres is None else dres.data_ptr(),
-                                       dx.data_ptr() if need_dx else None, int(bool(dx_accumulate)),
-                                       None if defer else dW.data_ptr(),
-                                       int(tW is not None), dg.data_ptr(), db.data_ptr(), int(bn_in_place),
-                                       ws.data_ptr(), ws.numel(), ops._stream()), "usc_conv_bn_act_backward")
+    tail = (bref, y.data_ptr(), stats.data_ptr(), None if out_relu is None else out_relu.data_ptr(),
+            dout.data_ptr(), dy_buf.data_ptr(), None if dres is None else dres.data_ptr(),
+            dx.data_ptr() if need_dx else None, int(bool(dx_accumulate)), None if defer else dW.data_ptr(),
+            int(tW is not None), dg.data_ptr(), db.data_ptr(), int(bn_in_place), ws.data_ptr(), ws.numel(), ops._stream())
+    if planes:
+        check(lib.usc_conv_bn_act_backward_split(kmap.ref, kind, x.data_ptr(), cin, W3.data_ptr(), cout, planes, *tail),
+              "usc_conv_bn_act_backward_split")
+    else:
+        check(lib.usc_conv_bn_act_backward(kmap.ref, kind, x.data_ptr(), cin, W3.data_ptr(), cout, *tail),
+              "usc_conv_bn_act_backward")
     if defer:
         # queued: x and this unit's OWN dy stay referenced until the grouped launch; the write is reported then
         _wgrad_queue(dev).push((id(kmap), cin, cout), kmap, x, dy_buf, W_param, tW)
@@ -407,11 +426,12 @@ class _Unit(torch.autograd.Function):
     """out = [relu](BN(conv(x)) [+ residual]) as one autograd node."""
 
     @staticmethod
-    def forward(ctx, x, W, gamma, beta, residual, bn, kmap, kind, relu, wp):
+    def forward(ctx, x, W, gamma, beta, residual, bn, kmap, kind, relu, wp, planes=0):
         x = x.contiguous()
         res = None if residual is None else residual.contiguous()
         W3 = _w3(W).contiguous()
-        y, stats, out = unit_forward(x, W3, bn, kmap, kind, res, relu, wp)
+        y, stats, out = unit_forward(x, W3, bn, kmap, kind, res, relu, wp, planes)
+        ctx.planes = planes
         ctx.save_for_backward(x, W3, y, stats, out if relu else None)
         ctx.bn, ctx.kmap, ctx.kind, ctx.has_res = bn, kmap, kind, residual is not None
         ctx.params = (W, gamma, beta)
@@ -425,17 +445,20 @@ class _Unit(torch.autograd.Function):
         dy = torch.empty_like(y)
         dx, dres, dW, dg, db = unit_backward(x, W3, ctx.bn, ctx.kmap, ctx.kind, y, stats, out_relu, dout, dy,
                                              ctx.has_res, None, False, ctx.needs_input_grad[0], W, gamma, beta,
-                                             defer_ok=True)
+                                             defer_ok=True, planes=ctx.planes)
         if dW is not None and W.dim() == 2:
             dW = dW.view(W.shape)
-        return dx, dW, dg, db, dres, None, None, None, None, None
+        return dx, dW, dg, db, dres, None, None, None, None, None, None
 
 
 def conv_bn_act(x, conv_weight, bn, kmap, kind, residual=None, relu=True):
     # bf16 only without autograd (precision.unit_weights returns None otherwise): decided here, outside the Function,
     # whose forward always runs with gradients off
+    # the split training precision likewise (precision.train_planes returns 0 without autograd)
+    n_out = kmap.n_in if kind == UP else kmap.n_out
     return _Unit.apply(x, conv_weight, bn.weight, bn.bias, residual, bn, kmap, kind, relu,
-                       precision.unit_weights(conv_weight, kind == SAME, kmap.n_in if kind == UP else kmap.n_out))
+                       precision.unit_weights(conv_weight, kind == SAME, n_out),
+                       precision.train_planes(conv_weight, kind == SAME, n_out))
 
 
 class _BasicBlock(torch.autograd.Function):
@@ -443,11 +466,11 @@ class _BasicBlock(torch.autograd.Function):
     (reference models/modules/resnet_block.py:48-64, models/resnet.py:124-146) as one autograd node."""
 
     @staticmethod
-    def forward(ctx, x, W1, g1, b1, W2, g2, b2, Wd, gd, bd, bns, kmap, kmap_id, wps):
+    def forward(ctx, x, W1, g1, b1, W2, g2, b2, Wd, gd, bd, bns, kmap, kmap_id, wps, sps=(0, 0)):
         x = x.contiguous()
         bn1, bn2, bnd = bns
         W1c, W2c = W1.contiguous(), W2.contiguous()
-        y1, st1, a1 = unit_forward(x, W1c, bn1, kmap, SAME, None, True, wps[0])
+        y1, st1, a1 = unit_forward(x, W1c, bn1, kmap, SAME, None, True, wps[0], sps[0])
         saved_d = (None, None, None)
         if Wd is not None:
             Wdc = _w3(Wd).contiguous()
@@ -455,7 +478,8 @@ class _BasicBlock(torch.autograd.Function):
             saved_d = (Wdc, yd, std)
         else:
             r = x
-        y2, st2, out = unit_forward(a1, W2c, bn2, kmap, SAME, r, True, wps[1])
+        y2, st2, out = unit_forward(a1, W2c, bn2, kmap, SAME, r, True, wps[1], sps[1])
+        ctx.sps = sps
         ctx.save_for_backward(x, W1c, W2c, y1, st1, a1, y2, st2, out, *saved_d)
         ctx.bns, ctx.kmap, ctx.kmap_id = bns, kmap, kmap_id
         ctx.params = (W1, g1, b1, W2, g2, b2, Wd, gd, bd)
@@ -478,20 +502,20 @@ class _BasicBlock(torch.autograd.Function):
         dyd = torch.empty_like(y2) if (own_dy and Wdc is not None) else dy     # (never a queued unit's buffer)
         # unit 2: dout -> (d a1, d residual)
         da1, dres, dW2, dg2, db2 = unit_backward(a1, W2c, bn2, ctx.kmap, SAME, y2, st2, out, dout, dy, True, None,
-                                                 False, True, W2, g2, b2, defer_ok=own_dy)
+                                                 False, True, W2, g2, b2, defer_ok=own_dy, planes=ctx.sps[1])
         dWd = dgd = dbd = None
         if Wdc is None:
             # identity residual: conv1's input gradient is accumulated straight onto the residual gradient
             dx, _, dW1, dg1, db1 = unit_backward(x, W1c, bn1, ctx.kmap, SAME, y1, st1, a1, da1, dy1, False, dres, True,
-                                                 need_dx, W1, g1, b1, defer_ok=own_dy)
+                                                 need_dx, W1, g1, b1, defer_ok=own_dy, planes=ctx.sps[0])
         else:
             dx, _, dW1, dg1, db1 = unit_backward(x, W1c, bn1, ctx.kmap, SAME, y1, st1, a1, da1, dy1, False, None, False,
-                                                 need_dx, W1, g1, b1, defer_ok=own_dy)
+                                                 need_dx, W1, g1, b1, defer_ok=own_dy, planes=ctx.sps[0])
             dx, _, dWd, dgd, dbd = unit_backward(x, Wdc, bnd, ctx.kmap_id, SAME, yd, std, None, dres, dyd, False, dx,
                                                  True, need_dx, Wd, gd, bd)
             if dWd is not None and Wd.dim() == 2:
                 dWd = dWd.view(Wd.shape)
-        return dx, dW1, dg1, db1, dW2, dg2, db2, dWd, dgd, dbd, None, None, None, None
+        return dx, dW1, dg1, db1, dW2, dg2, db2, dWd, dgd, dbd, None, None, None, None, None
 
 
 def basic_block(x, block, kmap, kmap_id):
@@ -506,4 +530,6 @@ def basic_block(x, block, kmap, kmap_id):
     wps = (precision.unit_weights(block.conv1.kernel, True, n), precision.unit_weights(block.conv2.kernel, True, n),
            None if Wd is None else precision.unit_weights(Wd, True, n))
     return _BasicBlock.apply(x, block.conv1.kernel, bn1.weight, bn1.bias, block.conv2.kernel, bn2.weight, bn2.bias,
-                             Wd, gd, bd, (bn1, bn2, bnd), kmap, kmap_id, wps)
+                             Wd, gd, bd, (bn1, bn2, bnd), kmap, kmap_id, wps,
+                             (precision.train_planes(block.conv1.kernel, True, n),
+                              precision.train_planes(block.conv2.kernel, True, n)))
