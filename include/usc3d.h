@@ -659,6 +659,16 @@ int usc_bn_backward_dx(const float* x, const float* dy, const float* y_out,
  * usc_bn_tile_max_rows(): the map size up to which usc_conv_bn_act_forward / _backward and usc_program_run TAKE this form
  * (4 096 rows). */
 int64_t usc_bn_tile_max_rows(void);
+/* Host only, launches nothing: the forms a [n, c] map takes (n, c >= 1; else -1).  Computed by the helpers the launch
+ * code itself calls.
+ *   bits 0-1   statistics form of usc_bn_forward_stats (backward = 0) / usc_bn_backward_reduce (backward = 1):
+ *              0 refused, 1 one launch (bn_small_kernel), 2 two launches (colstats_kernel + finalisation)
+ *   bit 2      one launch: the XCD column remap is on
+ *   bits 3-5   two launches: channels per lane (4 or 1);  bits 8-19: their number of workgroups
+ *   bit 20     usc_bn_tile_ok(n, c);  then bits 24-31: row tiles of usc_bn_tile_*, bits 32 up: rows per tile
+ *   bit 21     usc_conv_bn_act_forward (training mode) / _backward (both modes) and usc_program_run take the tile form on
+ *              this map */
+int64_t usc_bn_plan(int64_t n, int32_t c, int32_t backward);
 int usc_bn_tile_ok(int64_t n, int32_t c);
 int64_t usc_bn_tile_ws_bytes(int32_t c);
 int usc_bn_tile_forward(const float* partial, int32_t G, float* y, int64_t n,

@@ -84,6 +84,7 @@ SIGNATURES = {
     "usc_spconv_sorted_gemm_ex": (C.c_int, [_p, _i64, _i32, _p, _i32, _i32, _p, _p, _p, _i64, _p, _p, _i32, _i32, _p, _i64, _p, _p]),
     "usc_group_reduce": (C.c_int, [_p, _i32, _i64, _i32, _p, _i32, _p, _p]),
     "usc_bn_tile_max_rows": (C.c_int64, []),
+    "usc_bn_plan": (_i64, [_i64, _i32, _i32]),
     "usc_bn_tile_ok": (C.c_int, [_i64, _i32]),
     "usc_bn_tile_ws_bytes": (C.c_int64, [_i32]),
     "usc_bn_tile_forward": (C.c_int, [_p, _i32, _p, _i64, _i32, _p, _p, _f32, _f32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p,

@@ -204,13 +204,16 @@ __global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(const double* __res
 // measured (profiles/r03_hbm_bound_kernels.txt): statistics 9.4 -> 4.2 us at 507 rows, 9.8 -> 8.0 at 2 222, slower from
 // 9 402; the backward reduce (three inputs) 11.6 -> 5.3 us at 507 rows but 11.9 -> 13.4 at 2 222
 static int64_t bn_small_rows(bool backward) { return backward ? 1024 : 4096; }
+static bool bn_small_ok(int64_t n, int c, bool backward) { return n <= bn_small_rows(backward) && c % 4 == 0 && c >= 4; }
+// the XCD column remap of bn_small_kernel applies when the column groups divide over the 8 XCDs
+__host__ __device__ inline bool bn_small_remap(int groups) { return groups % 8 == 0; }
 template <int MODE, typename OUT>
 __global__ __launch_bounds__(256) void bn_small_kernel(StatArgs a, OUT o) {
   __shared__ double sh[8][256 + 2];
   // workgroups go round-robin over the 8 XCDs (each with its own L2): give XCD x the CONTIGUOUS column groups
   // [x*G/8, (x+1)*G/8) so that the 128-byte lines it pulls are used whole instead of 16 bytes at a time by 8 XCDs
   const int G = gridDim.x, b = blockIdx.x;
-  const int grp = (G % 8 == 0) ? (b % 8) * (G / 8) + b / 8 : b;
+  const int grp = bn_small_remap(G) ? (b % 8) * (G / 8) + b / 8 : b;
   const int c = a.c, ch0 = grp * 4, tid = threadIdx.x;
   double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
   float mu[4], is[4];
@@ -296,6 +299,12 @@ __global__ void bn_eval_stats_kernel(const float* __restrict__ gamma, const floa
   shift[ch] = beta[ch] - rmean[ch] * sc;
 }
 
+// lanes per row of colstats_kernel: 16-byte columns where the width allows it, else one channel per lane; 0: refused
+static int colstats_vec(int c) {
+  if (c < 1 || c > 1024) return 0;
+  const int vec = (c % 4 == 0 && c / 4 <= 256) ? 4 : 1;
+  return c / vec <= 256 ? vec : 0;
+}
 static int colstats_blocks(int64_t n, int c, int vec) {
   const int CT = c / vec, RP = 256 / CT;
   int64_t b = ceil_div(n, (int64_t)RP * 4 * kStatUnroll);
@@ -308,9 +317,8 @@ template <int MODE>
 static int launch_colstats_partials(const StatArgs& a, void* ws, int64_t ws_bytes, hipStream_t st, const char* name,
                                     int* nblocks_out) {
   const int c = a.c;
-  USC_REQUIRE(c >= 1 && c <= 1024, "%s: unsupported channel count %d", name, c);
-  const int vec = (c % 4 == 0 && c / 4 <= 256) ? 4 : 1;
-  USC_REQUIRE(c / vec <= 256, "%s: unsupported channel count %d", name, c);
+  const int vec = colstats_vec(c);
+  USC_REQUIRE(vec > 0, "%s: unsupported channel count %d", name, c);
   const int nb = colstats_blocks(a.n, c, vec);
   USC_REQUIRE(ws_bytes >= (int64_t)nb * 2 * c * 8, "%s: workspace too small", name);
   const int RP = 256 / (c / vec);
@@ -1180,11 +1188,35 @@ static int bn_apply_grid(int64_t nvec) {
   return (int)g;
 }
 
+// the unit calls (units.hip) take the tile form on maps of up to usc_bn_tile_max_rows() rows (the kernels themselves
+// cover any size)
+static bool tile_form_on() {
+  static const bool on = usc_bn_tile_max_rows() > 0;
+  return on;
+}
+bool tile_rows_ok(int64_t n, int c) { return tile_form_on() && n <= usc_bn_tile_max_rows() && usc_bn_tile_ok(n, c); }
+
 }  // namespace usc
 
 using namespace usc;
 
 extern "C" {
+
+int64_t usc_bn_plan(int64_t n, int32_t c, int32_t backward) {
+  USC_REQUIRE(n >= 1 && c >= 1, "usc_bn_plan: bad sizes");
+  int64_t code = 0;
+  if (bn_small_ok(n, c, backward != 0)) {
+    code = 1 | ((int64_t)bn_small_remap(c / 4) << 2);
+  } else if (const int vec = colstats_vec(c)) {
+    code = 2 | ((int64_t)vec << 3) | ((int64_t)colstats_blocks(n, c, vec) << 8);
+  }
+  if (usc_bn_tile_ok(n, c)) {
+    const BnTileGeom g = bn_tile_geom(n, c);
+    code |= ((int64_t)1 << 20) | ((int64_t)g.ntiles << 24) | ((int64_t)g.tr << 32);
+  }
+  if (tile_rows_ok(n, c)) code |= (int64_t)1 << 21;
+  return code;
+}
 
 int64_t usc_colstats_ws_bytes(int64_t n, int32_t c) { (void)n; return (int64_t)kStatMaxBlocks * 2 * c * 8; }
 
@@ -1209,7 +1241,7 @@ int usc_bn_forward_stats(const float* x, int64_t n, int32_t c, const float* gamm
   USC_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "usc_bn_forward_stats: running stats mismatch");
   StatArgs a{x, nullptr, nullptr, nullptr, nullptr, n, (int)c};
   BnFwdOut o{gamma, beta, running_mean, running_var, mean, invstd, scale, shift, eps, momentum, n, num_batches_tracked};
-  if (n <= bn_small_rows(false) && c % 4 == 0 && c >= 4) {
+  if (bn_small_ok(n, c, false)) {
     hipLaunchKernelGGL((bn_small_kernel<STAT_XY, BnFwdOut>), dim3((unsigned)(c / 4)), dim3(256), 0, as_stream(s), a, o);
     USC_CHECK_LAUNCH("usc_bn_forward_stats");
     return USC_OK;
@@ -1239,7 +1271,7 @@ int usc_bn_backward_reduce(const float* x, const float* dy, const float* y_out, 
               "usc_bn_backward_reduce: bad argument");
   StatArgs a{x, dy, y_out, mean, invstd, n, (int)c};
   BnBwdOut o{dgamma, dbeta, mean_g, mean_gxhat, n, (int)training, (int)accumulate};
-  if (n <= bn_small_rows(true) && c % 4 == 0 && c >= 4) {
+  if (bn_small_ok(n, c, true)) {
     hipLaunchKernelGGL((bn_small_kernel<STAT_BN_BWD, BnBwdOut>), dim3((unsigned)(c / 4)), dim3(256), 0, as_stream(s), a, o);
     USC_CHECK_LAUNCH("usc_bn_backward_reduce");
     return USC_OK;

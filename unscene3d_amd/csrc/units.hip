@@ -16,6 +16,10 @@
 
 #include "common.h"
 
+// rows.hip: the unit calls take the batch norm's tile form on maps of up to usc_bn_tile_max_rows() rows (usc_bn_plan
+// reports the same answer)
+namespace usc { bool tile_rows_ok(int64_t n, int c); }
+
 using namespace usc;
 
 namespace {
@@ -378,13 +382,6 @@ static int flush_pending(Pending& p, usc_stream_t s) {
   p = Pending{};
   return rc;
 }
-
-static bool tile_form_on() {
-  static const bool on = usc_bn_tile_max_rows() > 0;
-  return on;
-}
-// the unit calls take the tile form on maps of up to usc_bn_tile_max_rows() rows (the kernels themselves cover any size)
-static bool tile_rows_ok(int64_t n, int c) { return tile_form_on() && n <= usc_bn_tile_max_rows() && usc_bn_tile_ok(n, c); }
 
 static int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
                               const float* dy, float* dx, int32_t dx_accumulate, float* dW, int32_t dW_accumulate, void* ws,
