@@ -905,9 +905,10 @@ int usc_criterion_backward(const float* const* masks, float* const* dmasks, int3
 /* Linear layer on a handful of rows (the 100 decoder queries):
  *   y[M,N] = x[M,K] W[N,K]^T + b[N]   (b may be NULL);  N, K multiples of 32.
  * usc_linear_bwd: dx[M,K] = dy W, dW[N,K] = dy^T x, db[N] = column sums of dy; each
- * of dx / dW may be NULL to skip it (db is produced with dW); accumulate=1 adds
- * dW / db into the given buffers (parameter gradients).  One workgroup per 32x32
- * output tile on the f32 matrix cores, one launch per product.
+ * of dx / dW may be NULL to skip it (db is produced inside the dW tiles: db
+ * without dW is refused); accumulate=1 adds dW / db into the given buffers
+ * (parameter gradients).  One workgroup per 32x32 output tile on the f32 matrix
+ * cores; the forward is one launch, both gradients together are one launch.
  * Replaces nn.Linear / the nn.MultiheadAttention projections of the mask decoder
  * (models/mask3d.py:491-651 attention layers and FFN, :70-72 mask_embed_head). */
 int usc_linear_fwd(const float* x, const float* W, const float* b, int32_t M,

@@ -1290,6 +1290,36 @@ def test_decoder_graphs_refuse_parameters_moved_after_capture(device):
         fn(x)
 
 
+def test_graph_capture_keeps_the_cycle_collector_out(device):
+    """capture_passes collects dead cycles BEFORE its first capture (the runners of an earlier call are one: they own HIP
+    graphs and pool memory) and keeps the collector off while a stream captures: a finaliser that reaches the HIP runtime
+    from inside a capture aborts the process.  The collector is back on afterwards."""
+    import gc
+    import weakref
+
+    from unscene3d_amd.graphs import capture_passes
+
+    seen = []
+
+    class Probe(torch.nn.Linear):
+        def forward(self, x):
+            if torch.cuda.is_current_stream_capturing():
+                seen.append(gc.isenabled())
+            return super().forward(x)
+
+    torch.manual_seed(0)
+    x = torch.randn(8, 32, device=device, requires_grad=True)
+    earlier = capture_passes([torch.nn.Linear(32, 32).to(device)], [(x,)])
+    runner = weakref.ref(earlier[0]._runner)
+    del earlier                                   # only the runners' own cycle keeps them now
+    assert gc.isenabled()
+    (fn,) = capture_passes([Probe(32, 32).to(device)], [(x,)])
+    assert seen == [False] and gc.isenabled()
+    assert runner() is None, "the earlier capture's runners were still alive when the next capture began"
+    fn(x).sum().backward()
+    torch.cuda.synchronize()
+
+
 def test_chained_graph_pass_refuses_a_foreign_input_while_the_previous_output_is_live(device):
     """capture_passes(chain_input=0): pass 1 reads pass 0's output buffer in place.  Handing pass 1 ANOTHER tensor would
     make the replay copy it over that buffer — which pass 0's autograd consumers still need for this step's backward:

@@ -651,6 +651,7 @@ int usc_linear_bwd_ex2(const float* dy, const float* y_relu, const float* x, con
   USC_REQUIRE(M >= 1 && N >= 32 && N % 32 == 0 && K >= 32 && K % 32 == 0, "usc_linear_bwd: N, K must be multiples of 32");
   USC_REQUIRE(dy && x && W, "usc_linear_bwd: null pointer");
   USC_REQUIRE(dx || !(dx_add || dx_add2 || dx_b), "usc_linear_bwd: dx_add / dx_add2 / dx_b need dx");
+  USC_REQUIRE(dW || !db, "usc_linear_bwd: db is computed inside the dW tiles, it needs dW");
   hipStream_t st = usc::as_stream(s);
   const int dx_tiles = dx ? (K / 32) * ((M + 31) / 32) : 0;
   const int dw_tiles = dW ? (K / 32) * (N / 32) : 0;

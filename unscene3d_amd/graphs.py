@@ -13,11 +13,31 @@ does not change after capture — use `optimizer.zero_grad(set_to_none=False)` (
 """
 from __future__ import annotations
 
+import contextlib
+import gc
+
 import torch
 
 # "thread_local": other threads of the process (the RCCL watchdog polls events while a multi-GPU job captures) may
 # keep issuing HIP calls during capture without invalidating it
 _CAPTURE_MODE = "thread_local"
+
+
+@contextlib.contextmanager
+def _no_cyclic_collection():
+    """CPython's cycle collector switched off for the duration of the stream captures.  A collection that starts in the
+    middle of one (any allocation of a container object can start it) runs the finalisers of whatever dead cycle it
+    finds, and a finaliser that calls into the HIP runtime on the capturing thread aborts the process: seen once, inside
+    the collector, under the first forward capture of a model built after others had been dropped.  The runners of an
+    earlier capture_passes call are such a cycle (`r.group` holds every runner of its call) and own graphs and pool
+    memory; torch.cuda.graph does not collect before it begins (only with torch.compiler.config.force_cudagraph_gc)."""
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class _Runner:
@@ -193,34 +213,39 @@ def capture_passes(modules, sample_inputs, warmup_iters: int = 3, shared_inputs=
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
 
+    # dead cycles go now, outside any capture (the graphs and pool memory of earlier captures among them), and the
+    # collector stays off until the last capture has ended
+    gc.collect()
     pool = torch.cuda.graph_pool_handle()
     # all forward graphs first, then the backward graphs in reverse order: the pool's liveness during capture
     # then mirrors the liveness during a training step (fwd 0..n-1, bwd n-1..0)
     prev = None
-    for r in runners:
-        if chain_input is not None and prev is not None and prev.static_out.shape == r.static_in[chain_input].shape \
-                and prev.static_out.dtype == r.static_in[chain_input].dtype:
-            # a fresh leaf over the previous pass's output storage (same strides): replaying pass k then pass k+1 hands
-            # the queries over without a copy; any other tensor given at replay is copied into it as before
-            r.static_in[chain_input] = prev.static_out.detach().requires_grad_(r.static_in[chain_input].requires_grad)
-            r.chain_pos, r.chain_prev = chain_input, prev
-        with torch.cuda.graph(r.fwd_graph, pool=pool, capture_error_mode=_CAPTURE_MODE):
-            r.static_out = r.module(*r.static_in)
-        prev = r
-    for r in reversed(runners):
-        r.static_grad_out = torch.zeros_like(r.static_out)
-        targets = [r.static_in[j] for j in r.grad_in_idx] + r.params
-        with torch.cuda.graph(r.bwd_graph, pool=pool, capture_error_mode=_CAPTURE_MODE):
-            grads = torch.autograd.grad((r.static_out,), targets, (r.static_grad_out,), allow_unused=True)
-            n_in = len(r.grad_in_idx)
-            dst = [p.grad for p, g in zip(r.params, grads[n_in:]) if g is not None]
-            src = [g for g in grads[n_in:] if g is not None]
-            if dst:
-                torch._foreach_add_(dst, src)
-        r.static_grad_in = list(grads[:n_in])
-        _GRAD_OUT_BUFFERS[(r.static_out.device.index, r.static_out.data_ptr())] = r.static_grad_out
-        r.grad_ptrs = [p.grad.data_ptr() for p in r.params]
-        r.data_ptrs = [p.data_ptr() for p in r.params]
+    with _no_cyclic_collection():
+        for r in runners:
+            if chain_input is not None and prev is not None and prev.static_out.shape == r.static_in[chain_input].shape \
+                    and prev.static_out.dtype == r.static_in[chain_input].dtype:
+                # a fresh leaf over the previous pass's output storage (same strides): replaying pass k then pass k+1
+                # hands the queries over without a copy; any other tensor given at replay is copied into it as before
+                needs_grad = r.static_in[chain_input].requires_grad
+                r.static_in[chain_input] = prev.static_out.detach().requires_grad_(needs_grad)
+                r.chain_pos, r.chain_prev = chain_input, prev
+            with torch.cuda.graph(r.fwd_graph, pool=pool, capture_error_mode=_CAPTURE_MODE):
+                r.static_out = r.module(*r.static_in)
+            prev = r
+        for r in reversed(runners):
+            r.static_grad_out = torch.zeros_like(r.static_out)
+            targets = [r.static_in[j] for j in r.grad_in_idx] + r.params
+            with torch.cuda.graph(r.bwd_graph, pool=pool, capture_error_mode=_CAPTURE_MODE):
+                grads = torch.autograd.grad((r.static_out,), targets, (r.static_grad_out,), allow_unused=True)
+                n_in = len(r.grad_in_idx)
+                dst = [p.grad for p, g in zip(r.params, grads[n_in:]) if g is not None]
+                src = [g for g in grads[n_in:] if g is not None]
+                if dst:
+                    torch._foreach_add_(dst, src)
+            r.static_grad_in = list(grads[:n_in])
+            _GRAD_OUT_BUFFERS[(r.static_out.device.index, r.static_out.data_ptr())] = r.static_grad_out
+            r.grad_ptrs = [p.grad.data_ptr() for p in r.params]
+            r.data_ptrs = [p.data_ptr() for p in r.params]
     for r in runners:
         r.group = runners
         r.shared_pos = tuple(shared_inputs)
