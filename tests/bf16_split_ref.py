@@ -1,4 +1,4 @@
-"""Split-bf16 oracle of the training-precision tests (csrc/spconv_split.hip): the planes of an f32 value, the kept plane
+"""Split-bf16 oracle of the training-precision tests (csrc/spconv_bf16.hip): the planes of an f32 value, the kept plane
 products, and a float64 convolution that sums exactly those products.  Every product of two planes is exact in f32
 (and in float64), so the kernel differs from this oracle only by its f32 accumulation."""
 import numpy as np

@@ -146,6 +146,28 @@ def test_kernel_edge_rows_bias_accumulate_and_missing_neighbours(device, maps):
         _check(y2, ref2, mag2, (cin, cout, "bias"))
 
 
+def test_cast_rounds_like_the_reference_across_the_vector_tail_seam(device):
+    """ops.cast_bf16 on 4k + {0, 1, 2, 3} elements (four per thread, then a 1 - 3 element tail launch) equals
+    bf16_ref.bf16_bits bit for bit: +-inf, NaN (stays a quiet NaN), a denormal, exact ties to even both ways, a finite
+    value that rounds to inf; the specials sit at the front and at the very end (inside the tail where there is one)."""
+    from bf16_ref import bf16_bits
+    from unscene3d_amd import ops
+    special = np.array([np.inf, -np.inf, np.nan, 1e-40, -1e-40, 1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, -(1.0 + 2.0 ** -8),
+                        3.4e38, -3.4e38, 0.0, -0.0], np.float32)
+    special[2:3].view(np.uint32)[0] = 0x7F800001                          # a signalling NaN with an empty upper half
+    rng = np.random.default_rng(11)
+    for n in (1024, 1025, 1026, 1027, 1, 3):
+        a = (rng.standard_normal(n) * np.exp2(rng.integers(-30, 31, n))).astype(np.float32)
+        k = min(n, special.size)
+        a[:k] = special[:k]
+        a[n - min(n, 3):] = special[[0, 2, 8]][:min(n, 3)]
+        got = ops.cast_bf16(torch.from_numpy(a).to(device)).view(torch.int16).cpu().numpy().view(np.uint16)
+        want = bf16_bits(a)
+        assert np.array_equal(got, want), (n, np.flatnonzero(got != want)[:8])
+    assert bf16_bits(special[2:3])[0] == 0x7FC0 and bf16_bits(special[8:9])[0] == 0x7F80
+    assert bf16_bits(special[5:7]).tolist() == [0x3F80, 0x3F82]           # ties go to the even neighbour, down and up
+
+
 def test_bench_scene_96_map_and_determinism(device):
     """The ~145 k-row stride-1 map of the 150 k-voxel bench scene at 96 -> 96; two launches give the same bits."""
     from unscene3d_amd import ops, precision

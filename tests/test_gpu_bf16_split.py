@@ -1,4 +1,4 @@
-"""Opt-in split-bf16 training convolutions (csrc/spconv_split.hip, unscene3d_amd/precision.py) on the MI355X.
+"""Opt-in split-bf16 training convolutions (csrc/spconv_bf16.hip, unscene3d_amd/precision.py) on the MI355X.
 
 Kernels: the split and the packs against the numpy planes bit for bit; the gather-GEMM against a float64 sum of exactly
 the kept plane products (tests/bf16_split_ref.py) — every product is exact, so only the f32 accumulation differs:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Training precision f32 vs bf16x2 vs bf16x3 (unscene3d_amd.training_precision, csrc/spconv_split.hip).
+"""Training precision f32 vs bf16x2 vs bf16x3 (unscene3d_amd.training_precision, csrc/spconv_bf16.hip).
 
 (a) Per unit: for every distinct stride-1 K = 27 unit shape of Res16UNet34C on the bench scene's own kernel maps, the
     forward and the input gradient, each as the kernel alone (operands already split / packed) and as the whole pass:

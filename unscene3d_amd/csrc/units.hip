@@ -284,7 +284,7 @@ int usc_wgrad_lane_join(usc_stream_t s) {
   return USC_OK;
 }
 
-// ---- split-bf16 precision of a stride-1 unit (spconv_split.hip) --------------------------------------------------------
+// ---- the bf16 matrix-core precisions of a unit (spconv_bf16.hip): one plane for inference, 2 or 3 for training --------
 // the input gradient is the same product over the mirrored transpose: operand shape cout -> cin
 static bool split_dgrad_ok(const usc_kmap* m, int cin, int cout, int planes) {
   return usc_spconv_gather_gemm_split_ws_bytes(m->n_in, cout, cin, m->K, planes) >= 0;
@@ -295,23 +295,40 @@ static int64_t split_gemm_ws(const usc_kmap* m, int64_t n_src, int c_src, int c_
   return align_up(n_src * c_src * planes * 2, 256) + align_up((int64_t)planes * m->K * c_src * c_dst * 2, 256) +
          align_up(g > 0 ? g : 16, 256);
 }
-// dst[o] (+)= sum_k sum_{i+j<P} src_i[nbr[k][o]] W_j[k]   (transposed: over the mirrored transpose of W f32[K][cin][cout],
-// src has cout channels and dst cin).  src is split and W packed on every call, on the caller's stream.
-static int split_gemm(const usc_kmap* m, const float* src, int64_t n_src, int c_src, const float* W, int c_dst, int64_t n_dst,
-                      int planes, int transposed, float* dst, int accumulate, WsCursor cur, usc_stream_t s, const char* who) {
+// dst[o] (+)= sum_k sum_{i+j<P} src_i[nbr[k][o]] W_j[k].  src is converted on every call, on the caller's stream; so is W
+// f32[K][cin][cout], unless the caller has it packed (Wp, one plane).  transposed: the product over the mirrored
+// transpose of W, src has cout channels and dst cin.  up: the transposed conv of a stride-2 map, where every fine row has
+// one parent: the child table read backwards is the gather table over the fine rows.
+// Scratch, in this order: the operand's planes, the packed weight planes, the kernel's own, the table.
+static int planes_gemm(const usc_kmap* m, int P, const float* src, int64_t n_src, int c_src, const float* W,
+                       const uint16_t* Wp, int c_dst, int64_t n_dst, int transposed, bool up, float* dst, int accumulate,
+                       WsCursor cur, usc_stream_t s, const char* who) {
   const int K = m->K;
-  const int64_t gb = usc_spconv_gather_gemm_split_ws_bytes(n_dst, c_src, c_dst, K, planes);
-  USC_REQUIRE(gb >= 0, "%s: shape not covered by the split kernel (P=%d, K=%d, %d -> %d channels)", who, planes, K, c_src, c_dst);
-  uint16_t* xs = (uint16_t*)cur.take(n_src * c_src * planes * 2);
-  uint16_t* wp = (uint16_t*)cur.take((int64_t)planes * K * c_src * c_dst * 2);
+  const int64_t gb = P == 1 ? usc_spconv_gather_gemm_bf16_ws_bytes(n_dst, c_src, c_dst, K)
+                            : usc_spconv_gather_gemm_split_ws_bytes(n_dst, c_src, c_dst, K, P);
+  USC_REQUIRE(gb >= 0, "%s: shape not covered by the bf16 kernels (P=%d, K=%d, %d -> %d channels)", who, P, K, c_src, c_dst);
+  uint16_t* xs = (uint16_t*)cur.take(n_src * c_src * P * 2);
+  uint16_t* wp = Wp ? nullptr : (uint16_t*)cur.take((int64_t)P * K * c_src * c_dst * 2);
   void* gws = gb > 0 ? cur.take(gb) : nullptr;
-  USC_REQUIRE(xs && wp && (gb == 0 || gws), "%s: workspace too small for the split precision (usc_unit_split_ws_bytes)", who);
-  int rc = usc_split_bf16_rows(src, n_src, c_src, planes, xs, s);
+  int32_t* table = up ? (int32_t*)cur.take((int64_t)K * n_dst * 4) : nullptr;
+  USC_REQUIRE(xs && (Wp || wp) && (gb == 0 || gws) && (!up || table), "%s: workspace too small %s", who,
+              P == 1 ? "(usc_unit_bf16_ws_bytes)" : "for the split precision (usc_unit_split_ws_bytes)");
+  int rc = P == 1 ? usc_cast_bf16(src, n_src * c_src, xs, s) : usc_split_bf16_rows(src, n_src, c_src, P, xs, s);
   if (rc) return rc;
-  rc = transposed ? usc_spconv_pack_w_split(W, K, c_dst, c_src, planes, 1, wp, s)
-                  : usc_spconv_pack_w_split(W, K, c_src, c_dst, planes, 0, wp, s);
-  if (rc) return rc;
-  return usc_spconv_gather_gemm_split(xs, n_src, c_src, wp, K, c_dst, planes, m->nbr, n_dst, nullptr, dst, accumulate, gws, gb, s);
+  if (!Wp) {
+    rc = transposed ? usc_spconv_pack_w_split(W, K, c_dst, c_src, P, 1, wp, s)
+                    : usc_spconv_pack_w_split(W, K, c_src, c_dst, P, 0, wp, s);
+    if (rc) return rc;
+    Wp = wp;
+  }
+  const int32_t* nbr = m->nbr;
+  if (up) {
+    rc = spconv_up_table(m->nbr, K, m->n_out, n_dst, table, as_stream(s));
+    if (rc) return rc;
+    nbr = table;
+  }
+  return P == 1 ? usc_spconv_gather_gemm_bf16(xs, n_src, c_src, Wp, K, c_dst, nbr, n_dst, nullptr, dst, accumulate, gws, gb, s)
+                : usc_spconv_gather_gemm_split(xs, n_src, c_src, Wp, K, c_dst, P, nbr, n_dst, nullptr, dst, accumulate, gws, gb, s);
 }
 
 static void conv_ws_parts(const usc_kmap* m, int kind, int cin, int cout, int64_t* fwd, int64_t* dgrad, int64_t* wg) {
@@ -457,7 +474,8 @@ static int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, i
   Slices* want = (may_defer && dgrad_bytes > 0) ? &left : nullptr;
   if (dx && sh.n_in > 0) {
     if (split_dx) {
-      rc = split_gemm(m, dy, sh.n_out, cout, W, cin, sh.n_in, planes, 1, dx, dx_accumulate, cur, s, "usc_conv_backward");
+      rc = planes_gemm(m, planes, dy, sh.n_out, cout, W, nullptr, cin, sh.n_in, 1, false, dx, dx_accumulate, cur, s,
+                       "usc_conv_backward");
     } else if (kind == USC_CONV_SAME) {
       // stride-1 map: the mirrored offset reaches the rows that read row i; transpose folded where the kernel can
       rc = table_gemm(m, m->nbr, dy, sh.n_out, cout, W, K, cin, sh.n_in, nullptr, dx, dx_accumulate, 1, cur, s, want);
@@ -506,6 +524,34 @@ int64_t usc_unit_ws_bytes(const usc_kmap* m, int32_t kind, int32_t cin, int32_t 
          align_up(2 * (int64_t)cout * 4, 256) + 256;
 }
 
+// the batch norm's tile form (coarse levels) takes a forward unit's output when the statistics are the batch's
+static bool bn_tile_form(const usc_bn* bn, int64_t n, int c, int64_t sb) {
+  return bn->training && tile_rows_ok(n, c) && sb >= usc_bn_tile_ws_bytes(c);
+}
+
+// the end of every forward unit: statistics of y (the batch's, or the running ones in eval mode), then scale and shift
+// (+ residual) (+ ReLU).  tile: the caller allows the tile form (bn_tile_form), which sums the split-K slices the
+// convolution left behind on its way (none: y is finished).
+static int bn_act_tail(const char* who, const usc_bn* bn, bool tile, Slices left, float* y, int64_t n, int cout,
+                       const float* residual, int relu, float* stats, float* out, void* sws, int64_t sb, usc_stream_t s) {
+  float* mean = stats, *invstd = stats + cout, *scale = stats + 2 * cout, *shift = stats + 3 * cout;
+  if (tile)
+    return usc_bn_tile_forward(left.partial, left.G, y, n, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean,
+                               bn->running_var, bn->num_batches_tracked, mean, invstd, scale, shift, residual, relu, out, sws,
+                               sb, s);
+  int rc;
+  if (bn->training) {
+    rc = usc_bn_forward_stats(y, n, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean, bn->running_var,
+                              bn->num_batches_tracked, mean, invstd, scale, shift, sws, sb, s);
+  } else {
+    USC_REQUIRE(bn->running_mean && bn->running_var, "%s: eval mode needs running statistics", who);
+    rc = usc_bn_eval_stats(bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->eps, cout, mean, invstd, scale,
+                           shift, s);
+  }
+  if (rc) return rc;
+  return usc_bn_apply(y, scale, shift, residual, relu, out, n, cout, s);
+}
+
 int usc_conv_bn_act_forward(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
                             const usc_bn* bn, const float* residual, int32_t relu, float* y, float* stats, float* out,
                             void* ws, int64_t ws_bytes, usc_stream_t s) {
@@ -517,26 +563,12 @@ int usc_conv_bn_act_forward(const usc_kmap* m, int32_t kind, const float* x, int
   void* sws = cur.take(sb);                       // BN partials first: the conv's scratch takes the rest
   USC_REQUIRE(sws, "usc_conv_bn_act_forward: workspace too small");
   // tile form (coarse levels): the convolution leaves its split-K slices behind, two launches do the rest
-  const bool tile = bn->training && tile_rows_ok(sh.n_out, cout) && sb >= usc_bn_tile_ws_bytes(cout);
+  const bool tile = bn_tile_form(bn, sh.n_out, cout, sb);
   Slices left;
   int rc = conv_forward_impl(m, kind, x, cin, W, cout, nullptr, y, cur.rest(), cur.left(), s, tile ? &left : nullptr);
   if (rc) return rc;
   if (sh.n_out == 0) return USC_OK;
-  float* mean = stats, *invstd = stats + cout, *scale = stats + 2 * cout, *shift = stats + 3 * cout;
-  if (tile)
-    return usc_bn_tile_forward(left.partial, left.G, y, sh.n_out, cout, bn->gamma, bn->beta, bn->eps, bn->momentum,
-                               bn->running_mean, bn->running_var, bn->num_batches_tracked, mean, invstd, scale, shift,
-                               residual, relu, out, sws, sb, s);
-  if (bn->training) {
-    rc = usc_bn_forward_stats(y, sh.n_out, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean,
-                              bn->running_var, bn->num_batches_tracked, mean, invstd, scale, shift, sws, sb, s);
-  } else {
-    USC_REQUIRE(bn->running_mean && bn->running_var, "usc_conv_bn_act_forward: eval mode needs running statistics");
-    rc = usc_bn_eval_stats(bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->eps, cout, mean, invstd, scale,
-                           shift, s);
-  }
-  if (rc) return rc;
-  return usc_bn_apply(y, scale, shift, residual, relu, out, sh.n_out, cout, s);
+  return bn_act_tail("usc_conv_bn_act_forward", bn, tile, left, y, sh.n_out, cout, residual, relu, stats, out, sws, sb, s);
 }
 
 
@@ -563,37 +595,16 @@ int usc_conv_bn_act_forward_bf16(const usc_kmap* m, int32_t kind, const float* x
   if (sh.n_out == 0) return USC_OK;
   USC_REQUIRE(x && Wp, "usc_conv_bn_act_forward_bf16: null pointer");
   USC_REQUIRE(m->nbr || kind == USC_CONV_SAME, "usc_conv_bn_act_forward_bf16: strided maps need the child table");
-  hipStream_t st = as_stream(s);
   WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
   const int64_t sb = usc_colstats_ws_bytes(sh.n_out, cout);
   void* sws = cur.take(sb);
-  uint16_t* xb = (uint16_t*)cur.take(sh.n_in * cin * 2);
-  void* gws = gb > 0 ? cur.take(gb) : nullptr;
-  int32_t* table = kind == USC_CONV_UP ? (int32_t*)cur.take((int64_t)m->K * sh.n_out * 4) : nullptr;
-  USC_REQUIRE(sws && xb && (gb == 0 || gws) && (kind != USC_CONV_UP || table),
-              "usc_conv_bn_act_forward_bf16: workspace too small (usc_unit_bf16_ws_bytes)");
-  rc = usc_cast_bf16(x, sh.n_in * cin, xb, s);
+  USC_REQUIRE(sws, "usc_conv_bn_act_forward_bf16: workspace too small (usc_unit_bf16_ws_bytes)");
+  rc = planes_gemm(m, 1, x, sh.n_in, cin, nullptr, Wp, cout, sh.n_out, 0, kind == USC_CONV_UP, y, 0, cur, s,
+                   "usc_conv_bn_act_forward_bf16");
   if (rc) return rc;
-  const int32_t* nbr = m->nbr;
-  if (kind == USC_CONV_UP) {
-    // every fine row has one parent: the child table read backwards is the gather table over the fine rows
-    rc = spconv_up_table(m->nbr, m->K, m->n_out, sh.n_out, table, st);
-    if (rc) return rc;
-    nbr = table;
-  }
-  rc = usc_spconv_gather_gemm_bf16(xb, sh.n_in, cin, Wp, m->K, cout, nbr, sh.n_out, nullptr, y, 0, gws, gb, s);
-  if (rc) return rc;
-  float* mean = stats, *invstd = stats + cout, *scale = stats + 2 * cout, *shift = stats + 3 * cout;
-  if (bn->training) {
-    rc = usc_bn_forward_stats(y, sh.n_out, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean,
-                              bn->running_var, bn->num_batches_tracked, mean, invstd, scale, shift, sws, sb, s);
-  } else {
-    USC_REQUIRE(bn->running_mean && bn->running_var, "usc_conv_bn_act_forward_bf16: eval mode needs running statistics");
-    rc = usc_bn_eval_stats(bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->eps, cout, mean, invstd, scale,
-                           shift, s);
-  }
-  if (rc) return rc;
-  return usc_bn_apply(y, scale, shift, residual, relu, out, sh.n_out, cout, s);
+  // (inference: the tile form is not taken)
+  return bn_act_tail("usc_conv_bn_act_forward_bf16", bn, false, Slices{}, y, sh.n_out, cout, residual, relu, stats, out, sws,
+                     sb, s);
 }
 
 static int unit_backward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
@@ -691,25 +702,11 @@ int usc_conv_bn_act_forward_split(const usc_kmap* m, int32_t kind, const float* 
   const int64_t sb = usc_colstats_ws_bytes(sh.n_out, cout);
   void* sws = cur.take(sb);
   USC_REQUIRE(sws, "usc_conv_bn_act_forward_split: workspace too small (usc_unit_split_ws_bytes)");
-  WsCursor conv{(char*)cur.rest(), cur.left(), 0};
-  rc = split_gemm(m, x, sh.n_in, cin, W, cout, sh.n_out, P, 0, y, 0, conv, s, "usc_conv_bn_act_forward_split");
+  rc = planes_gemm(m, P, x, sh.n_in, cin, W, nullptr, cout, sh.n_out, 0, false, y, 0, cur, s, "usc_conv_bn_act_forward_split");
   if (rc) return rc;
-  float* mean = stats, *invstd = stats + cout, *scale = stats + 2 * cout, *shift = stats + 3 * cout;
   // the same forms as usc_conv_bn_act_forward; the tile form finds y finished (no slices)
-  if (bn->training && tile_rows_ok(sh.n_out, cout) && sb >= usc_bn_tile_ws_bytes(cout))
-    return usc_bn_tile_forward(nullptr, 0, y, sh.n_out, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean,
-                               bn->running_var, bn->num_batches_tracked, mean, invstd, scale, shift, residual, relu, out, sws,
-                               sb, s);
-  if (bn->training) {
-    rc = usc_bn_forward_stats(y, sh.n_out, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean,
-                              bn->running_var, bn->num_batches_tracked, mean, invstd, scale, shift, sws, sb, s);
-  } else {
-    USC_REQUIRE(bn->running_mean && bn->running_var, "usc_conv_bn_act_forward_split: eval mode needs running statistics");
-    rc = usc_bn_eval_stats(bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->eps, cout, mean, invstd, scale,
-                           shift, s);
-  }
-  if (rc) return rc;
-  return usc_bn_apply(y, scale, shift, residual, relu, out, sh.n_out, cout, s);
+  return bn_act_tail("usc_conv_bn_act_forward_split", bn, bn_tile_form(bn, sh.n_out, cout, sb), Slices{}, y, sh.n_out, cout,
+                     residual, relu, stats, out, sws, sb, s);
 }
 
 int usc_conv_bn_act_backward_split(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,

@@ -305,6 +305,30 @@ def cast_bf16(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _gather_gemm_planes(xs, planes, cin, Wp, K, cout, nbr, n_out, bias, out, accumulate):
+    """What gather_gemm_bf16 (planes None: xs bf16[n_in, cin]) and gather_gemm_split (xs bf16[n_in, planes, cin]) share:
+    the table, output and bias checks and the call."""
+    if planes is None:
+        name, ws_bytes, gemm, split = "usc_spconv_gather_gemm_bf16", lib.usc_spconv_gather_gemm_bf16_ws_bytes, \
+            lib.usc_spconv_gather_gemm_bf16, ()
+    else:
+        name, ws_bytes, gemm, split = "usc_spconv_gather_gemm_split", lib.usc_spconv_gather_gemm_split_ws_bytes, \
+            lib.usc_spconv_gather_gemm_split, (planes,)
+    if nbr is not None:
+        _chk(nbr, torch.int32, "nbr")
+        if nbr.shape[0] != K or nbr.shape[1] != n_out:
+            raise RuntimeError(f"{name[11:]}: neighbour table shape mismatch")
+    if out is None:
+        out = torch.empty((n_out, cout), dtype=torch.float32, device=xs.device)
+    if bias is not None:
+        _chk(bias, torch.float32, "bias")
+    wsb = ws_bytes(n_out, cin, cout, K, *split)
+    ws = _ws(wsb, xs.device) if wsb > 0 else None
+    check(gemm(_ptr(xs), xs.shape[0], cin, _ptr(Wp), K, cout, *split, _ptr(nbr), n_out, _ptr(bias), _ptr(out),
+               int(accumulate), _ptr(ws), max(wsb, 0), _stream()), name)
+    return out
+
+
 def gather_gemm_bf16(feats, Wp, K, cout, nbr, n_out, bias=None, out=None, accumulate=False):
     """out[o] (+)= sum_k bf16(feats[nbr[k,o]]) @ bf16(W[k]) (+bias), f32 accumulate (csrc/spconv_bf16.hip).
     feats bf16[n_in, cin] (cast_bf16) or f32 (cast here); Wp: precision.pack_weights(W f32[K, cin, cout]);
@@ -317,20 +341,7 @@ def gather_gemm_bf16(feats, Wp, K, cout, nbr, n_out, bias=None, out=None, accumu
     cin = feats.shape[1]
     if Wp.numel() != K * cin * cout:
         raise RuntimeError("gather_gemm_bf16: packed weights do not match K, cin, cout")
-    if nbr is not None:
-        _chk(nbr, torch.int32, "nbr")
-        if nbr.shape[0] != K or nbr.shape[1] != n_out:
-            raise RuntimeError("gather_gemm_bf16: neighbour table shape mismatch")
-    if out is None:
-        out = torch.empty((n_out, cout), dtype=torch.float32, device=feats.device)
-    if bias is not None:
-        _chk(bias, torch.float32, "bias")
-    wsb = lib.usc_spconv_gather_gemm_bf16_ws_bytes(n_out, cin, cout, K)
-    ws = _ws(wsb, feats.device) if wsb > 0 else None
-    check(lib.usc_spconv_gather_gemm_bf16(_ptr(feats), feats.shape[0], cin, _ptr(Wp), K, cout, _ptr(nbr), n_out,
-                                          _ptr(bias), _ptr(out), int(accumulate), _ptr(ws), max(wsb, 0), _stream()),
-          "usc_spconv_gather_gemm_bf16")
-    return out
+    return _gather_gemm_planes(feats, None, cin, Wp, K, cout, nbr, n_out, bias, out, accumulate)
 
 
 def split_bf16(x: torch.Tensor, planes: int) -> torch.Tensor:
@@ -359,27 +370,14 @@ def pack_w_split(W: torch.Tensor, planes: int, transposed: bool = False) -> torc
 
 
 def gather_gemm_split(xs, Wp, K, cout, nbr, n_out, bias=None, out=None, accumulate=False):
-    """out[o] (+)= sum_k sum_{i+j<P} x_i[nbr[k,o]] @ W_j[k] (+bias), f32 accumulate (csrc/spconv_split.hip).
+    """out[o] (+)= sum_k sum_{i+j<P} x_i[nbr[k,o]] @ W_j[k] (+bias), f32 accumulate (csrc/spconv_bf16.hip).
     xs bf16[n_in, P, cin] (split_bf16); Wp bf16[P, K*cin*cout] (pack_w_split); nbr i32[K, n_out] or None (identity)."""
     _chk(xs, torch.bfloat16, "xs")
     _chk(Wp, torch.bfloat16, "Wp")
     n_in, planes, cin = xs.shape
     if Wp.shape[0] != planes or Wp.shape[1] != K * cin * cout:
         raise RuntimeError("gather_gemm_split: packed weights do not match P, K, cin, cout")
-    if nbr is not None:
-        _chk(nbr, torch.int32, "nbr")
-        if nbr.shape[0] != K or nbr.shape[1] != n_out:
-            raise RuntimeError("gather_gemm_split: neighbour table shape mismatch")
-    if out is None:
-        out = torch.empty((n_out, cout), dtype=torch.float32, device=xs.device)
-    if bias is not None:
-        _chk(bias, torch.float32, "bias")
-    wsb = lib.usc_spconv_gather_gemm_split_ws_bytes(n_out, cin, cout, K, planes)
-    ws = _ws(wsb, xs.device) if wsb > 0 else None
-    check(lib.usc_spconv_gather_gemm_split(_ptr(xs), n_in, cin, _ptr(Wp), K, cout, planes, _ptr(nbr), n_out, _ptr(bias),
-                                           _ptr(out), int(accumulate), _ptr(ws), max(wsb, 0), _stream()),
-          "usc_spconv_gather_gemm_split")
-    return out
+    return _gather_gemm_planes(xs, planes, cin, Wp, K, cout, nbr, n_out, bias, out, accumulate)
 
 
 def pairs_gemm(feats, W, rows_in, rows_out, koff, P, n_out):

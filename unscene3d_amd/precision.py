@@ -28,7 +28,7 @@ Training
 
 Under "bf16x2" / "bf16x3" a stride-1 trunk convolution with more than one offset that runs WITH autograd, and that the
 policy below covers, computes its forward and its input gradient on the bf16 matrix cores at f32-grade accuracy
-(csrc/spconv_split.hip): each f32 operand is split into 2 or 3 bf16 planes and the plane products (i, j) with
+(csrc/spconv_bf16.hip): each f32 operand is split into 2 or 3 bf16 planes and the plane products (i, j) with
 i + j < planes are summed in f32.  Three planes drop at most 2^-23 |x||w| per product (below f32's own rounding), two
 planes 3 * 2^-16 |x||w|.  Weight gradients, batch norm, residual and ReLU stay on the f32 kernels.  Nothing is cached:
 activations are split and weights packed inside every call, on its stream, so an optimizer that writes parameters in
