@@ -1338,6 +1338,57 @@ int usc_instance_masks(const int32_t* rank, int64_t n, const int32_t* slot, int3
                        uint8_t* masks, const int64_t* seg, int32_t seg_ld, int64_t n_segments,
                        uint8_t* segment_mask, usc_stream_t s);
 
+/* ------------------------------------------------------------------------
+ * FreeMask pseudo masks, voxel mode (pseudo_masks/freemask_main.py:242-279,
+ * :352-417; utils/freemask_utils.py:8-18 cosine_sim; utils/pc_utils.py:727-757
+ * matrix_nms(kernel='mask')) without the f32[Q,K] similarity matrix.
+ *   a[q][k] = (fq[q] * sq[q]) . (fk[k] * sk[k]);  a -= rowmin[q];
+ *   a /= (rowmax[q] - rowmin[q]) + 1e-9;  a[:, all-zero keys] = 0;  mask = a >= threshold
+ * fq f32[q,c], fk f32[k,c], 1 <= c <= 512, any q, k >= 1 (tails inside the
+ * kernels).  The products run on v_mfma_f32_32x32x2_f32; every a[q][k] is the
+ * same chain of operations in the three kernels that form it, so the bits, the
+ * sums and the soft rows agree with each other bit for bit.  No atomics, fixed
+ * summation order: bit-identical from run to run.
+ *
+ * usc_freemask_normalize: scale[r] = 1 / (|feats[r]| + 1e-9) for every row;
+ *   zero u8[n] (may be NULL) = 1 where the row is all zero.
+ * usc_freemask_rowstats: rowmin / rowmax f32[q] of a over all k keys (the
+ *   all-zero keys included, as the reference).
+ * usc_freemask_bits: bits u64[q, ceil(k/64)], key j = bit j % 64 of word
+ *   j / 64, bits at positions >= k zero, every word written; count i32[q] = the
+ *   popcount of the row; soft_sum f32[q] = sum of a over the row's set bits.
+ * usc_freemask_soft_rows: out f32[m, k], row j = the normalised, key-zeroed a of
+ *   query qidx[j] (each in [0, q)); m <= 4096.
+ * ws: usc_freemask_ws_bytes(q, k) bytes, for rowstats and bits alike.
+ *
+ * usc_mask_bits_extent: lo / hi i32[n,3] = min / max of coords i32[k,3] over the
+ *   set bits of every row of bits u64[n, ceil(k/64)]; an empty row gives
+ *   lo = INT32_MAX > hi = INT32_MIN.
+ * usc_mask_bits_nms: greedy mask NMS over the rows order i32[n] of bits (each
+ *   in range, in descending score order), count i32[rows] their popcounts:
+ *   walking positions upward, a position i that is still alive kills every
+ *   later alive j with  union > 0 ? (float)inter / (float)union > nms_thr : true,
+ *   inter = popcount(row_i & row_j), union = count_i + count_j - inter.
+ *   keep u8[n] by position.  ws: usc_mask_bits_nms_ws_bytes(n) =
+ *   n * ceil(n/64) * 8 bytes (the "i would kill j" bit matrix); n <= 524288.
+ * ---------------------------------------------------------------------- */
+int usc_freemask_normalize(const float* feats, int64_t n, int32_t c, float* scale, uint8_t* zero, usc_stream_t s);
+int64_t usc_freemask_ws_bytes(int64_t q, int64_t k);
+int usc_freemask_rowstats(const float* fq, const float* sq, int64_t q, const float* fk, const float* sk, int64_t k,
+                          int32_t c, float* rowmin, float* rowmax, void* ws, int64_t ws_bytes, usc_stream_t s);
+int usc_freemask_bits(const float* fq, const float* sq, int64_t q, const float* fk, const float* sk,
+                      const uint8_t* zero_k, int64_t k, int32_t c, const float* rowmin, const float* rowmax,
+                      float threshold, uint64_t* bits, int32_t* count, float* soft_sum, void* ws, int64_t ws_bytes,
+                      usc_stream_t s);
+int usc_freemask_soft_rows(const float* fq, const float* sq, int64_t q, const float* fk, const float* sk,
+                           const uint8_t* zero_k, int64_t k, int32_t c, const float* rowmin, const float* rowmax,
+                           const int32_t* qidx, int32_t m, float* out, usc_stream_t s);
+int usc_mask_bits_extent(const uint64_t* bits, int64_t n, int64_t k, const int32_t* coords, int32_t* lo, int32_t* hi,
+                         usc_stream_t s);
+int64_t usc_mask_bits_nms_ws_bytes(int64_t n);
+int usc_mask_bits_nms(const uint64_t* bits, const int32_t* count, int64_t k, const int32_t* order, int32_t n,
+                      float nms_thr, uint8_t* keep, void* ws, int64_t ws_bytes, usc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,11 @@ Replicas only: rank r of W takes the scenes r, r+W, ... and nev
     python tools/pseudo_masks_run.py --scenes DIR --out OUT                         # one GPU
     python -m torch.distributed.run --nproc-per-node 8 tools/pseudo_masks_run.py --scenes DIR --out OUT
     python tools/pseudo_masks_run.py --synthetic 6 --out /tmp/pm                   # self-contained demo scenes
+    python tools/pseudo_masks_run.py --scenes DIR --out OUT --method freemask      # the FreeMask baseline instead of NCut
+
+--method ncut (default) writes `{scene}_masks.npy` as bool[N_full, K] NCut masks; --method freemask (reference
+pseudo_masks/freemask_main.py, voxel mode; unscene3d_amd.pseudo_masks.freemask) writes it as f32[N_full, M] soft masks,
+the file freemask_preprocessing.py:197-213 and datasets/freemask.py read.  Both write `{scene}_cloud.npy` last.
 
 Scene files (`DIR/*.npz`, one per scene; this tool does not read frames, so the encoders' per-voxel outputs are an
 input here.  Both encoders are in the package — the DINO ViT-S/8 image encoder as
@@ -97,6 +102,33 @@ def process_scene(path, out_dir, device, ncut_args):
     return name, int(all_masks.shape[1]), time.perf_counter() - t0
 
 
+def process_scene_freemask(path, out_dir, device, fm_args, modality="2d", resolution_scale=2):
+    """FreeMask voxel mode on one scene file -> (scene name, number of masks, seconds); None when already processed.  A
+    scene without instances writes nothing (the reference prints and skips it)."""
+    from unscene3d_amd.pseudo_masks import freemask as fm
+    name = os.path.splitext(os.path.basename(path))[0]
+    cloud_file = os.path.join(out_dir, f"{name}_cloud.npy")
+    if os.path.exists(cloud_file):
+        return None
+    t0 = time.perf_counter()
+    z = np.load(path)
+    key = f"feats_{modality}"
+    if key not in z.files:
+        raise RuntimeError(f"{path}: needs {key} for --method freemask --modality {modality}")
+    coords = torch.from_numpy(z["coords"].astype(np.int32)).to(device)
+    feats = torch.from_numpy(z[key].astype(np.float32)).to(device)
+    voxel_size = float(z["voxel_size"]) if "voxel_size" in z.files else 0.02
+    r = fm.freemask_from_voxel_feats(coords, feats, resolution_scale, **fm_args)
+    if r.soft_masks.shape[0] == 0:
+        return name, 0, time.perf_counter() - t0
+    full = z["full_res_coords"].astype(np.float32)
+    all_masks = fm.soft_masks_to_full_resolution(r.key_coords, r.tensor_stride, full, voxel_size, r.soft_masks)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"{name}_masks.npy"), all_masks)
+    np.save(cloud_file, full.astype(np.single))                     # written last: its presence marks "done"
+    return name, int(all_masks.shape[1]), time.perf_counter() - t0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scenes", help="directory with one .npz per scene")
@@ -107,6 +139,17 @@ def main(argv=None):
     ap.add_argument("--min-segment-size", type=int, default=4)
     ap.add_argument("--separation-mode", default="max")
     ap.add_argument("--max-extent-ratio", type=float, default=0.8)
+    ap.add_argument("--method", choices=("ncut", "freemask"), default="ncut")
+    fm = ap.add_argument_group("--method freemask (freemask_main.py's config.freemask)")
+    fm.add_argument("--modality", choices=("2d", "3d"), default="2d", help="which per-voxel features of the scene file")
+    fm.add_argument("--resolution-scale", type=int, default=2)
+    fm.add_argument("--hard-mask-threshold", type=float, default=0.35)
+    fm.add_argument("--min-mask-points", type=int, default=10)
+    fm.add_argument("--instance-to-scene-max-ratio", type=float, default=0.8)
+    fm.add_argument("--nms-thr", type=float, default=0.5)
+    fm.add_argument("--max-instance-num", type=int, default=50)
+    fm.add_argument("--nms-maskness-threshold", type=float, default=0.6)
+    fm.add_argument("--similarity-metric", default="cos")
     args = ap.parse_args(argv)
     from unscene3d_amd.pseudo_masks.driver import scene_shard
 
@@ -129,9 +172,16 @@ def main(argv=None):
     ncut_args = dict(affinity_tau=args.affinity_tau, max_number_of_instances=args.max_instances,
                      min_segment_size=args.min_segment_size, separation_mode=args.separation_mode,
                      max_extent_ratio=args.max_extent_ratio)
+    fm_args = dict(hard_mask_threshold=args.hard_mask_threshold, min_mask_points=args.min_mask_points,
+                   instance_to_scene_max_ratio=args.instance_to_scene_max_ratio, nms_thr=args.nms_thr,
+                   max_instance_num=args.max_instance_num, nms_maskness_threshold=args.nms_maskness_threshold,
+                   similarity_metric=args.similarity_metric)
     done = 0
     for i in mine:
-        r = process_scene(files[i], args.out, device, ncut_args)
+        if args.method == "freemask":
+            r = process_scene_freemask(files[i], args.out, device, fm_args, args.modality, args.resolution_scale)
+        else:
+            r = process_scene(files[i], args.out, device, ncut_args)
         if r is None:
             print(f"[rank {rank}] scene already processed: {os.path.basename(files[i])}", flush=True)
         else:

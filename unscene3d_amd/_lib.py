@@ -230,6 +230,14 @@ SIGNATURES = {
     "usc_instance_index": (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _p]),
     "usc_instance_select": (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _i32, _i64, _p, _p, _p, _p]),
     "usc_instance_masks": (C.c_int, [_p, _i64, _p, _i32, _i32, _p, _p, _i32, _i64, _p, _p]),
+    "usc_freemask_normalize": (C.c_int, [_p, _i64, _i32, _p, _p, _p]),
+    "usc_freemask_ws_bytes": (_i64, [_i64, _i64]),
+    "usc_freemask_rowstats": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _i32, _p, _p, _p, _i64, _p]),
+    "usc_freemask_bits": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, _i32, _p, _p, _f32, _p, _p, _p, _p, _i64, _p]),
+    "usc_freemask_soft_rows": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, _i32, _p, _p, _p, _i32, _p, _p]),
+    "usc_mask_bits_extent": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _p]),
+    "usc_mask_bits_nms_ws_bytes": (_i64, [_i64]),
+    "usc_mask_bits_nms": (C.c_int, [_p, _p, _i64, _p, _i32, _f32, _p, _p, _i64, _p]),
 }
 
 
