@@ -1170,6 +1170,25 @@ int usc_raycast_first_hit_dense(const int64_t* occupancy, int32_t dim_z, int32_t
 int usc_project_reduce(const float* feats, int32_t c, const int64_t* order,
                        const int64_t* seg_off, int64_t n_rows, int32_t mode,
                        float* out, int32_t* num, usc_stream_t s);
+/* Mode 1 of usc_project_reduce for V frames in one launch, reading the image encoder's token grids instead
+ * of their resized maps (models/encoders_2d/dino.py:53-60 resizes every grid to [H,W,c] with
+ * F.interpolate(size=(H,W), mode='bilinear'); pseudo_masks/unscene3d_pseudo_main.py:303-313 then folds one
+ * frame at a time).  tokens f32[V,gh,gw,c], 1 <= c <= 512; (order, seg_off) is the CSR usc_segment_csr
+ * built over n_rows+1 segments from the `seg` of ONE ray cast over the same V views (B = 1), so the pixel
+ * index is (v*H + y)*W + x and every row's list is grouped by frame, in frame order.  Per row r and per
+ * frame f that hits it, in ascending f:
+ *   m_f = (sum over the frame's pixels, in list order, of bilinear(tokens[f], y, x)) / (count_f + 10e-5)
+ *   scene[r] = (scene[r] + m_f) / 2
+ * bilinear, in f32 with separately rounded operations (half-pixel centres, as torch computes it):
+ *   src = (gh / H) * (y + 0.5) - 0.5, clamped at 0 from below; y0 = (int)src; lambda = src - y0;
+ *   second tap y0 + (y0 < gh - 1); the same in x;
+ *   val = (1-ly) * ((1-lx)*t00 + lx*t01) + ly * ((1-lx)*t10 + lx*t11).
+ * Rows no frame hits are not written.  frames_hit i32[n_rows] (may be NULL) = number of frames of this call
+ * that hit the row.  No atomics: the result does not depend on how frames are grouped into calls. */
+int usc_project_fuse_tokens(const float* tokens, int32_t V, int32_t gh, int32_t gw,
+                            int32_t c, int32_t H, int32_t W, const int64_t* order,
+                            const int64_t* seg_off, int64_t n_rows, float* scene,
+                            int32_t* frames_hit, usc_stream_t s);
 /* Prediction mode (project_image_cuda_kernel.cu:68-109): out i32[n_rows,c] (caller-initialised to the
  * ignore label) = max(out, preds of the pixels that hit the row); preds i32[n_pix,c]. */
 int usc_project_predictions(const int32_t* preds, int32_t c, const int32_t* hit,

@@ -15,17 +15,21 @@ Replicas only: rank r of W takes the scenes r, r+W, ... and nev
 pseudo_masks/freemask_main.py, voxel mode; unscene3d_amd.pseudo_masks.freemask) writes it as f32[N_full, M] soft masks,
 the file freemask_preprocessing.py:197-213 and datasets/freemask.py read.  Both write `{scene}_cloud.npy` last.
 
-Scene files (`DIR/*.npz`, one per scene; this tool does not read frames, so the encoders' per-voxel outputs are an
-input here.  Both encoders are in the package — the DINO ViT-S/8 image encoder as
-unscene3d_amd.models.encoders_2d.DinoNet, the CSC Res16UNet as models.res16unet — and `encode_scene_feats_2d/_3d` of
-unscene3d_amd.pseudo_masks.pipeline produce these arrays from frames / a backbone; their published weights are files the
-user brings):
+Scene files (`DIR/*.npz`, one per scene; the encoders' per-voxel outputs are an input here.
+tools/scene_files_from_scans.py writes these files from ScanNet-style scan directories — colour frames, poses, the info
+file and the mesh — with `feats_2d` from the DINO ViT-S/8 image encoder (unscene3d_amd.pseudo_masks.scans.build_scene).
+`feats_3d` is the user's to add: the CSC Res16UNet is in the package as models.res16unet, and
+unscene3d_amd.pseudo_masks.pipeline.encode_scene_feats_3d produces the array from a backbone.  The encoders' published
+weights are files the user brings):
     coords            int[N,3] or [N,4]   voxel coordinates (b,x,y,z or x,y,z)
     feats_2d, feats_3d f32[N,d]            per-voxel features of one or both modalities (all-zero rows = not seen)
     segment_ids       int[N]              over-segmentation id per voxel (felzenszwalb_cpp.segment_mesh + 1-NN)
     seg_connectivity  int[E,2]            directed segment adjacency
     full_res_coords   f32[M,3]            the scene's full-resolution points (metres)
     voxel_size        float               default 0.02
+    colors            f32[N,3]            optional, not read here: rgb / 255 - 0.5 per voxel, what the 3D backbone takes
+                                          to produce feats_3d (scene_files_from_scans.py writes it, with the counts
+                                          frames_used / frames_dropped of its image branch)
 """
 import argparse
 import glob

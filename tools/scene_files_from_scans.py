@@ -1,0 +1,111 @@
+#!/usr/bin/env python
+"""Scan directories -> the scene files tools/pseudo_masks_run.py reads: for every `SCANS/{scene}/` (info file, mesh,
+color/, pose/ — the layout unscene3d_amd/pseudo_masks/scans.py documents, ScanNet's) voxelise the mesh, over-segment it,
+run the colour frames through the DINO ViT-S/8 encoder and project them onto the voxels
+(scans.build_scene; reference pseudo_masks/datasets/scannet.py + unscene3d_pseudo_main.py:287-330), and write
+`OUT/{scene}.npz`.  Scenes whose file exists are skipped.
+
+Replicas only, like pseudo_masks_run.py: rank r of W takes the scenes r, r+W, ...
+
+    python tools/scene_files_from_scans.py --scans SCANS --out SCENES --dino-weights dino_deitsmall8_pretrain.pth
+    python -m torch.distributed.run --nproc-per-node 8 tools/scene_files_from_scans.py --scans SCANS --out SCENES ...
+    python tools/pseudo_masks_run.py --scenes SCENES --out MASKS
+
+--dino-weights is the published DINO ViT-S/8 checkpoint (a state_dict; not part of this repository);
+--random-weights SEED initialises the encoder from a seed instead (smoke runs and benchmarks: the features mean nothing).
+--frame-batch K sends K frames per encoder pass and projection launch (pipeline.encode_scene_feats_2d); 0 is the
+per-frame path through the resized feature maps.  The default is what profiles/scene_encode_bench.txt measured fastest."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+DINO_LAYER, DINO_STRIDE = 10, 4   # pseudo_masks/config/default.yaml:53-54
+DEFAULT_FRAME_BATCH = 16      # profiles/scene_encode_bench.txt: 0.162 s per 64-frame scene (8: 0.175, per-frame maps: 0.364)
+
+
+def make_encoder(args, device):
+    from types import SimpleNamespace
+
+    from unscene3d_amd.models.encoders_2d import DinoNet
+    from unscene3d_amd.models.encoders_2d.dino import init_random_weights
+
+    feature = "attention" if args.attention else "descriptors"
+    cfg = SimpleNamespace(image_data=SimpleNamespace(image_backbone="dino_vits8", dino_vit_feature=feature,
+                                                     dino_vit_layer=DINO_LAYER, dino_vit_stride=DINO_STRIDE))
+    net = DinoNet(cfg, precision=args.precision)
+    if args.dino_weights:
+        net.vit.load_state_dict(torch.load(args.dino_weights, map_location="cpu"), strict=True)
+    else:
+        init_random_weights(net.vit, args.random_weights)
+    return net.to(device).eval()
+
+
+def process_scan(scan_dir, out_dir, model, args):
+    """-> (scene name, voxels, frames used, frames dropped, seconds) or None when the scene file exists."""
+    from unscene3d_amd.pseudo_masks import scans
+
+    name = os.path.basename(os.path.normpath(scan_dir))
+    path = os.path.join(out_dir, f"{name}.npz")
+    if os.path.exists(path):
+        return None
+    t0 = time.perf_counter()
+    scene = scans.build_scene(scan_dir, model, voxel_size=args.voxel_size, image_hw=(args.height, args.width),
+                              segments_min_verts=args.segments_min_verts, frame_batch=args.frame_batch or None,
+                              attention=args.attention, every=args.every,
+                              device=next(model.parameters()).device)
+    os.makedirs(out_dir, exist_ok=True)
+    tmp = path + ".tmp.npz"
+    np.savez(tmp, **scene)
+    os.replace(tmp, path)                                           # a killed run leaves no half-written scene file
+    return name, scene["coords"].shape[0], scene["frames_used"], scene["frames_dropped"], time.perf_counter() - t0
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--scans", required=True, help="directory with one sub-directory per scan")
+    ap.add_argument("--out", required=True, help="directory for the .npz scene files")
+    w = ap.add_mutually_exclusive_group(required=True)
+    w.add_argument("--dino-weights", help="state_dict file of DINO ViT-S/8")
+    w.add_argument("--random-weights", type=int, metavar="SEED")
+    ap.add_argument("--frame-batch", type=int, default=DEFAULT_FRAME_BATCH, metavar="K",
+                    help="frames per encoder pass and projection launch; 0 = the per-frame map path")
+    ap.add_argument("--every", type=int, default=1, metavar="K", help="use every K-th frame")
+    ap.add_argument("--precision", choices=("f32", "bf16"), default="f32")
+    ap.add_argument("--attention", action="store_true", help="key and query of the last block (feats_2d_query too)")
+    ap.add_argument("--voxel-size", type=float, default=0.02)
+    ap.add_argument("--height", type=int, default=192)
+    ap.add_argument("--width", type=int, default=256)
+    ap.add_argument("--segments-min-verts", type=int, default=50)
+    args = ap.parse_args(argv)
+    if args.frame_batch < 0 or args.every < 1:
+        ap.error("--frame-batch needs K >= 0 and --every K >= 1")
+    from unscene3d_amd.pseudo_masks.driver import scene_shard
+
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
+    torch.cuda.set_device(local)
+    device = torch.device("cuda", local)
+    dirs = sorted(d for d in (os.path.join(args.scans, e) for e in os.listdir(args.scans)) if os.path.isdir(d))
+    mine = scene_shard(len(dirs), rank, world)
+    model = make_encoder(args, device)
+    done = 0
+    for i in mine:
+        r = process_scan(dirs[i], args.out, model, args)
+        if r is None:
+            print(f"[rank {rank}] scene file exists: {os.path.basename(dirs[i])}", flush=True)
+        else:
+            done += 1
+            print(f"[rank {rank}] {r[0]}: {r[1]} voxels, {r[2]} frames ({r[3]} dropped) in {r[4]:.2f} s", flush=True)
+    print(f"[rank {rank}/{world}] {done} of {len(mine)} scans of this shard written ({len(dirs)} in the list)", flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

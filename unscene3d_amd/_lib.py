@@ -176,6 +176,7 @@ SIGNATURES = {
     "usc_raycast_first_hit_dense": (C.c_int, [_p, _i32, _i32, _i32, _i64, _p, _p, _i32, _i32, _i32, _i32, _f32, _f32,
                                               _f32, _p, _p, _p]),
     "usc_project_reduce": (C.c_int, [_p, _i32, _p, _p, _i64, _i32, _p, _p, _p]),
+    "usc_project_fuse_tokens": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _i64, _p, _p, _p]),
     "usc_project_predictions": (C.c_int, [_p, _i32, _p, _i64, _p, _p]),
     "usc_unproject_depth": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p]),
     "usc_spin": (C.c_int, [_i64, C.c_int, _p]),

@@ -3,6 +3,7 @@
 //   per-voxel reduction of the hit pixels' features            (project_image_cuda_kernel.cu:58-65, raycast_image.py:66-68)
 //   running-mean fusion of a frame into the scene features     (pseudo_masks/unscene3d_pseudo_main.py:311-330)
 //   prediction mode (integer max) and depth-image unprojection (project_image_cuda_kernel.cu:68-109,249-290)
+//   the same fusion for several frames per launch, sampling the encoder's token grids (models/encoders_2d/dino.py:53-60)
 //
 // The reference marches every ray in steps of voxel_size/2 *voxel units* (0.01 voxel: ~19 500 samples per ray) and
 // reads a dense int64 occupancy grid at every sample, then adds the pixel's feature vector to its voxel with one float
@@ -215,6 +216,97 @@ __global__ __launch_bounds__(256) void project_reduce_kernel(const float* __rest
   }
 }
 
+// Source position of output index i on a grid of g cells resized to n pixels: torch's bilinear resize with half-pixel
+// centres (F.interpolate(size=..., mode="bilinear"), the resize of models/encoders_2d/dino.py `_to_image`).
+struct Tap { int i0, i1; float lam; };
+__device__ inline Tap bilinear_tap(int i, float scale, int g) {
+#pragma clang fp contract(off)
+  float src = scale * ((float)i + 0.5f) - 0.5f;
+  src = src < 0.0f ? 0.0f : src;
+  Tap t;
+  t.i0 = (int)src;                        // < g for every i < n: src <= g - 0.5 - g / (2 n)
+  t.i1 = t.i0 + (t.i0 < g - 1 ? 1 : 0);
+  t.lam = src - (float)t.i0;
+  return t;
+}
+
+constexpr int kTokC = 512;   // channel limit of project_fuse_tokens_kernel: 8 accumulators per lane
+
+// Mode 1 of project_reduce_kernel for V frames at once, reading the encoder's token grids instead of their resized
+// [H,W,C] maps: one wave per voxel row, lanes stride over the channels.  The row's pixel list is ascending in the
+// frame-major pixel index (v*H + y)*W + x, so it is grouped by frame in frame order; every pixel's feature is the
+// bilinear sample of its frame's grid, the frame's samples are summed in list order, and the frame's mean is folded
+// into the running mean before the next frame starts.  The row is read once and written once, by this wave only.
+__global__ __launch_bounds__(256) void project_fuse_tokens_kernel(const float* __restrict__ tokens, int V, int gh,
+                                                                 int gw, int C, int H, int W,
+                                                                 const int64_t* __restrict__ order,
+                                                                 const int64_t* __restrict__ seg_off, int64_t n_rows,
+                                                                 float* __restrict__ scene,
+                                                                 int32_t* __restrict__ frames_hit) {
+#pragma clang fp contract(off)
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n_rows) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t p0 = seg_off[r], p1 = seg_off[r + 1];
+  if (p1 <= p0) {
+    if (lane == 0 && frames_hit) frames_hit[r] = 0;
+    return;
+  }
+  constexpr int kAcc = kTokC / 64;
+  const float sy = (float)gh / (float)H, sx = (float)gw / (float)W;
+  const unsigned hw = (unsigned)H * W, n_pix = hw * V;   // < 2^31: the entry point checks it
+  float run[kAcc], acc[kAcc];
+#pragma unroll
+  for (int j = 0; j < kAcc; ++j) {
+    const int c = lane + 64 * j;
+    run[j] = c < C ? scene[r * C + c] : 0.0f;
+    acc[j] = 0.0f;
+  }
+  // 32-bit index arithmetic, and one division per FRAME of the row: the list is ascending, so a pixel outside
+  // [base, base + hw) starts a later frame (or is the end of the list, which reads as n_pix)
+  unsigned base = 0;
+  int frame = 0, cnt = 0, n_frames = 0;
+  for (int64_t p = p0; p <= p1; ++p) {
+    const unsigned pix = p < p1 ? (unsigned)order[p] : n_pix;
+    if (pix - base >= hw) {
+      if (cnt > 0) {
+        const float den = (float)cnt + 10e-5f;
+#pragma unroll
+        for (int j = 0; j < kAcc; ++j) {
+          run[j] = (run[j] + acc[j] / den) / 2.0f;
+          acc[j] = 0.0f;
+        }
+        ++n_frames;
+        cnt = 0;
+      }
+      if (pix >= n_pix) break;
+      frame = (int)(pix / hw);
+      base = (unsigned)frame * hw;
+    }
+    const unsigned rem = pix - base;
+    const int y = (int)(rem / (unsigned)W), x = (int)(rem - (unsigned)y * (unsigned)W);
+    const Tap ty = bilinear_tap(y, sy, gh), tx = bilinear_tap(x, sx, gw);
+    const float ly1 = ty.lam, ly0 = 1.0f - ly1, lx1 = tx.lam, lx0 = 1.0f - lx1;
+    const float* g = tokens + (int64_t)frame * gh * gw * C;
+    const float* t00 = g + ((int64_t)ty.i0 * gw + tx.i0) * C;
+    const float* t01 = g + ((int64_t)ty.i0 * gw + tx.i1) * C;
+    const float* t10 = g + ((int64_t)ty.i1 * gw + tx.i0) * C;
+    const float* t11 = g + ((int64_t)ty.i1 * gw + tx.i1) * C;
+#pragma unroll
+    for (int j = 0; j < kAcc; ++j) {
+      const int c = lane + 64 * j;
+      if (c < C) acc[j] += ly0 * (lx0 * t00[c] + lx1 * t01[c]) + ly1 * (lx0 * t10[c] + lx1 * t11[c]);
+    }
+    ++cnt;
+  }
+#pragma unroll
+  for (int j = 0; j < kAcc; ++j) {
+    const int c = lane + 64 * j;
+    if (c < C) scene[r * C + c] = run[j];
+  }
+  if (lane == 0 && frames_hit) frames_hit[r] = n_frames;
+}
+
 __global__ __launch_bounds__(256) void project_preds_kernel(const int32_t* __restrict__ preds, int C,
                                                            const int32_t* __restrict__ hit, int64_t n_pix,
                                                            int32_t* __restrict__ out) {
@@ -310,6 +402,20 @@ int usc_project_reduce(const float* feats, int32_t c, const int64_t* order, cons
   hipLaunchKernelGGL(project_reduce_kernel, dim3((unsigned)ceil_div(n_rows, 4)), dim3(256), 0, as_stream(s), feats, c,
                      order, seg_off, n_rows, mode, out, num);
   USC_CHECK_LAUNCH("usc_project_reduce");
+  return 0;
+}
+
+int usc_project_fuse_tokens(const float* tokens, int32_t V, int32_t gh, int32_t gw, int32_t c, int32_t H, int32_t W,
+                            const int64_t* order, const int64_t* seg_off, int64_t n_rows, float* scene,
+                            int32_t* frames_hit, usc_stream_t s) {
+  USC_REQUIRE(c >= 1 && c <= kTokC, "usc_project_fuse_tokens: %d channels (1..%d)", c, kTokC);
+  USC_REQUIRE(V > 0 && gh > 0 && gw > 0 && H > 0 && W > 0, "usc_project_fuse_tokens: empty batch (%d,%d,%d,%d,%d)", V,
+              gh, gw, H, W);
+  USC_REQUIRE((int64_t)V * H * W < ((int64_t)1 << 31), "usc_project_fuse_tokens: more than 2^31 pixels per call");
+  if (n_rows <= 0) return 0;
+  hipLaunchKernelGGL(project_fuse_tokens_kernel, dim3((unsigned)ceil_div(n_rows, 4)), dim3(256), 0, as_stream(s),
+                     tokens, V, gh, gw, c, H, W, order, seg_off, n_rows, scene, frames_hit);
+  USC_CHECK_LAUNCH("usc_project_fuse_tokens");
   return 0;
 }
 

@@ -174,6 +174,20 @@ class DinoViT(nn.Module):
         return F.layer_norm(x, (EMBED_DIM,), self.norm.weight, self.norm.bias, self.norm.eps)[:, 0]
 
 
+def init_random_weights(vit: DinoViT, seed: int) -> DinoViT:
+    """Weights from a seed instead of the published checkpoint (smoke runs, benchmarks, tests: the features mean
+    nothing): every tensor N(0, 0.02) from a CPU generator, LayerNorm weights one and biases zero."""
+    gen = torch.Generator().manual_seed(int(seed))
+    with torch.no_grad():
+        for p in vit.parameters():
+            p.copy_(torch.randn(p.shape, generator=gen) * 0.02)
+        for m in vit.modules():
+            if isinstance(m, nn.LayerNorm):
+                m.weight.fill_(1.0)
+                m.bias.zero_()
+    return vit
+
+
 class DinoNet(nn.Module):
     """Interface of the reference's models/encoders_2d/dino.py: forward(images [1, n, 3, H, W]) ->
     (features, None) in 'descriptors' mode, (keys, queries) in 'attention' mode, each [1, n, H, W, 384] after the bilinear
@@ -217,6 +231,22 @@ class DinoNet(nn.Module):
             qkv = self.vit.qkv_at(input_images.reshape(-1, *input_images.shape[2:]), DEPTH - 1)
             key, query = qkv[:, 1:, 1].flatten(-2), qkv[:, 1:, 0].flatten(-2)
             return self._to_image(key, input_images.shape), self._to_image(query, input_images.shape)
+
+    def forward_tokens(self, input_images):
+        """images [1, n, 3, H, W] -> (key_tokens f32[n, gh, gw, 384], query_tokens or None): what `forward` resizes,
+        before the resize, in the same column orders ('descriptors': key of block `dino_vit_layer`, column d*6 + head;
+        'attention': key and query of the last block, column head*64 + d).  `Project2DFeaturesCUDA.fuse_frames_tokens`
+        samples these grids at the hit pixels, so the [n, H, W, 384] maps are never written."""
+        n, H, W = input_images.shape[1], input_images.shape[3], input_images.shape[4]
+        gh, gw = self.vit.grid(H, W)
+        grid = lambda t: t.reshape(n, gh, gw, -1).float().contiguous()
+        with torch.no_grad():
+            images = input_images.reshape(-1, *input_images.shape[2:])
+            if self.vit_feature == "attention":
+                qkv = self.vit.qkv_at(images, DEPTH - 1)
+                return grid(qkv[:, 1:, 1].flatten(-2)), grid(qkv[:, 1:, 0].flatten(-2))
+            qkv = self.vit.qkv_at(images, self.layer)
+            return grid(qkv[:, 1:, 1].permute(0, 1, 3, 2).flatten(-2)), None
 
     def forward(self, input_images):
         if self.vit_feature == "attention":

@@ -9,7 +9,8 @@ Two layers, both on the HIP library (no CPU path):
 * `Project2DFeaturesCUDA` (utils/cuda_utils/raycast_image.py:18-77): same constructor / forward and return
   values, but the occupancy comes from the coordinate hash (no dense grid is built), the hit pixels are reduced
   per voxel in a fixed order, and `fuse_frame` folds the caller's running mean over frames
-  (pseudo_masks/unscene3d_pseudo_main.py:303-330) into the same kernel.
+  (pseudo_masks/unscene3d_pseudo_main.py:303-330) into the same kernel; `fuse_frames_tokens` does that for several
+  frames per call from the image encoder's token grids, without the resized feature maps.
 """
 from __future__ import annotations
 
@@ -176,6 +177,11 @@ class Project2DFeaturesCUDA(nn.Module):
         if (H, W) != (self.image_height, self.image_width):
             raise RuntimeError(f"features are {H}x{W}, the projecter was built for "
                                f"{self.image_height}x{self.image_width}")
+        return self._cast_views(coords, view_matrix, intrinsic_params, want_seg)
+
+    def _cast_views(self, coords, view_matrix, intrinsic_params, want_seg):
+        """One ray cast of the module's image size over view_matrix [B, V, 4, 4] -> (n_rows, hit, seg)."""
+        H, W = self.image_height, self.image_width
         cmap, shift, bricks = self._scene_state(coords)
         local_views = view_matrix.detach().to(torch.float32).clone()
         local_views[:, :, :3, 3] -= shift.to(torch.float32)[:, None, :]
@@ -216,3 +222,32 @@ class Project2DFeaturesCUDA(nn.Module):
         num = torch.empty(n, dtype=torch.int32, device=scene_feats.device)
         project_reduce(feats, csr, n, scene_feats, num, mode="fuse")
         return num, (n, csr)
+
+    def fuse_frames_tokens(self, scene_feats, tokens, coords, view_matrices, intrinsic_params, hit_seg=None):
+        """`fuse_frame` for V frames in one call, from the encoder's token grids instead of their resized maps:
+        tokens f32[V, gh, gw, C] (C <= 512), view_matrices [1, V, 4, 4].  One ray cast over the V views, one CSR of the
+        hit pixels and one kernel, which samples every hit pixel bilinearly from its frame's grid (the resize of
+        `DinoNet._to_image`) and folds the frames into scene_feats in frame order, in place; voxels no frame hits are
+        not written.  The result has the same bits however the frames are grouped into calls.
+        -> (frames_hit i32[n]: frames of this call that hit the voxel, hit_seg); pass hit_seg back in to project a
+        second token map of the same frames (key and query features) without casting the rays again."""
+        _chk(scene_feats, torch.float32, "scene_feats")
+        _chk(tokens, torch.float32, "tokens")
+        if tokens.dim() != 4 or view_matrices.dim() != 4 or view_matrices.shape[0] != 1 \
+                or view_matrices.shape[1] != tokens.shape[0]:
+            raise RuntimeError("fuse_frames_tokens: tokens [V, gh, gw, C] and view_matrices [1, V, 4, 4] of one scene")
+        V, gh, gw, C = tokens.shape
+        H, W = self.image_height, self.image_width
+        if hit_seg is None:
+            if not coords.is_cuda:
+                raise RuntimeError("Project2DFeaturesCUDA needs CUDA tensors (there is no CPU path)")
+            n, _, seg = self._cast_views(coords, view_matrices, intrinsic_params, want_seg=True)
+            csr = ops.segment_csr(seg, n + 1)
+        else:
+            n, csr = hit_seg
+        if csr.order.shape[0] != V * H * W or csr.S != n + 1 or scene_feats.shape != (n, C):
+            raise RuntimeError("fuse_frames_tokens: shape mismatch")
+        frames_hit = torch.empty(n, dtype=torch.int32, device=scene_feats.device)
+        check(lib.usc_project_fuse_tokens(_ptr(tokens), V, gh, gw, C, H, W, _ptr(csr.order), _ptr(csr.seg_off), n,
+                                          _ptr(scene_feats), _ptr(frames_hit), _stream()), "usc_project_fuse_tokens")
+        return frames_hit, (n, csr)

@@ -24,7 +24,8 @@ def encode_scene_feats_3d(model, sinput, resolution_scale=2, precision="f32"):
         return enc.F[match].detach()
 
 
-def encode_scene_feats_2d(model, images, camera_poses, color_intrinsics, coords, projecter, attention=False):
+def encode_scene_feats_2d(model, images, camera_poses, color_intrinsics, coords, projecter, attention=False,
+                          frame_batch=None):
     """Image branch of `encode_scene_feats` (unscene3d_pseudo_main.py:287-330).
 
     model(img[1,1,c,h,w]) -> (key_features, query_features), each [1,1,H,W,C] (the 2D backbone is the caller's, e.g.
@@ -32,9 +33,31 @@ def encode_scene_feats_2d(model, images, camera_poses, color_intrinsics, coords,
     images [1,n_frames,c,h,w], camera_poses [1,n_frames,4,4], color_intrinsics [1,4]; coords int[n,4];
     projecter: `Project2DFeaturesCUDA`.  One ray cast per frame serves both feature maps; every frame's features
     are reduced per voxel and folded into the running mean in one kernel (`fuse_frame`).
+    frame_batch=k (an integer >= 1): the frames go, in order, in groups of k through `model.forward_tokens` and
+    `projecter.fuse_frames_tokens` — one encoder pass, one ray cast and one projection kernel per group, and the
+    resized [H,W,C] maps are never written; the model must have `forward_tokens` (DinoNet has).  The running mean folds
+    the same frames in the same order; the bilinear samples round differently from torch's resize.
     -> scene_key_feats (and scene_query_feats when `attention`), f32[n,C]."""
     n = coords.shape[0]
     scene_key = scene_query = None
+    if frame_batch is not None:
+        k = int(frame_batch)
+        if k < 1:
+            raise ValueError(f"frame_batch must be None or an integer >= 1, got {frame_batch!r}")
+        if not hasattr(model, "forward_tokens"):
+            raise RuntimeError("encode_scene_feats_2d(frame_batch=k) needs a model with forward_tokens "
+                               "(models.encoders_2d.DinoNet); frame_batch=None takes any model")
+        for i in range(0, images.shape[1], k):
+            key_tokens, query_tokens = model.forward_tokens(images[:, i:i + k])
+            if scene_key is None:
+                C = key_tokens.shape[-1]
+                scene_key = torch.zeros((n, C), dtype=torch.float32, device=coords.device)
+                scene_query = torch.zeros_like(scene_key) if attention else None
+            views = camera_poses[:1, i:i + k]
+            _, cast = projecter.fuse_frames_tokens(scene_key, key_tokens, coords, views, color_intrinsics)
+            if attention:
+                projecter.fuse_frames_tokens(scene_query, query_tokens, coords, views, color_intrinsics, hit_seg=cast)
+        return (scene_key, scene_query) if attention else scene_key
     with torch.no_grad():
         for i, img in enumerate(images[0]):
             key_features, query_features = model(img.unsqueeze(0).unsqueeze(0))

@@ -1,0 +1,326 @@
+"""ScanNet-style scan directories -> the scene files tools/pseudo_masks_run.py reads (reference
+pseudo_masks/datasets/scannet.py: `load_intrinsics` :199-216, `load_rgb_data` :126-154, `segment_mesh` :156-197,
+`prepare_scene_data` :234-283, voxelised by pseudo_masks/datasets/voxelizer.py:109-148).
+
+A scan directory `DIR/{scene}/` holds what the reference reads under `scannet_images_path/{scene}/`:
+
+    {scene}.txt               `key = value` lines: axisAlignment, colorHeight / colorWidth, fx/fy/mx/my_color
+    {scene}_vh_clean_2.ply    the coloured triangle mesh
+    color/*.jpg | *.png | *.npy   colour frames (.npy: uint8 [H, W, 3], already at the target size)
+    pose/*.txt                one 4x4 camera-to-world matrix per frame
+
+The readers are numpy only; Pillow is imported when a frame is a .jpg / .png, and only then.  The reference reads the
+same files through open3d, plyfile and torchvision.  `build_scene` joins the readers with the stages of the package:
+voxelisation (ME.utils.sparse_quantize), the mesh over-segmentation (felzenszwalb_cpp.segment_mesh), the image encoder
+and the ray-cast projection (pipeline.encode_scene_feats_2d).
+
+Not covered: the 3D modality (`pipeline.encode_scene_feats_3d` exists; add `feats_3d` to the file), depth
+images, label / instance columns, chunked scenes, the other datasets' layouts."""
+from __future__ import annotations
+
+import glob
+import os
+
+import numpy as np
+
+PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+             "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+             "double": "f8", "float64": "f8"}
+FRAME_SUFFIXES = (".jpg", ".png", ".npy")
+
+
+# ---------------------------------------------------------------------------------------------------- info and poses
+def read_scan_info(path, align=True):
+    """`{scene}.txt` (scannet.py:199-216): one `key = value` per line, numeric values as float arrays.
+    -> dict with axisAlignment f64[4,4] (identity when the key is absent or `align` is False, :210), colorHeight,
+    colorWidth (int), fx_color, fy_color, mx_color, my_color (float), and every other key as the reference keeps it (a
+    float array; text values, which the reference turns into empty arrays, stay strings)."""
+    info = {}
+    with open(path) as f:
+        for line in f:
+            if " = " not in line:
+                continue
+            key, val = line.split(" = ", 1)
+            try:
+                info[key.strip()] = np.array([float(t) for t in val.split()], np.float64)
+            except ValueError:
+                info[key.strip()] = val.strip()
+    axis = info.get("axisAlignment")
+    if align and isinstance(axis, np.ndarray):
+        if axis.size != 16:
+            raise ValueError(f"{path}: axisAlignment has {axis.size} values, expected 16")
+        info["axisAlignment"] = axis.reshape(4, 4)
+    else:
+        info["axisAlignment"] = np.identity(4)
+    for key, cast in (("colorHeight", int), ("colorWidth", int), ("fx_color", float), ("fy_color", float),
+                      ("mx_color", float), ("my_color", float)):
+        v = info.get(key)
+        if not isinstance(v, np.ndarray) or v.size != 1:
+            raise ValueError(f"{path}: needs one number for {key}")
+        info[key] = cast(v[0])
+    return info
+
+
+def read_pose(path):
+    """A 4x4 matrix as text, one row per line (utils/utils.py `load_matrix_from_txt`) -> f64[4,4].  ScanNet writes
+    `-inf` in every entry of a frame whose tracking was lost; those parse to non-finite values."""
+    with open(path) as f:
+        vals = [float(t) for t in f.read().split()]
+    if len(vals) != 16:
+        raise ValueError(f"{path}: {len(vals)} values, expected a 4x4 matrix")
+    return np.array(vals, np.float64).reshape(4, 4)
+
+
+def color_intrinsics(info, shape_hw):
+    """fx, fy, mx, my of the colour camera at the target image size, f64[4], as scannet.py:133-138 scales them:
+    color_scale = (H / colorHeight, W / colorWidth) and fx, mx take color_scale[0], fy, my take color_scale[1].  That
+    pairs fx and mx with the HEIGHT ratio and fy and my with the WIDTH ratio — the other way round from the axes they
+    belong to.  It is kept because the reference's features were produced with it; ScanNet's 1296x968 frames resized to
+    256x192 have ratios 0.1983 and 0.1975, so the two pairings differ by 0.4 %."""
+    H, W = shape_hw
+    scale = (H / info["colorHeight"], W / info["colorWidth"])
+    return np.array([info["fx_color"] * scale[0], info["fy_color"] * scale[1], info["mx_color"] * scale[0],
+                     info["my_color"] * scale[1]], np.float64)
+
+
+# --------------------------------------------------------------------------------------------------------------- PLY
+def _ply_header(f, path):
+    if f.readline().strip() != b"ply":
+        raise ValueError(f"{path}: not a PLY file")
+    fmt, elements = None, []
+    while True:
+        line = f.readline()
+        if not line:
+            raise ValueError(f"{path}: PLY header has no end_header")
+        t = line.decode("ascii", "replace").split()
+        if not t or t[0] in ("comment", "obj_info"):
+            continue
+        if t[0] == "end_header":
+            break
+        if t[0] == "format":
+            fmt = t[1]
+        elif t[0] == "element":
+            elements.append((t[1], int(t[2]), []))
+        elif t[0] == "property":
+            if not elements:
+                raise ValueError(f"{path}: PLY property before the first element")
+            types = t[2:4] if t[1] == "list" else t[1:2]
+            if any(ty not in PLY_TYPES for ty in types):
+                raise ValueError(f"{path}: unknown PLY property type in {' '.join(t)!r}")
+            elements[-1][2].append(("list", t[2], t[3], t[4]) if t[1] == "list" else ("scalar", t[1], t[2]))
+        else:
+            raise ValueError(f"{path}: unknown PLY header line {' '.join(t)!r}")
+    if fmt not in ("binary_little_endian", "ascii"):
+        raise ValueError(f"{path}: PLY format {fmt!r} is not covered (binary_little_endian and ascii are)")
+    return fmt, elements
+
+
+def _face_layout(props, path):
+    """The face element's record with every list holding 3 entries: (numpy dtype, name of the index field)."""
+    lists = [p for p in props if p[0] == "list"]
+    if len(lists) != 1 or lists[0][3] not in ("vertex_indices", "vertex_index"):
+        raise ValueError(f"{path}: the face element needs exactly one list property, vertex_indices")
+    if lists[0][1] not in ("uchar", "uint8", "int", "int32"):
+        raise ValueError(f"{path}: face list count type {lists[0][1]!r} is not covered (uchar and int are)")
+    fields = []
+    for p in props:
+        if p[0] == "list":
+            fields += [("_count", "<" + PLY_TYPES[p[1]]), ("_index", "<" + PLY_TYPES[p[2]], (3,))]
+        else:
+            fields.append((p[2], "<" + PLY_TYPES[p[1]]))
+    return np.dtype(fields)
+
+
+def read_ply_mesh(path):
+    """A coloured triangle mesh -> (vertices f32[V,3], colors f32[V,3] in [0,1], faces i32[F,3]); what the reference
+    takes from open3d's read_triangle_mesh (scannet.py:163-176).
+
+    Formats `binary_little_endian` and `ascii`.  Vertex properties are scalars of any standard PLY type (x, y, z, red,
+    green, blue are used, the others skipped; integer colours are divided by 255).  The face element has one list
+    property `vertex_indices` with a `uchar` or `int` count, and scalars beside it are skipped; the file is read as
+    fixed-size records of three indices, so a mesh of triangles never takes a per-face loop.  A face that is not a
+    triangle, another format (big endian) or an unknown property type raises ValueError with the file name."""
+    path = os.fspath(path)
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f, path)
+        vertex = faces = None
+        for name, count, props in elements:
+            if name == "face":
+                dt = _face_layout(props, path)
+            else:
+                if any(p[0] == "list" for p in props):
+                    raise ValueError(f"{path}: list property in element {name!r} is not covered")
+                dt = np.dtype([(p[2], "<" + PLY_TYPES[p[1]]) for p in props])
+            if fmt == "binary_little_endian":
+                buf = f.read(dt.itemsize * count)
+                rec = np.frombuffer(buf[:len(buf) // dt.itemsize * dt.itemsize], dtype=dt)
+                if name != "face" and rec.shape[0] != count:      # a short face element may be a face with > 3 indices
+                    raise ValueError(f"{path}: element {name!r} ends after {rec.shape[0]} of {count} records")
+            else:
+                rows = [f.readline().decode("ascii", "replace").split() for _ in range(count)]
+                width = sum(int(np.prod(dt[n].shape, dtype=np.int64)) for n in dt.names)
+                if name == "face":
+                    bad = [i for i, r in enumerate(rows) if not r or int(r[0]) != 3]
+                    if bad:
+                        raise ValueError(f"{path}: face {bad[0]} is not a triangle "
+                                         f"({rows[bad[0]][0] if rows[bad[0]] else 'no'} vertices)")
+                if any(len(r) != width for r in rows):
+                    raise ValueError(f"{path}: element {name!r} has a line that does not hold {width} values")
+                table = np.array(rows, dtype=np.float64).reshape(count, width)
+                rec = np.zeros(count, dtype=dt)
+                col = 0
+                for n in dt.names:
+                    w = int(np.prod(dt[n].shape, dtype=np.int64))
+                    rec[n] = table[:, col:col + w].reshape((count,) + dt[n].shape)
+                    col += w
+            if name == "vertex":
+                vertex = rec
+            elif name == "face":
+                counts = rec["_count"]
+                bad = np.nonzero(counts != 3)[0]
+                if bad.size:
+                    raise ValueError(f"{path}: face {int(bad[0])} is not a triangle ({int(counts[bad[0]])} vertices)")
+                if rec.shape[0] != count:
+                    raise ValueError(f"{path}: element 'face' ends after {rec.shape[0]} of {count} records")
+                faces = rec["_index"]
+    if vertex is None or faces is None:
+        raise ValueError(f"{path}: needs a vertex and a face element")
+    for n in ("x", "y", "z", "red", "green", "blue"):
+        if n not in vertex.dtype.names:
+            raise ValueError(f"{path}: vertex property {n!r} is missing")
+    vertices = np.stack([vertex["x"], vertex["y"], vertex["z"]], 1).astype(np.float32)
+    rgb = [vertex[n] for n in ("red", "green", "blue")]
+    colors = np.stack([c.astype(np.float64) / 255.0 if c.dtype.kind in "iu" else c.astype(np.float64) for c in rgb], 1)
+    if faces.size and (faces.min() < 0 or faces.max() >= vertices.shape[0]):
+        raise ValueError(f"{path}: face index outside [0, {vertices.shape[0]})")
+    return vertices, colors.astype(np.float32), np.ascontiguousarray(faces, dtype=np.int32)
+
+
+# ------------------------------------------------------------------------------------------------------------ frames
+def frame_files(color_dir, pose_dir, every=1):
+    """-> [(colour file, pose file)] in the reference's order: `sorted()` of the file names of each directory, paired by
+    position (scannet.py:142,149).  `sorted()` is LEXICOGRAPHIC: frames 0, 20, 100 come as 0, 100, 20.  The order is
+    kept because the scene features are a running pairwise mean over the frames (a later frame weighs more), so another
+    order gives other features.  The two lists must hold the same frame names; `every` keeps every k-th pair."""
+    colors = sorted((p for s in FRAME_SUFFIXES for p in glob.glob(os.path.join(color_dir, "*" + s))),
+                    key=os.path.basename)
+    poses = sorted(glob.glob(os.path.join(pose_dir, "*.txt")), key=os.path.basename)
+    stem = lambda p: os.path.splitext(os.path.basename(p))[0]
+    if [stem(p) for p in colors] != [stem(p) for p in poses]:
+        raise ValueError(f"{color_dir} and {pose_dir} do not hold the same frames "
+                         f"({len(colors)} colour files, {len(poses)} poses)")
+    return list(zip(colors, poses))[::max(1, int(every))]
+
+
+def load_image(path, shape_hw):
+    """One colour frame -> f32[3,H,W] in [-1, 1]: resized to (H, W) as scannet.py:122 does
+    (`Image.open(p).convert('RGB').resize((W, H), Image.BILINEAR)`), then / 255 (:144) and (x - 0.5) / 0.5 (:115).  A
+    .npy frame is uint8 [H, W, 3] at the target size already and needs no Pillow."""
+    H, W = shape_hw
+    if path.endswith(".npy"):
+        rgb = np.load(path)
+        if rgb.dtype != np.uint8 or rgb.shape != (H, W, 3):
+            raise ValueError(f"{path}: a .npy frame must be uint8 [{H}, {W}, 3], got {rgb.dtype} {list(rgb.shape)}")
+    else:
+        from PIL import Image
+        rgb = np.array(Image.open(path).convert("RGB").resize((W, H), Image.BILINEAR))
+    x = (rgb / 255.0).astype(np.float32)
+    x = (x - np.float32(0.5)) / np.float32(0.5)
+    return np.ascontiguousarray(x.transpose(2, 0, 1))
+
+
+def load_frames(color_dir, pose_dir, shape_hw, every=1, axis_alignment=None):
+    """-> (images f32[n,3,H,W], poses f64[n,4,4], n_dropped): the frames of `frame_files` (lexicographic order, see
+    there) as `load_image` reads them, with poses `axis_alignment @ pose` (scannet.py:152).  The intrinsics that go with
+    `shape_hw` come from `color_intrinsics`, which keeps the reference's pairing of fx with the height ratio.
+
+    Deviation: a frame whose pose is not finite (ScanNet writes -inf where tracking was lost) is dropped and counted in
+    n_dropped.  The reference casts such frames too; every ray of one is NaN and hits nothing."""
+    H, W = shape_hw
+    axis = np.identity(4) if axis_alignment is None else np.asarray(axis_alignment, np.float64)
+    images, poses, dropped = [], [], 0
+    for color_file, pose_file in frame_files(color_dir, pose_dir, every):
+        pose = read_pose(pose_file)
+        if not np.isfinite(pose).all():
+            dropped += 1
+            continue
+        images.append(load_image(color_file, shape_hw))
+        poses.append(axis @ pose)
+    if not images:
+        return np.zeros((0, 3, H, W), np.float32), np.zeros((0, 4, 4), np.float64), dropped
+    return np.stack(images), np.stack(poses), dropped
+
+
+# ------------------------------------------------------------------------------------------------------------- scene
+def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_min_verts=50, frame_batch=None,
+                attention=False, every=1, align=True, device="cuda"):
+    """One scan directory -> the arrays of a scene file (tools/pseudo_masks_run.py), as the reference's dataset and
+    `encode_scene_feats` produce them at test time (no augmentation):
+
+        coords            i32[N,4]   (0, x, y, z) voxel coordinates
+        colors            f32[N,3]   rgb / 255 - 0.5 of the kept vertices (scannet.py:281): the 3D backbone's input
+        feats_2d          f32[N,C]   running mean of the image features over the frames; all-zero rows = not seen
+        feats_2d_query    f32[N,C]   only with `attention`
+        segment_ids       i64[N]     felzenszwalb_cpp.segment_mesh(vertices, faces, colors, 0.005, segments_min_verts)
+        seg_connectivity  i64[E,2]
+        full_res_coords   f32[M,3]   the aligned mesh vertices, metres
+        voxel_size        float
+        frames_used, frames_dropped  int
+
+    The points are the mesh vertices, aligned with axisAlignment (:213-214).  They are voxelised as voxelizer.py:132-148
+    does with augmentation off and no clip bound: floor(xyz * (1 / voxel_size)) in float64 — a product with the
+    reciprocal, as the voxelisation matrix has it, not a division — and ME.utils.sparse_quantize(return_index=True).
+    Deviations: the kept row of a voxel is its FIRST vertex and the rows keep vertex order (this package's
+    sparse_quantize; the reference's MinkowskiEngine leaves the order to its hash map); the reference takes a vertex's
+    segment through a 1-NN search of the points against the mesh vertices (:186-191), which is the identity here since
+    the points are those vertices; frames with a non-finite pose are dropped (`load_frames`).
+    The camera translations are divided by the voxel size (:255-258; no rotation at test time), the frames run through
+    `pipeline.encode_scene_feats_2d(model, ..., frame_batch=frame_batch)` with `model` a models.encoders_2d.DinoNet."""
+    import torch
+
+    from .. import MinkowskiEngine as ME
+    from .. import felzenszwalb_cpp
+    from ..project_features_cuda import Project2DFeaturesCUDA
+    from .pipeline import encode_scene_feats_2d
+
+    dev = torch.device(device)
+    scene = os.path.basename(os.path.normpath(scan_dir))
+    info = read_scan_info(os.path.join(scan_dir, f"{scene}.txt"), align=align)
+    axis = info["axisAlignment"]
+    vertices, colors, faces = read_ply_mesh(os.path.join(scan_dir, f"{scene}_vh_clean_2.ply"))       # scannet.py:163
+    homo = np.hstack([vertices.astype(np.float64), np.ones((vertices.shape[0], 1))])
+    xyz = homo @ axis.T[:, :3]
+
+    grid = np.floor(xyz * (1.0 / voxel_size)).astype(np.int32)
+    _, kept = ME.utils.sparse_quantize(grid, return_index=True, device=dev)
+    kept = kept.cpu().numpy()
+    coords = np.concatenate([np.zeros((kept.shape[0], 1), np.int32), grid[kept]], 1)
+
+    seg, conn = felzenszwalb_cpp.segment_mesh(xyz.astype(np.float32), faces, colors, 0.005, int(segments_min_verts),
+                                              device=dev)
+
+    H, W = image_hw
+    images, poses, dropped = load_frames(os.path.join(scan_dir, "color"), os.path.join(scan_dir, "pose"), image_hw,
+                                         every=every, axis_alignment=axis)
+    poses = poses.copy()
+    poses[:, :3, 3] /= voxel_size
+    out = {"coords": coords, "colors": (colors[kept] - np.float32(0.5)).astype(np.float32)}
+    coords_d = torch.from_numpy(coords).to(dev)
+    feats = None
+    if images.shape[0]:
+        projecter = Project2DFeaturesCUDA(width=W, height=H, voxel_size=voxel_size)
+        intr = torch.from_numpy(color_intrinsics(info, image_hw).astype(np.float32)).to(dev).view(1, 4)
+        feats = encode_scene_feats_2d(model, torch.from_numpy(images).to(dev).unsqueeze(0),
+                                      torch.from_numpy(poses.astype(np.float32)).to(dev).unsqueeze(0), intr, coords_d,
+                                      projecter, attention=attention, frame_batch=frame_batch)
+    if feats is None:                                               # no usable frame: nothing was seen
+        zeros = torch.zeros((coords.shape[0], int(model.feature_dim)), dtype=torch.float32)
+        feats = (zeros, zeros.clone()) if attention else zeros
+    key, query = feats if attention else (feats, None)
+    out["feats_2d"] = key.cpu().numpy()
+    if attention:
+        out["feats_2d_query"] = query.cpu().numpy()
+    out.update(segment_ids=seg[kept].astype(np.int64), seg_connectivity=np.asarray(conn, np.int64).reshape(-1, 2),
+               full_res_coords=xyz.astype(np.float32), voxel_size=float(voxel_size),
+               frames_used=int(images.shape[0]), frames_dropped=int(dropped))
+    return out
