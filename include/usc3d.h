@@ -840,7 +840,9 @@ int usc_lsap_batch(const float* cost, int32_t n_prob, int32_t nr, int32_t nc,
 
 /* The set criterion on the device, per scene and for all L <= 16 prediction levels at once (reference
  * models/matcher.py:98-168 cost matrices; models/criterion.py:22-73, :138-216 losses, :194-200 DropLoss).  masks[l] /
- * dmasks[l]: the level's mask logits f32[S, ld] (ld >= Q columns, Q <= 128 queries) and their gradient; logits: class
+ * dmasks[l]: the level's mask logits f32[S, ld] (Q <= ld <= 256 columns, any value; Q <= 256 queries: above 128 queries
+ * or columns the launches take a second group of 128 columns, up to 128 they are what they always were) and their
+ * gradient; logits: class
  * logits addressed as logits[l*ls_level + q*ls_q + c], c < C; labels i64[T] (253 = ignore).
  * max_targets, 32 .. 128 (anything else is an error), is the caller's bound on T: T outside 1 .. max_targets is
  * refused before anything is launched (SetCriterion passes its device_max_targets, 32 unless opted in).  The target
@@ -853,9 +855,11 @@ int usc_lsap_batch(const float* cost, int32_t n_prob, int32_t nr, int32_t nc,
  *                              parts cmask / cdice [L,Q,T], nmat [L,Q,T] = sum_s sigmoid(x) tm, ssum [L,Q] =
  *                              sum_s sigmoid(x), logp [L,Q,C] = log softmax (kept for the losses and the backward).
  *                              Once per word, one word after the other on the stream: word w fills the columns 32w ..
- *                              (2 W launches); the workspace of usc_criterion_ws_bytes(L, S, T) is reused per word, so
- *                              above 32 targets it is the 32-target size.  A pair's entries do not depend on the
- *                              scene's other targets
+ *                              (2 W launches); the workspace of usc_criterion_ws_bytes_q(L, S, T, Q) is reused per word,
+ *                              so above 32 targets it is the 32-target size.  It is strided by the column count: 128 up
+ *                              to 128 queries (usc_criterion_ws_bytes(L, S, T), the same number), 256 above; ws_bytes
+ *                              below the size for this call's Q is refused.  A pair's entries do not depend on the
+ *                              scene's other targets or queries
  *   usc_criterion_drop_counts  DropLoss only, after usc_lsap_batch: counts i32[2,L,T] = per matched pair (row order of
  *                              src / tid) I = |pred & target| and F = |pred|, pred = (x > 0); integer sums, exact.
  *                              counts is zeroed here
@@ -874,6 +878,7 @@ int usc_lsap_batch(const float* cost, int32_t n_prob, int32_t nr, int32_t nc,
  * SetCriterion.loss_labels / loss_masks, with DropLoss `(fg * tm).sum(1) / (fg + tm).sum(1) >= thresh` on the gathered
  * [T, S] masks, and above 32 targets the operator path's device->host copy and scipy solve per level and scene. */
 int64_t usc_criterion_ws_bytes(int32_t L, int32_t S, int32_t T);
+int64_t usc_criterion_ws_bytes_q(int32_t L, int32_t S, int32_t T, int32_t Q);
 int usc_criterion_target_bits(const uint8_t* tm, int32_t T, int32_t max_targets, int32_t S,
                               uint32_t* bits, int32_t* cnt, usc_stream_t s);
 int usc_criterion_costs(const float* const* masks, int32_t L, int32_t ld, int32_t S,

@@ -190,6 +190,7 @@ SIGNATURES = {
     "usc_attn_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _i64, _p]),
     "usc_lsap_batch": (C.c_int, [_p, _i32, _i32, _i32, _p, _p, _p, _p]),
     "usc_criterion_ws_bytes": (_i64, [_i32, _i32, _i32]),
+    "usc_criterion_ws_bytes_q": (_i64, [_i32, _i32, _i32, _i32]),
     "usc_criterion_target_bits": (C.c_int, [_p, _i32, _i32, _i32, _p, _p, _p]),
     "usc_criterion_costs": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _i64, _i32, _p, _f32, _f32,
                                       _f32, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),

@@ -47,7 +47,9 @@ def default_config():
                  "oversample_ratio": 3.0, "importance_sample_ratio": 0.75, "class_weights": -1, "directions": "xyz",
                  "use_droploss": False, "droploss_iou_thresh": 0.1,
                  # most targets per scene the device criterion takes (32 .. 128; above 32: opt-in)
-                 "device_max_targets": 32},
+                 "device_max_targets": 32,
+                 # most queries the device criterion takes (128 .. 256; above 128: opt-in)
+                 "device_max_queries": 128},
         "optimizer": {"lr": 1e-4},
         "trainer": {"max_epochs": 601, "check_val_every_n_epoch": 5},
     })

@@ -10,6 +10,9 @@ models/criterion.py::_FusedCriterion wraps these three functions for autograd, t
 
 A scene has at most max_targets targets (32 unless the caller opts in, at most 128); the library refuses more.  Up to 32
 targets a row's target membership is one 32-bit word, above that W = ceil(T / 32) words per row, word-major.
+Queries and table columns: up to 256 (Q <= ld <= 256, any ld); above 128 the library's launches take a second group of
+128 columns and the workspace is the larger one of usc_criterion_ws_bytes_q.  There is no bound on Q here: the library
+refuses what it cannot take (SetCriterion admits more than 128 queries only with device_max_queries).
 
 No device->host copy, no host solve, no synchronisation.  Inputs are contiguous HIP tensors of the stated dtypes; the
 callers see to that, nothing is checked or converted here.  Every output and the
@@ -82,7 +85,7 @@ def scene_forward(tabs, tm, labels, logits, b, cost_weights, class_w, noobj, par
     cmask, cdice, nmat = alloc((3, L, Q, T), _F32).unbind(0)
     ssum = alloc((L, Q), _F32)
     logp = alloc((L, Q, NC), _F32)
-    wsb = lib.usc_criterion_ws_bytes(L, S, T)
+    wsb = lib.usc_criterion_ws_bytes_q(L, S, T, Q)
     ws = alloc((wsb,), torch.uint8)
     lg = logits[:, b]                                                           # [L,Q,C] view: strides (B*Q*C, C, 1)
     w_mask, w_class, w_dice = cost_weights

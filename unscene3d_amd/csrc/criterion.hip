@@ -408,11 +408,18 @@ int usc_lsap_batch(const float* cost, int32_t n_prob, int32_t nr, int32_t nc, in
 // other targets the scene has; ssum / logp do not depend on the word and are rewritten with the same bits by every
 // word.  No TMAX above 32: 3 TMAX accumulators per lane are 96 registers already.
 // Everything after the costs looks a target's bit up as word tid >> 5, bit tid & 31.
+// Queries: one column per thread of a 128-thread workgroup.  Up to 128 queries and columns that is one workgroup per
+// (chunk, level); above, up to 256, a grid dimension adds a second group of 128 columns, and the workspace is strided by
+// 256 columns instead of 128.  No sum runs across columns except the cross entropy of crit_loss, so a query's entries do
+// not depend on the other queries; crit_loss runs 256 threads and a 256-slot tree above 128 queries.
 namespace usc {
 namespace {
 
 constexpr int kCritMaxLevels = 16;
-constexpr int kCritCols = 128;          // queries per level (one per lane of the 128-thread workgroups)
+constexpr int kCritGroup = 128;         // query columns per workgroup, one per thread
+constexpr int kCritCols = 256;          // queries per level at most: above 128 a launch takes a second column group
+// the column stride of the partial-sum workspace: 128 up to 128 queries (the layout those always had), 256 above
+inline int crit_stride(int Q) { return Q <= kCritGroup ? kCritGroup : kCritCols; }
 struct CritLevels { const float* x[kCritMaxLevels]; float* dx[kCritMaxLevels]; };
 
 // workspace rows per (level, chunk): sum softplus | sum sigmoid | per target: sum x*tm | sum sigmoid*tm | BCE numerator
@@ -435,11 +442,14 @@ __global__ __launch_bounds__(256) void crit_target_bits_kernel(const uint8_t* __
   }
 }
 
-template <int TMAX>
+// COLS: the workspace's column stride, crit_stride(Q) (a template argument, so that the 128-column instance is the
+// code it always was: with a run-time stride crit_cost<32> needs 256 registers instead of 203)
+template <int TMAX, int COLS>
 __global__ __launch_bounds__(128) void crit_partial_kernel(CritLevels lv, int ld, int S, int Q,
                                                            const uint32_t* __restrict__ bits, int nchunk,
                                                            float* __restrict__ partial) {
-  const int q = threadIdx.x, chunk = blockIdx.x, l = blockIdx.y;
+  const int q = blockIdx.z * kCritGroup + threadIdx.x, chunk = blockIdx.x, l = blockIdx.y;
+  constexpr int cols = COLS;
   const float* __restrict__ X = lv.x[l];
   float nsum = 0.f, ssum = 0.f, xs[TMAX], gs[TMAX], bce[TMAX];
 #pragma unroll
@@ -464,14 +474,14 @@ __global__ __launch_bounds__(128) void crit_partial_kernel(CritLevels lv, int ld
       }
     }
   }
-  float* dst = partial + ((int64_t)(l * nchunk + chunk) * kCritRows<TMAX>) * kCritCols + q;
+  float* dst = partial + ((int64_t)(l * nchunk + chunk) * kCritRows<TMAX>) * cols + q;
   dst[0] = nsum;
-  dst[kCritCols] = ssum;
+  dst[cols] = ssum;
 #pragma unroll
   for (int t = 0; t < TMAX; ++t) {
-    dst[(2 + t) * kCritCols] = xs[t];
-    dst[(2 + TMAX + t) * kCritCols] = gs[t];
-    dst[(2 + 2 * TMAX + t) * kCritCols] = bce[t];
+    dst[(2 + t) * cols] = xs[t];
+    dst[(2 + TMAX + t) * cols] = gs[t];
+    dst[(2 + 2 * TMAX + t) * cols] = bce[t];
   }
 }
 
@@ -490,22 +500,23 @@ struct CritCostArgs {
   float* logp;      // [L, Q, C]  log softmax of the class logits
 };
 
-template <int TMAX>
+template <int TMAX, int COLS>
 __global__ __launch_bounds__(128) void crit_cost_kernel(CritCostArgs a) {
-  const int q = threadIdx.x, l = blockIdx.x;
+  const int q = blockIdx.y * kCritGroup + threadIdx.x, l = blockIdx.x;
   if (q >= a.Q) return;
+  constexpr int cols = COLS;
   float nsum = 0.f, ssum = 0.f, xs[TMAX], gs[TMAX], bce[TMAX];
 #pragma unroll
   for (int t = 0; t < TMAX; ++t) { xs[t] = 0.f; gs[t] = 0.f; bce[t] = 0.f; }
   for (int c = 0; c < a.nchunk; ++c) {
-    const float* src = a.partial + ((int64_t)(l * a.nchunk + c) * kCritRows<TMAX>) * kCritCols + q;
+    const float* src = a.partial + ((int64_t)(l * a.nchunk + c) * kCritRows<TMAX>) * cols + q;
     nsum += src[0];
-    ssum += src[kCritCols];
+    ssum += src[cols];
 #pragma unroll
     for (int t = 0; t < TMAX; ++t) {
-      xs[t] += src[(2 + t) * kCritCols];
-      gs[t] += src[(2 + TMAX + t) * kCritCols];
-      bce[t] += src[(2 + 2 * TMAX + t) * kCritCols];
+      xs[t] += src[(2 + t) * cols];
+      gs[t] += src[(2 + TMAX + t) * cols];
+      bce[t] += src[(2 + 2 * TMAX + t) * cols];
     }
   }
   // class part: log softmax over the C logits of this query
@@ -541,19 +552,20 @@ __global__ __launch_bounds__(128) void crit_cost_kernel(CritCostArgs a) {
 // and `pred_foreground + target_mask` on bool tensors are AND and OR).  Grid (32-row chunk, level), one column per
 // thread; a matched column counts its foreground rows (x > 0: a NaN logit is not foreground) and those of them inside
 // its target, in integers, and adds them to counts i32[2, L, T] (I | F, pair order = the row order of src / tid), which
-// the caller has zeroed.  Columns >= Q are never read.
+// the caller has zeroed.  Columns >= Q are never read.  Above 128 columns blockIdx.z is the column group; every
+// workgroup builds the whole query -> pair map.
 __global__ __launch_bounds__(128) void crit_drop_counts_kernel(CritLevels lv, int ld, int S, int Q, int T, int L,
                                                                const uint32_t* __restrict__ bits_all,
                                                                const int64_t* __restrict__ src,
                                                                const int64_t* __restrict__ tid,
                                                                int32_t* __restrict__ counts) {
   __shared__ int pmap[kCritCols];
-  const int col = threadIdx.x, chunk = blockIdx.x, l = blockIdx.y;
-  pmap[col] = -1;
+  const int tx = threadIdx.x, col = blockIdx.z * kCritGroup + tx, chunk = blockIdx.x, l = blockIdx.y;
+  for (int e = tx; e < kCritCols; e += kCritGroup) pmap[e] = -1;
   __syncthreads();
-  if (col < T) {
-    const int q = (int)src[(int64_t)l * T + col];
-    if (q >= 0 && q < kCritCols) pmap[q] = col;
+  if (tx < T) {
+    const int q = (int)src[(int64_t)l * T + tx];
+    if (q >= 0 && q < kCritCols) pmap[q] = tx;
   }
   __syncthreads();
   const int p = col < Q ? pmap[col] : -1;
@@ -575,9 +587,10 @@ __global__ __launch_bounds__(128) void crit_drop_counts_kernel(CritLevels lv, in
 }
 
 // one workgroup per level: losses of the matched pairs + weighted cross entropy.  DROP: the pair weights of DropLoss
-// from `counts` (crit_drop_counts) and the target sizes `cnt`, written to wts f32[L, T] in pair order
-template <bool DROP>
-__global__ __launch_bounds__(128) void crit_loss_kernel(const float* __restrict__ cmask, const float* __restrict__ cdice,
+// from `counts` (crit_drop_counts) and the target sizes `cnt`, written to wts f32[L, T] in pair order.  COLS threads:
+// 128 up to 128 queries, 256 above (the cross-entropy sums are a fixed pairwise tree over COLS slots)
+template <bool DROP, int COLS>
+__global__ __launch_bounds__(COLS) void crit_loss_kernel(const float* __restrict__ cmask, const float* __restrict__ cdice,
                                                         const float* __restrict__ logp, const int64_t* __restrict__ src,
                                                         const int64_t* __restrict__ tid, const int64_t* __restrict__ labels,
                                                         const float* __restrict__ class_w, int Q, int T, int C, int noobj,
@@ -585,8 +598,8 @@ __global__ __launch_bounds__(128) void crit_loss_kernel(const float* __restrict_
                                                         const int32_t* __restrict__ counts,
                                                         const int32_t* __restrict__ cnt, float thresh,
                                                         float* __restrict__ wts) {
-  __shared__ int tc[kCritCols];
-  __shared__ float rnum[kCritCols], rden[kCritCols];
+  __shared__ int tc[COLS];
+  __shared__ float rnum[COLS], rden[COLS];
   const int q = threadIdx.x, l = blockIdx.x;
   tc[q] = noobj;
   __syncthreads();
@@ -606,7 +619,7 @@ __global__ __launch_bounds__(128) void crit_loss_kernel(const float* __restrict_
   rnum[q] = num;
   rden[q] = den;
   __syncthreads();
-  for (int o = kCritCols / 2; o > 0; o >>= 1) {          // fixed pairwise tree
+  for (int o = COLS / 2; o > 0; o >>= 1) {               // fixed pairwise tree
     if (q < o) { rnum[q] += rnum[q + o]; rden[q] += rden[q + o]; }
     __syncthreads();
   }
@@ -663,16 +676,16 @@ struct CritBwdArgs {
   const float* wts;         // DropLoss: pair weights [L, T] (crit_bwd_masks_kernel<true> only)
 };
 
-// d loss / d mask logits of every level: grid (chunk, level), one column per thread, full padded width written.
-// DROP: the column of a pair with weight 0 is written as zeros, like an unmatched one
+// d loss / d mask logits of every level: grid (chunk, level, 128-column group), one column per thread, full padded
+// width written.  DROP: the column of a pair with weight 0 is written as zeros, like an unmatched one
 template <bool DROP>
 __global__ __launch_bounds__(128) void crit_bwd_masks_kernel(CritBwdArgs a) {
   __shared__ int qmap[kCritCols];
-  const int col = threadIdx.x, chunk = blockIdx.x, l = blockIdx.y;
-  qmap[col] = -1;
+  const int tx = threadIdx.x, col = blockIdx.z * kCritGroup + tx, chunk = blockIdx.x, l = blockIdx.y;
+  for (int e = tx; e < kCritCols; e += kCritGroup) qmap[e] = -1;
   __syncthreads();
-  if (col < a.T && !(DROP && a.wts[(int64_t)l * a.T + col] == 0.f))
-    qmap[(int)a.src[(int64_t)l * a.T + col]] = (int)a.tid[(int64_t)l * a.T + col];
+  if (tx < a.T && !(DROP && a.wts[(int64_t)l * a.T + tx] == 0.f))
+    qmap[(int)a.src[(int64_t)l * a.T + tx]] = (int)a.tid[(int64_t)l * a.T + tx];
   __syncthreads();
   if (col >= a.ld) return;
   const int t = col < a.Q ? qmap[col] : -1;
@@ -704,7 +717,7 @@ __global__ __launch_bounds__(128) void crit_bwd_logits_kernel(const float* __res
                                                               const float* __restrict__ gtable,
                                                               const float* __restrict__ den_tot, int Q, int C,
                                                               int64_t ls_level, int64_t ls_q, float* __restrict__ dlogits) {
-  const int q = threadIdx.x, l = blockIdx.x;
+  const int q = blockIdx.y * kCritGroup + threadIdx.x, l = blockIdx.x;
   if (q >= Q) return;
   const int tc = tcls[(int64_t)l * Q + q];
   const float w = tc == 253 ? 0.f : class_w[tc];
@@ -717,8 +730,15 @@ __global__ __launch_bounds__(128) void crit_bwd_logits_kernel(const float* __res
 template <int TMAX>
 static void launch_cost(const CritLevels& lv, int L, int ld, int S, int Q, const uint32_t* bits, int nchunk,
                         float* partial, const CritCostArgs& ca, hipStream_t st) {
-  hipLaunchKernelGGL(crit_partial_kernel<TMAX>, dim3(nchunk, L), dim3(128), 0, st, lv, ld, S, Q, bits, nchunk, partial);
-  hipLaunchKernelGGL(crit_cost_kernel<TMAX>, dim3(L), dim3(128), 0, st, ca);
+  if (Q <= kCritGroup) {
+    hipLaunchKernelGGL((crit_partial_kernel<TMAX, kCritGroup>), dim3(nchunk, L), dim3(kCritGroup), 0, st, lv, ld, S, Q, bits,
+                       nchunk, partial);
+    hipLaunchKernelGGL((crit_cost_kernel<TMAX, kCritGroup>), dim3(L), dim3(kCritGroup), 0, st, ca);
+  } else {
+    hipLaunchKernelGGL((crit_partial_kernel<TMAX, kCritCols>), dim3(nchunk, L, 2), dim3(kCritGroup), 0, st, lv, ld, S, Q,
+                       bits, nchunk, partial);
+    hipLaunchKernelGGL((crit_cost_kernel<TMAX, kCritCols>), dim3(L, 2), dim3(kCritGroup), 0, st, ca);
+  }
 }
 
 static int tmax_of(int T) { return T <= 8 ? 8 : (T <= 16 ? 16 : 32); }
@@ -728,10 +748,11 @@ static int tmax_of(int T) { return T <= 8 ? 8 : (T <= 16 ? 16 : 32); }
 
 extern "C" {
 
-int64_t usc_criterion_ws_bytes(int32_t L, int32_t S, int32_t T) {
+int64_t usc_criterion_ws_bytes_q(int32_t L, int32_t S, int32_t T, int32_t Q) {
   const int64_t nchunk = usc::ceil_div(S, 32);
-  return usc::align_up((int64_t)L * nchunk * (3 * usc::tmax_of(T) + 2) * usc::kCritCols * 4, 256);
+  return usc::align_up((int64_t)L * nchunk * (3 * usc::tmax_of(T) + 2) * usc::crit_stride(Q) * 4, 256);
 }
+int64_t usc_criterion_ws_bytes(int32_t L, int32_t S, int32_t T) { return usc_criterion_ws_bytes_q(L, S, T, 128); }
 
 // max_targets (32 .. 128) is the caller's bound on T: a scene above it is refused here, before any launch.  Up to 32
 // targets the bits are one word per row; above, W = ceil(T / 32) words, word-major, through the same kernels.
@@ -758,12 +779,13 @@ int usc_criterion_costs(const float* const* masks, int32_t L, int32_t ld, int32_
   using namespace usc;
   USC_REQUIRE(max_targets >= 32 && max_targets <= 128, "usc_criterion_costs: max_targets %d is outside 32..128",
               (int)max_targets);
-  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && T >= 1 && T <= max_targets &&
-                  (T <= 32 || T <= Q) && S >= 1 && C >= 1,
-              "usc_criterion_costs: needs <= 16 levels, <= 128 queries, 1..%d targets, above 32 not more than queries",
-              (int)max_targets);
+  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && ld <= kCritCols && T >= 1 &&
+                  T <= max_targets && (T <= 32 || T <= Q) && S >= 1 && C >= 1,
+              "usc_criterion_costs: needs <= 16 levels, <= 256 queries and columns, 1..%d targets, above 32 not more than "
+              "queries", (int)max_targets);
   USC_REQUIRE(masks && bits && cnt && logits && labels && cost && cmask && cdice && nmat && ssum && logp && ws &&
-                  ws_bytes >= usc_criterion_ws_bytes(L, S, T), "usc_criterion_costs: bad argument");
+                  ws_bytes >= usc_criterion_ws_bytes_q(L, S, T, Q),
+              "usc_criterion_costs: bad argument (null pointer, or a workspace below usc_criterion_ws_bytes_q)");
   CritLevels lv{};
   for (int l = 0; l < L; ++l) { USC_REQUIRE(masks[l], "usc_criterion_costs: null level"); lv.x[l] = masks[l]; }
   const int nchunk = (int)ceil_div(S, 32);
@@ -790,16 +812,17 @@ int usc_criterion_drop_counts(const float* const* masks, int32_t L, int32_t ld, 
   using namespace usc;
   USC_REQUIRE(max_targets >= 32 && max_targets <= 128, "usc_criterion_drop_counts: max_targets %d is outside 32..128",
               (int)max_targets);
-  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && T >= 1 && T <= max_targets &&
-                  T <= Q && S >= 1,
-              "usc_criterion_drop_counts: needs <= 16 levels, <= 128 queries, 1..%d targets", (int)max_targets);
+  USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && ld <= kCritCols && T >= 1 &&
+                  T <= max_targets && T <= Q && S >= 1,
+              "usc_criterion_drop_counts: needs <= 16 levels, <= 256 queries and columns, 1..%d targets, not more than "
+              "queries", (int)max_targets);
   USC_REQUIRE(masks && bits && src && tid && counts, "usc_criterion_drop_counts: null argument");
   CritLevels lv{};
   for (int l = 0; l < L; ++l) { USC_REQUIRE(masks[l], "usc_criterion_drop_counts: null level"); lv.x[l] = masks[l]; }
   hipStream_t st = as_stream(s);
   (void)hipMemsetAsync(counts, 0, (size_t)2 * L * T * 4, st);
-  hipLaunchKernelGGL(crit_drop_counts_kernel, dim3((unsigned)ceil_div(S, 32), L), dim3(128), 0, st, lv, (int)ld, (int)S,
-                     (int)Q, (int)T, (int)L, bits, src, tid, counts);
+  hipLaunchKernelGGL(crit_drop_counts_kernel, dim3((unsigned)ceil_div(S, 32), L, (unsigned)ceil_div(Q, kCritGroup)),
+                     dim3(kCritGroup), 0, st, lv, (int)ld, (int)S, (int)Q, (int)T, (int)L, bits, src, tid, counts);
   USC_CHECK_LAUNCH("usc_criterion_drop_counts");
   return USC_OK;
 }
@@ -813,19 +836,19 @@ int usc_criterion_losses(const float* cmask, const float* cdice, const float* lo
               (int)max_targets);
   USC_REQUIRE(L >= 1 && Q >= 1 && Q <= kCritCols && T >= 1 && T <= max_targets && T <= Q && C >= 1 && noobj >= 0 &&
                   noobj < C,
-              "usc_criterion_losses: bad sizes (needs <= 128 queries, 1..%d targets, not more than queries)",
+              "usc_criterion_losses: bad sizes (needs <= 256 queries, 1..%d targets, not more than queries)",
               (int)max_targets);
   USC_REQUIRE(cmask && cdice && logp && src && tid && labels && class_w && tcls && part,
               "usc_criterion_losses: null argument");
   USC_REQUIRE((counts && cnt && wts) || (!counts && !cnt && !wts),
               "usc_criterion_losses: counts, cnt and wts go together (all three, or none for no DropLoss)");
-  if (wts)
-    hipLaunchKernelGGL(crit_loss_kernel<true>, dim3(L), dim3(128), 0, as_stream(s), cmask, cdice, logp, src, tid, labels,
-                       class_w, (int)Q, (int)T, (int)C, (int)noobj, tcls, part, counts, cnt, thresh, wts);
-  else
-    hipLaunchKernelGGL(crit_loss_kernel<false>, dim3(L), dim3(128), 0, as_stream(s), cmask, cdice, logp, src, tid, labels,
-                       class_w, (int)Q, (int)T, (int)C, (int)noobj, tcls, part, (const int32_t*)nullptr,
-                       (const int32_t*)nullptr, 0.f, (float*)nullptr);
+  // the 128-thread instance and its 128-slot tree up to 128 queries, the 256-thread one above
+#define USC_CRIT_LOSS(DROP, COLS)                                                                                       \
+  hipLaunchKernelGGL((crit_loss_kernel<DROP, COLS>), dim3(L), dim3(COLS), 0, as_stream(s), cmask, cdice, logp, src, tid, \
+                     labels, class_w, (int)Q, (int)T, (int)C, (int)noobj, tcls, part, counts, cnt, wts ? thresh : 0.f, wts)
+  if (Q <= kCritGroup) { if (wts) USC_CRIT_LOSS(true, kCritGroup); else USC_CRIT_LOSS(false, kCritGroup); }
+  else { if (wts) USC_CRIT_LOSS(true, kCritCols); else USC_CRIT_LOSS(false, kCritCols); }
+#undef USC_CRIT_LOSS
   USC_CHECK_LAUNCH("usc_criterion_losses");
   return USC_OK;
 }
@@ -849,7 +872,7 @@ int usc_criterion_backward(const float* const* masks, float* const* dmasks, int3
               (int)max_targets);
   USC_REQUIRE(L >= 1 && L <= kCritMaxLevels && Q >= 1 && Q <= kCritCols && ld >= Q && ld <= kCritCols && T >= 1 &&
                   T <= max_targets && (T <= 32 || T <= Q) && S >= 1 && C >= 1,
-              "usc_criterion_backward: bad sizes (needs <= 16 levels, <= 128 queries and columns, 1..%d targets, above 32 "
+              "usc_criterion_backward: bad sizes (needs <= 16 levels, <= 256 queries and columns, 1..%d targets, above 32 "
               "not more than queries)", (int)max_targets);
   USC_REQUIRE(masks && dmasks && bits && cnt && src && tid && nmat && ssum && logp && tcls && class_w && gtable &&
                   den_tot && dlogits, "usc_criterion_backward: null argument");
@@ -862,10 +885,11 @@ int usc_criterion_backward(const float* const* masks, float* const* dmasks, int3
   a.ld = ld; a.S = S; a.Q = Q; a.T = T; a.nchunk = (int)ceil_div(S, 32);
   a.bits = bits; a.cnt = cnt; a.src = src; a.tid = tid; a.nmat = nmat; a.ssum = ssum; a.gtable = gtable; a.wts = wts;
   hipStream_t st = as_stream(s);
-  if (wts) hipLaunchKernelGGL(crit_bwd_masks_kernel<true>, dim3(a.nchunk, L), dim3(128), 0, st, a);
-  else hipLaunchKernelGGL(crit_bwd_masks_kernel<false>, dim3(a.nchunk, L), dim3(128), 0, st, a);
-  hipLaunchKernelGGL(crit_bwd_logits_kernel, dim3(L), dim3(128), 0, st, logp, tcls, class_w, gtable, den_tot, (int)Q, (int)C,
-                     ls_level, ls_q, dlogits);
+  const dim3 gm(a.nchunk, L, (unsigned)ceil_div(ld, kCritGroup));      // every column below ld is written
+  if (wts) hipLaunchKernelGGL(crit_bwd_masks_kernel<true>, gm, dim3(kCritGroup), 0, st, a);
+  else hipLaunchKernelGGL(crit_bwd_masks_kernel<false>, gm, dim3(kCritGroup), 0, st, a);
+  hipLaunchKernelGGL(crit_bwd_logits_kernel, dim3(L, (unsigned)ceil_div(Q, kCritGroup)), dim3(kCritGroup), 0, st, logp, tcls,
+                     class_w, gtable, den_tot, (int)Q, (int)C, ls_level, ls_q, dlogits);
   USC_CHECK_LAUNCH("usc_criterion_backward");
   return USC_OK;
 }

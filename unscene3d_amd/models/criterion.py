@@ -11,11 +11,13 @@ reference line by line.  `SetCriterion.forward` takes one of three paths:
   (`_plain_losses`), float32 HIP predictions with 1-16 levels and at most 128 queries, and per scene 1-32 targets whose
   masks and labels are on the device.  `SetCriterion(device_max_targets=N)`, 32 <= N <= 128 (config:
   `loss.device_max_targets`), raises the 32 to min(N, queries): such scenes take one pass of the cost
-  kernels per 32 targets (criterion_device.py).
+  kernels per 32 targets (criterion_device.py).  `SetCriterion(device_max_queries=N)`, 128 <= N <= 256 (config:
+  `loss.device_max_queries`), raises the 128 queries to N: above 128 queries or table columns the kernels take a second
+  group of 128 columns (csrc/criterion.hip).
 * batched operators: `match_all_levels` builds all levels' cost matrices with torch operators and copies them to the host
   in ONE transfer (the reference syncs 13*B times), scipy solves them, `_batched_losses` computes all levels at once.
   Runs for `_plain_losses` inputs the device path does not take (CPU tensors, more than `device_max_targets` targets,
-  ...); on HIP tensors it warns once.
+  more than `device_max_queries` queries, ...); on HIP tensors it warns once.
 * per level: `get_loss` level by level, as the reference does.  Runs for everything else: point sub-sampling, the
   noise-robust loss, another list of losses, or imposed assignments of unequal length."""
 import os
@@ -44,8 +46,8 @@ FUSED = os.environ.get("USC3D_FUSED_CRITERION", "1") == "1"
 class _FusedCriterion(torch.autograd.Function):
     """Matching + losses of all prediction levels on the device: the autograd wrapper of criterion_device.scene_forward /
     table / scene_backward (the launches are described there).
-    Inputs: class logits f32[L,B,Q,C] and, per scene and level, the mask logits f32[S_b, ld] (ld >= Q: the padded
-    tables of models.mask3d._mask_logits are taken as they are).  Output: the [L*4] loss table
+    Inputs: class logits f32[L,B,Q,C] and, per scene and level, the mask logits f32[S_b, ld] (Q <= ld <= 256: the
+    padded tables of models.mask3d._mask_logits are taken as they are).  Output: the [L*4] loss table
     (loss_ce, loss_mask, loss_dice, loss_noise_robust = 0 per level).  With `crit.use_droploss` (reference
     models/criterion.py:194-200) the 0 / 1 pair weights stay on the device (`crit.last_drop_weights`)."""
 
@@ -115,7 +117,7 @@ def _loss_dict(flat, L):
 class SetCriterion(nn.Module):
     def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses, num_points, oversample_ratio,
                  importance_sample_ratio, class_weights, directions="xyz", use_droploss=False,
-                 droploss_iou_thresh=0.1, device_max_targets=32):
+                 droploss_iou_thresh=0.1, device_max_targets=32, device_max_queries=128):
         super().__init__()
         # the most targets per scene the device criterion takes (32: one word of target bits per row; up to 128, opt-in:
         # up to four).  Scenes above it, or above the number of queries, take the operator path
@@ -123,6 +125,12 @@ class SetCriterion(nn.Module):
                 or not 32 <= device_max_targets <= 128:
             raise ValueError(f"SetCriterion: device_max_targets must be an integer in 32 .. 128, not {device_max_targets!r}")
         self.device_max_targets = device_max_targets
+        # the most queries the device criterion takes (128: one group of query columns per workgroup; up to 256, opt-in:
+        # two).  Predictions with more queries take the operator path
+        if isinstance(device_max_queries, bool) or not isinstance(device_max_queries, int) \
+                or not 128 <= device_max_queries <= 256:
+            raise ValueError(f"SetCriterion: device_max_queries must be an integer in 128 .. 256, not {device_max_queries!r}")
+        self.device_max_queries = device_max_queries
         self.num_classes = num_classes - 1
         self.class_weights, self.matcher, self.weight_dict = class_weights, matcher, weight_dict
         self.eos_coef, self.losses = eos_coef, list(losses)
@@ -360,11 +368,12 @@ class SetCriterion(nn.Module):
     def _fused_tables(self, levels, targets, mask_type):
         """The per-(scene, level) mask-logit tables [S, ld] for the device criterion, or None when the fused path does
         not apply (CPU tensors, sub-sampled points, noise-robust loss, more than min(device_max_targets, Q) targets in a
-        scene — device_max_targets is 32 unless the constructor was given up to 128 — or > 128 queries ...)."""
+        scene — device_max_targets is 32 unless the constructor was given up to 128 — or more than device_max_queries
+        queries: 128 unless the constructor was given up to 256 ...)."""
         if not (FUSED and self._plain_losses() and self.matcher.num_points == -1 and targets and 1 <= len(levels) <= 16):
             return None
         lg = levels[0]["pred_logits"]
-        if not (lg.is_cuda and lg.dtype == torch.float32 and lg.dim() == 3 and lg.shape[1] <= 128
+        if not (lg.is_cuda and lg.dtype == torch.float32 and lg.dim() == 3 and lg.shape[1] <= self.device_max_queries
                 and lg.shape[2] == self.num_classes + 1):
             return None
         Q = lg.shape[1]
@@ -379,9 +388,9 @@ class SetCriterion(nn.Module):
             ld = None
             for lv in levels:
                 t = lv["pred_masks"][b]
-                t = getattr(t, "_usc_padded", t)                 # models.mask3d._mask_logits: the padded [S, 128] table
+                t = getattr(t, "_usc_padded", t)                 # models.mask3d._mask_logits: the padded [S, ld] table
                 if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
-                        and Q <= t.shape[1] <= 128 and t.shape[0] == tm.shape[1] and t.shape[1] == (ld or t.shape[1])):
+                        and Q <= t.shape[1] <= max(128, self.device_max_queries) and t.shape[0] == tm.shape[1] and t.shape[1] == (ld or t.shape[1])):
                     return None
                 ld = t.shape[1]
                 tables.append(t)
@@ -394,12 +403,13 @@ class SetCriterion(nn.Module):
         tables = self._fused_tables(levels, targets, mask_type)
         if tables is None and FUSED and levels[0]["pred_logits"].is_cuda and not self.__dict__.get("_warned_operator_path"):
             # e.g. a prediction table that lost its `_usc_padded` companion by being cloned / re-wrapped, host-side
-            # targets, > device_max_targets targets: correct, but ~150 stock launches and a device->host copy per step slower
+            # targets, > device_max_targets targets, > device_max_queries queries: correct, but ~150 stock launches and a device->host copy per step slower
             self.__dict__["_warned_operator_path"] = True
             import warnings
             warnings.warn("SetCriterion: the device criterion (csrc/criterion.hip) does not apply to these inputs; "
                           "using the torch-operator path (see SetCriterion._fused_tables for the conditions; scenes "
-                          f"with more than {self.device_max_targets} targets need a larger device_max_targets, up to 128)")
+                          f"with more than {self.device_max_targets} targets need a larger device_max_targets, up to 128; "
+                          f"more than {self.device_max_queries} queries need a larger device_max_queries, up to 256)")
         if tables is not None:
             if is_dist_avail_and_initialized():   # the reference's collective (criterion.py:258-260); its result is
                 # never used by the losses (loss_masks overwrites num_masks, :189), so nobody waits for it here

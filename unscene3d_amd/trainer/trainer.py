@@ -135,7 +135,8 @@ class InstanceSegmentation(nn.Module):
                                       importance_sample_ratio=l.importance_sample_ratio,
                                       class_weights=l.class_weights, directions=l.directions,
                                       use_droploss=l.use_droploss, droploss_iou_thresh=l.droploss_iou_thresh,
-                                      device_max_targets=getattr(l, "device_max_targets", 32))
+                                      device_max_targets=getattr(l, "device_max_targets", 32),
+                                      device_max_queries=getattr(l, "device_max_queries", 128))
 
     def forward(self, x, point2segment=None, raw_coordinates=None, is_eval=False, num_segments=None):
         return self.model(x, point2segment, raw_coordinates=raw_coordinates, is_eval=is_eval,
