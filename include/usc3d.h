@@ -1413,6 +1413,53 @@ int64_t usc_mask_bits_nms_ws_bytes(int64_t n);
 int usc_mask_bits_nms(const uint64_t* bits, const int32_t* count, int64_t k, const int32_t* order, int32_t n,
                       float nms_thr, uint8_t* keep, void* ws, int64_t ws_bytes, usc_stream_t s);
 
+/* ------------------------------------------------------------------------
+ * FreeMask pseudo masks, segment mode (pseudo_masks/freemask_main.py:186-233,
+ * :282-350, :359-370): keys = queries = the S segment features, a mask is a
+ * set of whole segments, rows are S-bit rows in the layout of usc_freemask_bits.
+ * Explicit stream, no allocation, no synchronisation, no float atomics; two
+ * runs give identical bits.
+ *
+ * usc_maxpool_down2_i32 (:189-199, MinkowskiMaxPooling(kernel_size=2, stride=2)
+ *   on the id column, pooled as integers): out[p] = max of in[child] over the
+ *   present children nbr2[k * n_coarse + p] (k < 8, -1 = absent; the table of
+ *   usc_avgpool_down2); a child index >= n_fine counts as absent; a parent
+ *   without a child gives -1.
+ * usc_mask_bits_components (:288-327, the per-query scan over sets): for the
+ *   rows rows[i] (i < n_rows, each in [0, n_bits_rows)) of bits
+ *   u64[n_bits_rows, ceil(S/64)], the connected parts of the row's mask on the
+ *   undirected adjacency adj_off i64[S+1], adj i32[adj_off[S]] (symmetric, every
+ *   entry in [0, S): the CALLER checks that).  label i32[n_rows, S]: -1 outside
+ *   the mask, else the smallest segment index of the part; n_comp i32[n_rows].
+ *   One workgroup per row, labels in LDS, min-label propagation until a round
+ *   changes nothing.  S <= USC_MASK_BITS_MAX_SEGMENTS
+ *   (= usc_mask_bits_max_segments()), refused above.
+ * usc_mask_bits_split (:329-348, :353 numerators): row_off i64[n_rows] = the
+ *   exclusive scan of n_comp.  Output row row_off[i] + j is the part of input
+ *   row i with the j-th smallest root: out_bits u64[R, ceil(S/64)], out_src
+ *   (= i), out_root, seg_count, vox_count = sum of weight[s] over the part
+ *   (i32[R]), soft_sum f32[R] = sum of soft[soft_row[i] * soft_ld + s] over the
+ *   part in ascending s.  Same cap on S.
+ * usc_mask_bits_nms_weighted (utils/pc_utils.py:727-757 on the remapped masks of
+ *   :361-370): usc_mask_bits_nms with inter = sum of weight[s] over the set bits
+ *   of row_i & row_j (weight i32[k]) and the caller's weighted counts.  Exact
+ *   while the sum of all weights is below 2^24 (the CALLER checks that).
+ * ---------------------------------------------------------------------- */
+#define USC_MASK_BITS_MAX_SEGMENTS 8192
+int32_t usc_mask_bits_max_segments(void);
+int usc_maxpool_down2_i32(const int32_t* in, int64_t n_fine, const int32_t* nbr2, int64_t n_coarse, int32_t* out,
+                          usc_stream_t s);
+int usc_mask_bits_components(const uint64_t* bits, int64_t n_bits_rows, int32_t n_segments, const int32_t* rows,
+                             int32_t n_rows, const int64_t* adj_off, const int32_t* adj, int32_t* label,
+                             int32_t* n_comp, usc_stream_t s);
+int usc_mask_bits_split(const int32_t* label, int32_t n_rows, int32_t n_segments, const int64_t* row_off,
+                        const int32_t* n_comp, const int32_t* weight, const float* soft, int64_t soft_ld,
+                        const int32_t* soft_row, uint64_t* out_bits, int32_t* out_src, int32_t* out_root,
+                        int32_t* seg_count, int32_t* vox_count, float* soft_sum, usc_stream_t s);
+int usc_mask_bits_nms_weighted(const uint64_t* bits, const int32_t* count, const int32_t* weight, int64_t k,
+                               const int32_t* order, int32_t n, float nms_thr, uint8_t* keep, void* ws,
+                               int64_t ws_bytes, usc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

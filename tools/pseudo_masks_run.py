@@ -10,10 +10,13 @@ Replicas only: rank r of W takes the scenes r, r+W, ... and nev
     python -m torch.distributed.run --nproc-per-node 8 tools/pseudo_masks_run.py --scenes DIR --out OUT
     python tools/pseudo_masks_run.py --synthetic 6 --out /tmp/pm                   # self-contained demo scenes
     python tools/pseudo_masks_run.py --scenes DIR --out OUT --method freemask      # the FreeMask baseline instead of NCut
+    python tools/pseudo_masks_run.py --scenes DIR --out OUT --method freemask --freemask-mode segment   # on segments
 
 --method ncut (default) writes `{scene}_masks.npy` as bool[N_full, K] NCut masks; --method freemask (reference
 pseudo_masks/freemask_main.py, voxel mode; unscene3d_amd.pseudo_masks.freemask) writes it as f32[N_full, M] soft masks,
-the file freemask_preprocessing.py:197-213 and datasets/freemask.py read.  Both write `{scene}_cloud.npy` last.
+the file freemask_preprocessing.py:197-213 and datasets/freemask.py read; `--freemask-mode segment` runs the script's
+segment mode instead (keys and queries are the scene file's segments, masks split into connected parts; needs
+`segment_ids` and `seg_connectivity`), the default `voxel` is unchanged.  Both write `{scene}_cloud.npy` last.
 
 Scene files (`DIR/*.npz`, one per scene; the encoders' per-voxel outputs are an input here.
 tools/scene_files_from_scans.py writes these files from ScanNet-style scan directories — colour frames, poses, the info
@@ -106,9 +109,9 @@ def process_scene(path, out_dir, device, ncut_args):
     return name, int(all_masks.shape[1]), time.perf_counter() - t0
 
 
-def process_scene_freemask(path, out_dir, device, fm_args, modality="2d", resolution_scale=2):
-    """FreeMask voxel mode on one scene file -> (scene name, number of masks, seconds); None when already processed.  A
-    scene without instances writes nothing (the reference prints and skips it)."""
+def process_scene_freemask(path, out_dir, device, fm_args, modality="2d", resolution_scale=2, mode="voxel"):
+    """FreeMask (voxel or segment mode) on one scene file -> (scene name, number of masks, seconds); None when already
+    processed.  A scene without instances writes nothing (the reference prints and skips it)."""
     from unscene3d_amd.pseudo_masks import freemask as fm
     name = os.path.splitext(os.path.basename(path))[0]
     cloud_file = os.path.join(out_dir, f"{name}_cloud.npy")
@@ -122,7 +125,16 @@ def process_scene_freemask(path, out_dir, device, fm_args, modality="2d", resolu
     coords = torch.from_numpy(z["coords"].astype(np.int32)).to(device)
     feats = torch.from_numpy(z[key].astype(np.float32)).to(device)
     voxel_size = float(z["voxel_size"]) if "voxel_size" in z.files else 0.02
-    r = fm.freemask_from_voxel_feats(coords, feats, resolution_scale, **fm_args)
+    if mode == "segment":
+        for need in ("segment_ids", "seg_connectivity"):
+            if need not in z.files:
+                raise RuntimeError(f"{path}: needs {need} for --freemask-mode segment")
+        seg_args = {k: v for k, v in fm_args.items() if k != "min_mask_points"}
+        r = fm.freemask_segments_from_voxel_feats(coords, feats, torch.from_numpy(z["segment_ids"].astype(np.int64)),
+                                                  torch.from_numpy(z["seg_connectivity"].astype(np.int64)),
+                                                  resolution_scale, **seg_args)
+    else:
+        r = fm.freemask_from_voxel_feats(coords, feats, resolution_scale, **fm_args)
     if r.soft_masks.shape[0] == 0:
         return name, 0, time.perf_counter() - t0
     full = z["full_res_coords"].astype(np.float32)
@@ -146,6 +158,9 @@ def main(argv=None):
     ap.add_argument("--method", choices=("ncut", "freemask"), default="ncut")
     fm = ap.add_argument_group("--method freemask (freemask_main.py's config.freemask)")
     fm.add_argument("--modality", choices=("2d", "3d"), default="2d", help="which per-voxel features of the scene file")
+    fm.add_argument("--freemask-mode", choices=("voxel", "segment"), default="voxel",
+                    help="segment: keys and queries are the scene file's segments (segment_ids, seg_connectivity), "
+                         "masks split into connected parts (the reference's segments_as_grids default)")
     fm.add_argument("--resolution-scale", type=int, default=2)
     fm.add_argument("--hard-mask-threshold", type=float, default=0.35)
     fm.add_argument("--min-mask-points", type=int, default=10)
@@ -183,7 +198,8 @@ def main(argv=None):
     done = 0
     for i in mine:
         if args.method == "freemask":
-            r = process_scene_freemask(files[i], args.out, device, fm_args, args.modality, args.resolution_scale)
+            r = process_scene_freemask(files[i], args.out, device, fm_args, args.modality, args.resolution_scale,
+                                       args.freemask_mode)
         else:
             r = process_scene(files[i], args.out, device, ncut_args)
         if r is None:

@@ -449,6 +449,33 @@ class MinkowskiAvgPooling(nn.Module):
         return SparseTensor(features=out, coordinate_manager=cm, coordinate_map_key=CoordinateMapKey(2 * ts))
 
 
+class MinkowskiMaxPooling(nn.Module):
+    """kernel_size=2, stride=2 max pooling over present children of ONE integer-valued column (forward only): the
+    segment ids of reference pseudo_masks/freemask_main.py:189-199.  The column may be integer, or float holding exact
+    integers (the reference's `segment_ids.float().view(-1, 1)`); the result has the input's dtype."""
+
+    def __init__(self, kernel_size=-1, stride=1, dilation=1, kernel_generator=None, dimension=-1):
+        super().__init__()
+        ks = _to_list(kernel_size, dimension)
+        st = _to_list(stride, dimension)
+        if set(ks) != {2} or set(st) != {2}:
+            raise NotImplementedError("only MinkowskiMaxPooling(kernel_size=2, stride=2) is on the hot path")
+
+    def forward(self, x: SparseTensor) -> SparseTensor:
+        cm, ts = x.coordinate_manager, x._ts()
+        d = cm.stride_map(ts)
+        f = x.F.detach()
+        if f.dim() != 2 or f.shape[1] != 1:
+            raise NotImplementedError("MinkowskiMaxPooling pools one id column [n, 1]; feature pooling has no kernel")
+        ids = f
+        if f.is_floating_point():
+            ids = f.to(torch.int64)
+            if not bool((ids.to(f.dtype) == f).all()):
+                raise RuntimeError("MinkowskiMaxPooling: a float column must hold exact integers")
+        out = ops.maxpool_down2_i32(ids, d["nbr2"]).to(f.dtype)
+        return SparseTensor(features=out, coordinate_manager=cm, coordinate_map_key=CoordinateMapKey(2 * ts))
+
+
 def cat(*tensors):
     """MinkowskiOps.cat: channel concat of tensors on the same map (reference res16unet.py:259-289)."""
     if len(tensors) == 1 and isinstance(tensors[0], (list, tuple)):
@@ -494,4 +521,5 @@ def _submodule(name, **members):
 
 
 MinkowskiOps = _submodule("MinkowskiOps", SparseTensor=SparseTensor, cat=cat)
-MinkowskiPooling = _submodule("MinkowskiPooling", MinkowskiAvgPooling=MinkowskiAvgPooling)
+MinkowskiPooling = _submodule("MinkowskiPooling", MinkowskiAvgPooling=MinkowskiAvgPooling,
+                              MinkowskiMaxPooling=MinkowskiMaxPooling)

@@ -240,6 +240,11 @@ SIGNATURES = {
     "usc_mask_bits_extent": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _p]),
     "usc_mask_bits_nms_ws_bytes": (_i64, [_i64]),
     "usc_mask_bits_nms": (C.c_int, [_p, _p, _i64, _p, _i32, _f32, _p, _p, _i64, _p]),
+    "usc_mask_bits_max_segments": (_i32, []),
+    "usc_maxpool_down2_i32": (C.c_int, [_p, _i64, _p, _i64, _p, _p]),
+    "usc_mask_bits_components": (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _p, _p]),
+    "usc_mask_bits_split": (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "usc_mask_bits_nms_weighted": (C.c_int, [_p, _p, _p, _i64, _p, _i32, _f32, _p, _p, _i64, _p]),
 }
 
 

@@ -13,6 +13,8 @@
 //   usc_mask_bits_extent     bounding box of every mask over the key coordinates of its set bits
 //   usc_mask_bits_nms        greedy mask NMS over packed rows: AND + popcount "i would kill j" bit matrix, then a
 //                            one-workgroup sequential scan (a dead mask suppresses nothing)
+//   usc_mask_bits_nms_weighted  the same with a weight per bit (segment mode, freemask_segments.hip: a bit is a segment,
+//                            its weight the segment's key voxels)
 //   usc_freemask_soft_rows   the f32 rows of the few surviving queries, from the same tile code (bit-consistent with
 //                            pass 2: every a[q][k] is one fixed chain of fused multiply-adds over the channels)
 //
@@ -336,16 +338,20 @@ constexpr int kNmsChunk = 16;       // 64-bit words of every row per LDS round
 
 // kill[a][b / 64] bit b % 64 = "mask at position a suppresses the mask at position b" for the 64 x 64 block (ta, tb),
 // tb >= ta (the scan reads nothing below the diagonal block).  Thread (ty, tx) counts the 4 x 4 pairs
-// (4 ty + u, 4 tx + v).
+// (4 ty + u, 4 tx + v).  WEIGHTED (segment mode: a bit is a whole segment): the intersection is the sum of weight[s]
+// over the set bits of the AND instead of their number, and `count` holds the rows' weighted sizes.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void mask_bits_nms_fill_kernel(const uint64_t* __restrict__ bits, int64_t W,
                                                                  const int32_t* __restrict__ count,
                                                                  const int32_t* __restrict__ order, int32_t n,
-                                                                 float thr, uint64_t* __restrict__ kill, int32_t nW) {
+                                                                 float thr, uint64_t* __restrict__ kill, int32_t nW,
+                                                                 const int32_t* __restrict__ weight, int64_t K) {
   const int ta = blockIdx.y, tb = blockIdx.x;
   if (tb < ta) return;
   __shared__ uint64_t sa[64][kNmsChunk + 1], sb[64][kNmsChunk + 1];
   __shared__ int32_t inter_s[64][65];
   __shared__ int32_t row_a[64], row_b[64], cnt_a[64], cnt_b[64];
+  __shared__ int32_t sw[WEIGHTED ? kNmsChunk * 64 : 1];
   if (threadIdx.x < 64) {
     const int pa = ta * 64 + threadIdx.x, pb = tb * 64 + threadIdx.x;
     const int ra = pa < n ? order[pa] : -1, rb = pb < n ? order[pb] : -1;
@@ -367,6 +373,11 @@ __global__ __launch_bounds__(256) void mask_bits_nms_fill_kernel(const uint64_t*
       sa[r][wc] = (in && row_a[r] >= 0) ? bits[(int64_t)row_a[r] * W + w0 + wc] : 0ull;
       sb[r][wc] = (in && row_b[r] >= 0) ? bits[(int64_t)row_b[r] * W + w0 + wc] : 0ull;
     }
+    if (WEIGHTED)
+      for (int e = threadIdx.x; e < 64 * kNmsChunk; e += 256) {
+        const int64_t k = w0 * 64 + e;
+        sw[e] = k < K ? weight[k] : 0;
+      }
     __syncthreads();
 #pragma unroll 4
     for (int wc = 0; wc < kNmsChunk; ++wc) {
@@ -376,7 +387,17 @@ __global__ __launch_bounds__(256) void mask_bits_nms_fill_kernel(const uint64_t*
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int v = 0; v < 4; ++v) inter[u][v] += __popcll(xa[u] & xb[v]);
+        for (int v = 0; v < 4; ++v) {
+          if (WEIGHTED) {
+            uint64_t m = xa[u] & xb[v];
+            while (m) {
+              inter[u][v] += sw[wc * 64 + __builtin_ctzll(m)];
+              m &= m - 1;
+            }
+          } else {
+            inter[u][v] += __popcll(xa[u] & xb[v]);
+          }
+        }
     }
     __syncthreads();
   }
@@ -549,22 +570,40 @@ int usc_mask_bits_extent(const uint64_t* bits, int64_t n, int64_t k, const int32
 
 int64_t usc_mask_bits_nms_ws_bytes(int64_t n) { return n < 1 ? 0 : n * ceil_div(n, 64) * 8; }
 
-int usc_mask_bits_nms(const uint64_t* bits, const int32_t* count, int64_t k, const int32_t* order, int32_t n,
-                      float nms_thr, uint8_t* keep, void* ws, int64_t ws_bytes, usc_stream_t s) {
-  USC_REQUIRE(n >= 0 && n <= 524288, "usc_mask_bits_nms: n out of range [0, 524288]");
-  USC_REQUIRE(k >= 1 && k <= INT32_MAX - 64, "usc_mask_bits_nms: k out of range");
+static int mask_bits_nms_run(const char* name, const uint64_t* bits, const int32_t* count, const int32_t* weight,
+                             int64_t k, const int32_t* order, int32_t n, float nms_thr, uint8_t* keep, void* ws,
+                             int64_t ws_bytes, usc_stream_t s) {
+  USC_REQUIRE(n >= 0 && n <= 524288, "%s: n out of range [0, 524288]", name);
+  USC_REQUIRE(k >= 1 && k <= INT32_MAX - 64, "%s: k out of range", name);
   if (n == 0) return USC_OK;
-  USC_REQUIRE(bits && count && order && keep && ws, "usc_mask_bits_nms: null pointer");
-  USC_REQUIRE(ws_bytes >= usc_mask_bits_nms_ws_bytes(n), "usc_mask_bits_nms: workspace too small");
+  USC_REQUIRE(bits && count && order && keep && ws, "%s: null pointer", name);
+  USC_REQUIRE(ws_bytes >= usc_mask_bits_nms_ws_bytes(n), "%s: workspace too small", name);
   const int32_t nW = (int32_t)ceil_div(n, 64);      // <= 8192: dead[] fits 64 KB of LDS
   hipStream_t st = as_stream(s);
-  hipLaunchKernelGGL(mask_bits_nms_fill_kernel, dim3(nW, nW), dim3(256), 0, st, bits, ceil_div(k, 64), count, order, n,
-                     nms_thr, (uint64_t*)ws, nW);
-  USC_CHECK_LAUNCH("usc_mask_bits_nms");
+  if (weight)
+    hipLaunchKernelGGL(mask_bits_nms_fill_kernel<true>, dim3(nW, nW), dim3(256), 0, st, bits, ceil_div(k, 64), count,
+                       order, n, nms_thr, (uint64_t*)ws, nW, weight, k);
+  else
+    hipLaunchKernelGGL(mask_bits_nms_fill_kernel<false>, dim3(nW, nW), dim3(256), 0, st, bits, ceil_div(k, 64), count,
+                       order, n, nms_thr, (uint64_t*)ws, nW, weight, k);
+  USC_CHECK_LAUNCH(name);
   hipLaunchKernelGGL(mask_bits_nms_scan_kernel, dim3(1), dim3(1024), (size_t)nW * 8, st, (const uint64_t*)ws, n, nW,
                      keep);
-  USC_CHECK_LAUNCH("usc_mask_bits_nms");
+  USC_CHECK_LAUNCH(name);
   return USC_OK;
+}
+
+int usc_mask_bits_nms(const uint64_t* bits, const int32_t* count, int64_t k, const int32_t* order, int32_t n,
+                      float nms_thr, uint8_t* keep, void* ws, int64_t ws_bytes, usc_stream_t s) {
+  return mask_bits_nms_run("usc_mask_bits_nms", bits, count, nullptr, k, order, n, nms_thr, keep, ws, ws_bytes, s);
+}
+
+int usc_mask_bits_nms_weighted(const uint64_t* bits, const int32_t* count, const int32_t* weight, int64_t k,
+                               const int32_t* order, int32_t n, float nms_thr, uint8_t* keep, void* ws,
+                               int64_t ws_bytes, usc_stream_t s) {
+  USC_REQUIRE(weight || n == 0, "usc_mask_bits_nms_weighted: null pointer");
+  return mask_bits_nms_run("usc_mask_bits_nms_weighted", bits, count, weight, k, order, n, nms_thr, keep, ws, ws_bytes,
+                           s);
 }
 
 }  // extern "C"

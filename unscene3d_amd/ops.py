@@ -784,6 +784,30 @@ def avgpool_down2(feats, nbr2, row_of=None, threshold=False):
     return out
 
 
+MAXPOOL_I32_ID_LIMIT = 1 << 24   # the reference pools the ids as f32: above 2^24 its result is not an id any more
+
+
+def maxpool_down2_i32(ids, nbr2):
+    """MinkowskiMaxPooling(kernel_size=2, stride=2) forward on one integer column (segment ids, reference
+    pseudo_masks/freemask_main.py:189-199): max over the present children of the `avgpool_down2` child table.
+    ids: integer [n_fine] or [n_fine, 1] on the device -> i32 of the same rank.  Ids < 0 or >= 2^24 are refused."""
+    if not ids.is_cuda or ids.dtype not in (torch.int32, torch.int64) or ids.dim() not in (1, 2) \
+            or (ids.dim() == 2 and ids.shape[1] != 1):
+        raise RuntimeError("maxpool_down2_i32: ids must be an i32 / i64 HIP column [n] or [n, 1]")
+    _chk(nbr2, torch.int32, "nbr2")
+    if nbr2.dim() != 2 or nbr2.shape[0] != 8:
+        raise RuntimeError("maxpool_down2_i32: nbr2 must be the i32 [8, n_coarse] child table")
+    flat = ids.reshape(-1)
+    if flat.numel() and (int(flat.min()) < 0 or int(flat.max()) >= MAXPOOL_I32_ID_LIMIT):
+        raise RuntimeError(f"maxpool_down2_i32: ids outside [0, 2^24): {int(flat.min())} .. {int(flat.max())}")
+    flat = flat.to(torch.int32).contiguous()
+    nc = nbr2.shape[1]
+    out = torch.empty(nc, dtype=torch.int32, device=ids.device)
+    check(lib.usc_maxpool_down2_i32(_ptr(flat), flat.numel(), _ptr(nbr2), nc, _ptr(out), _stream()),
+          "usc_maxpool_down2_i32")
+    return out if ids.dim() == 1 else out.view(-1, 1)
+
+
 class _GatherRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, src, idx, out=None, unique=False):
