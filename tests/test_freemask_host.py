@@ -1,10 +1,12 @@
 """CPU: the float64 restatement tests/freemask_ref.py reproduces the reference's own run (tests/golden/freemask.npz,
-written by tests/golden/make_golden_freemask.py from the reference's cosine_sim and matrix_nms), and the inputs of the
-GPU kernel tests meet the condition those tests put on them."""
+written by tests/golden/make_golden_freemask.py from the reference's cosine_sim and matrix_nms), the inputs of the
+GPU kernel tests meet the condition those tests put on them, and the package's selection tail (`_select`, torch
+operators only) picks the restatement's survivors from the restatement's candidates."""
 import os
 
 import numpy as np
 import pytest
+import torch
 
 import freemask_cases as FC
 import freemask_ref as FR
@@ -37,6 +39,61 @@ def test_ref_extent_filter_is_what_drops_the_room():
     p["instance_to_scene_max_ratio"] = 2.0                      # filter off: the room's best mask survives as well
     _, _, qidx = FR.freemask_ref(z["key_feats"], z["key_coords"], z["query_feats"], z["scene_extent"], **p)
     assert sorted(z["query_cluster"][qidx].tolist()) == [0, 1, 2, 3, 4, 5]
+
+
+# `_select` on what the restatement computes.  The three parameter sets: the golden ones, a cut at 3 masks, and a scene
+# extent scaled down until no mask passes the extent filter ("none left -> all stay"); 2.0 is above every maskness.
+SELECT_SETS = [dict(), dict(max_instance_num=3), dict(extent_scale=1e-3)]
+
+
+def check_select(sums, counts, masks, coords, scene_extent, p, want_for):
+    """sums f64[n], counts int[n], masks bool[n,K] of the candidates in candidate order, coords int[K,3];
+    want_for(parameters) -> the restatement's survivors as positions in the candidate list."""
+    from unscene3d_amd.pseudo_masks.freemask import _select
+    m64 = sums / counts
+    maskness = torch.from_numpy(sums).float() / torch.from_numpy(counts)        # f32 sum / integer, as on the device
+    assert maskness.dtype == torch.float32
+    # no tie that f32 and f64 order differently, in any subset of the candidates
+    assert np.array_equal(np.argsort(-maskness.numpy(), kind="stable"), np.argsort(-m64, kind="stable"))
+    lo, hi = (torch.from_numpy(b).int() for b in FR.mask_extent(masks, coords))
+    vox = masks.sum(1)
+
+    def nms(order):
+        o = order.numpy()
+        return torch.from_numpy(FR.greedy_nms(masks[o], vox[o], p["nms_thr"]))
+
+    def run(extent_scale=1.0, **over):
+        q = {**p, **over}
+        ext = np.asarray(scene_extent, np.float64) * extent_scale
+        got = _select(maskness, torch.arange(len(sums)), lo, hi, torch.from_numpy(ext), nms,
+                      instance_to_scene_max_ratio=q["instance_to_scene_max_ratio"],
+                      max_instance_num=q["max_instance_num"], nms_maskness_threshold=q["nms_maskness_threshold"])
+        return got, want_for(ext, q), ((hi - lo)[:, :2].double() / torch.from_numpy(ext)[:2] > q[
+            "instance_to_scene_max_ratio"]).any(1)
+
+    for i, over in enumerate(SELECT_SETS):
+        (got_m, got_rows), want, too_big = run(**over)
+        assert too_big.any() and (bool(too_big.all()) == (i == 2))              # set 2 is the "all stay" branch
+        assert got_rows.dtype == torch.int64 and got_rows.tolist() == want.tolist() and len(want) >= 3
+        assert len(want) == 3 or i != 1
+        assert np.abs(got_m.numpy() - m64[want]).max() <= 1e-6                   # two f32 roundings of a value <= 1
+    got, want, _ = run(nms_maskness_threshold=2.0)
+    assert got is None and len(want) == 0
+
+
+def test_select_picks_the_restatements_survivors():
+    z = np.load(GOLDEN)
+    p = _params(z)
+    a, _, _, _ = FR.cosine_rows(z["key_feats"], z["query_feats"])
+    masks = a >= p["hard_mask_threshold"]
+    cand = np.nonzero(masks.sum(1) > p["min_mask_points"])[0]
+
+    def want_for(ext, q):
+        qidx = FR.freemask_ref(z["key_feats"], z["key_coords"], z["query_feats"], ext, **q)[2]
+        return np.searchsorted(cand, qidx)
+
+    check_select((a[cand] * masks[cand]).sum(1), masks[cand].sum(1), masks[cand], z["key_coords"], z["scene_extent"], p,
+                 want_for)
 
 
 def test_ref_nms_rules():

@@ -2,7 +2,8 @@
 (tests/golden/freemask_segments.npz, written by tests/golden/make_golden_freemask_segments.py from the reference's
 cosine_sim, separate_segments and matrix_nms); the voxel-level quantities it works with equal the segment-level
 formulas the device path uses; and on the recorded triple-bridge graph it gives the true components where the
-reference's scan does not (deviation (d))."""
+reference's scan does not (deviation (d)); and the package's selection tail picks the restatement's survivors from
+the restatement's split rows."""
 import os
 
 import numpy as np
@@ -10,6 +11,7 @@ import pytest
 
 import freemask_ref as FR
 import freemask_segment_ref as SR
+import test_freemask_host as TH
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "freemask_segments.npz")
 
@@ -80,6 +82,26 @@ def test_voxel_level_equals_segment_level(golden):
     # segment-count IoU and voxel-count IoU do differ on this scene
     w = SR.segment_tables(idx, coords, S)[0]
     assert len(set(w.tolist())) > 2
+
+
+def test_select_picks_the_restatements_survivors(golden):
+    z, _, dbg = golden
+    p = golden_params(z)
+    a, uniq = dbg["a"], dbg["unique_segments"]
+    masks = a >= p["hard_mask_threshold"]
+    cand = np.nonzero(masks.sum(1) > p["min_mask_segments"])[0]
+    rows, query, root = SR.split_rows(a, masks, cand, dbg["adj"], p["min_part_segments"])    # candidate order
+    seg_masks = rows >= p["hard_mask_threshold"]
+    vmasks = SR.remap(rows, dbg["idx"]) >= p["hard_mask_threshold"]
+    pairs = list(zip(uniq[query].tolist(), uniq[root].tolist()))
+    assert len(set(pairs)) == len(pairs)
+
+    def want_for(ext, q):
+        _, _, qs, rs = SR.freemask_segments_ref(z["key_feats"], z["key_coords"], z["key_segment_ids"],
+                                                z["seg_connectivity"], ext, **q)
+        return np.array([pairs.index(pr) for pr in zip(qs.tolist(), rs.tolist())], np.int64)
+
+    TH.check_select((rows * seg_masks).sum(1), seg_masks.sum(1), vmasks, z["key_coords"], z["scene_extent"], p, want_for)
 
 
 def test_triple_bridge_graph_documents_deviation_d(golden):

@@ -5,8 +5,12 @@ coordinates), the float64 restatement tests/freemask_segment_ref.py and the refe
 
 Bounds.  Labels, counts, bits and NMS decisions are integers: exact.  Soft sums of the split rows: 1e-5 relative
 against the f64 sum over the device's own labels (the bound of test_gpu_freemask.py's soft_sum).  End to end: 1e-5 on
-maskness and soft rows, the bound of the voxel-mode golden; the generator's decision margins are wider."""
+maskness and soft rows, the bound of the voxel-mode golden; the generator's decision margins are wider.
+Both modes' entry points also return the bits recorded before their selection tail and scene layer became one
+(tests/golden/freemask_bits.json, recorded on the parent commit): no tolerance."""
+import hashlib
 import importlib.util
+import json
 import os
 
 import numpy as np
@@ -315,6 +319,7 @@ def test_unweighted_nms_is_unchanged_and_is_the_unit_weight_case(device):
             unit = fm.mask_nms_weighted(bits, dc, torch.ones(K, dtype=torch.int32, device="cuda"), o, 0.5)
             assert plain.cpu().numpy().tolist() == want.tolist(), name
             assert torch.equal(plain, unit), name
+            assert torch.equal(unit, fm.mask_nms(bits, dc, o, 0.5, weight=torch.ones(K, dtype=torch.int32, device="cuda")))
 
 
 # -------------------------------------------------------------------------------------------------------- end to end
@@ -450,6 +455,55 @@ def test_tool_segment_mode_on_a_synthetic_scene(device, tmp_path, monkeypatch):
     with pytest.raises(RuntimeError, match="seg_connectivity"):
         tool.main(["--scenes", bare, "--out", str(tmp_path / "o2"), "--method", "freemask", "--freemask-mode", "segment"])
     assert tool.main(["--scenes", bare, "--out", str(tmp_path / "o3"), "--method", "freemask"]) == 0
+
+
+# -------------------------------------------------------------------------------------------------------------- bits
+def _sha(fields):
+    h = hashlib.sha256()
+    for t in fields:
+        if not torch.is_tensor(t):                              # tensor_stride
+            h.update(repr(t).encode())
+            continue
+        t = t.detach().cpu().contiguous()
+        h.update(str(tuple(t.shape)).encode())
+        h.update(t.view(torch.uint8).numpy().tobytes())
+    return h.hexdigest()
+
+
+def freemask_bits(scene_dir):
+    """name -> sha256 over every field of the result, for both modes: the golden parameters, a cut at 3 masks, a scene
+    extent so small that no mask passes the extent filter (all stay), and the scene-level entry points."""
+    spec = importlib.util.spec_from_file_location("pseudo_masks_run", os.path.join(ROOT, "tools", "pseudo_masks_run.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    import test_freemask_host as TH
+    bits = {}
+    v = np.load(TH.GOLDEN)
+    vp = TH._params(v)
+    vargs = [torch.from_numpy(v[k]).cuda() for k in ("key_feats", "key_coords", "query_feats")]
+    z = np.load(GOLDEN)
+    sp = golden_params(z)
+    sargs = [torch.from_numpy(z["key_feats"]).cuda(), torch.from_numpy(z["key_coords"]).cuda(),
+             torch.from_numpy(z["key_segment_ids"]).cuda(), torch.from_numpy(z["seg_connectivity"])]
+    for name, scale, over in (("golden", 1.0, {}), ("cut_3", 1.0, dict(max_instance_num=3)), ("all_stay", 1e-3, {})):
+        bits[f"voxel_{name}"] = _sha(fm.freemask(*vargs, torch.from_numpy(v["scene_extent"] * np.float32(scale)),
+                                                 **{**vp, **over}))
+        bits[f"segment_{name}"] = _sha(fm.freemask_segments(*sargs, torch.from_numpy(z["scene_extent"] * np.float32(scale)),
+                                                            **{**sp, **over}))
+    bits["segment_from_voxel_feats"] = _sha(fm.freemask_segments_from_voxel_feats(
+        torch.from_numpy(z["in_coords"]).cuda(), torch.from_numpy(z["key_feats"][z["in_parent"]]).cuda(),
+        torch.from_numpy(z["in_segment_ids"]), z["seg_connectivity"], 2, **sp))
+    (path,) = tool.synthetic_scene_files(1, scene_dir)
+    y = np.load(path)
+    bits["voxel_from_voxel_feats"] = _sha(fm.freemask_from_voxel_feats(torch.from_numpy(y["coords"]).cuda(),
+                                                                       torch.from_numpy(y["feats_2d"]).cuda(), 2))
+    return bits
+
+
+@pytest.mark.gpu
+def test_both_modes_compute_the_recorded_bits(device, tmp_path):
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "freemask_bits.json")))
+    assert freemask_bits(str(tmp_path / "scenes")) == want
 
 
 # ------------------------------------------------------------------------------------------------------------ memory

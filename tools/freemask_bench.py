@@ -52,9 +52,41 @@ def make_inputs(Q, K, C, clusters, seed=0):
             torch.from_numpy(fq.astype(np.float32)).to(dev), torch.from_numpy(ext))
 
 
+def torch_select(masks_of, maskness, carry, coords, ext, instance_to_scene_max_ratio, nms_thr, max_instance_num,
+                 nms_maskness_threshold, counts=None):
+    """Steps 5-7 of both modes with torch operators.  masks_of() -> bool[n,K] in maskness order (a function, so that the
+    unfiltered masks die with the extent filter's copy), maskness f32[n], carry: index tensors [n] that go with the
+    rows, counts: the masks' sizes as a table indexed by carry[0] (None: the row sums).
+    -> (the survivors' carry, their maskness)."""
+    m = masks_of()
+    big, c = torch.iinfo(torch.int32).max, coords[:, :2].int()
+    ok = torch.ones(len(m), dtype=torch.bool, device=m.device)
+    for d in range(2):                                           # [n,K] temporaries, one axis at a time
+        hi = torch.where(m, c[:, d][None, :], -big).amax(1)
+        lo = torch.where(m, c[:, d][None, :], big).amin(1)
+        ok &= ~((hi - lo).double() / float(ext[d]) > instance_to_scene_max_ratio)
+    if bool(ok.any()):
+        m, maskness, carry = m[ok], maskness[ok], [t[ok] for t in carry]
+    mf = m.float()
+    inter = mf @ mf.T
+    n_i = mf.sum(1) if counts is None else counts[carry[0]].float()
+    union = n_i[:, None] + n_i[None, :] - inter
+    kill = torch.where(union > 0, inter / union > nms_thr, torch.ones_like(union, dtype=torch.bool)).cpu().numpy()
+    dead = np.zeros(len(kill), bool)
+    for i in range(len(kill)):
+        if not dead[i]:
+            dead[i + 1:] |= kill[i, i + 1:]
+    maskness = torch.where(torch.from_numpy(~dead).to(m.device), maskness, torch.zeros_like(maskness))
+    maskness, by = torch.sort(maskness, descending=True, stable=True)
+    by = by[:max_instance_num]
+    maskness, carry = maskness[:max_instance_num], [t[by] for t in carry]
+    sel = maskness > nms_maskness_threshold
+    return [t[sel] for t in carry], maskness[sel]
+
+
 def torch_freemask(fk, coords, fq, ext, hard_mask_threshold, min_mask_points, instance_to_scene_max_ratio, nms_thr,
                    max_instance_num, nms_maskness_threshold):
-    """Steps 1-7 with torch operators; [Q,K] in f32 and bool."""
+    """Steps 1-4 with torch operators, then `torch_select`; [Q,K] in f32 and bool."""
     eps = 1e-9
     kh = fk / (fk.norm(dim=1, keepdim=True) + eps)
     qh = fq / (fq.norm(dim=1, keepdim=True) + eps)
@@ -70,30 +102,9 @@ def torch_freemask(fk, coords, fq, ext, hard_mask_threshold, min_mask_points, in
     maskness = (a[cand] * masks[cand]).sum(1) / counts[cand]
     maskness, by = torch.sort(maskness, descending=True, stable=True)
     cand = cand[by]
-    m = masks[cand]
-    big, c = torch.iinfo(torch.int32).max, coords[:, :2].int()
-    ok = torch.ones(len(cand), dtype=torch.bool, device=fk.device)
-    for d in range(2):                                           # [n,K] temporaries, one axis at a time
-        hi = torch.where(m, c[:, d][None, :], -big).amax(1)
-        lo = torch.where(m, c[:, d][None, :], big).amin(1)
-        ok &= ~((hi - lo).double() / float(ext[d]) > instance_to_scene_max_ratio)
-    if bool(ok.any()):
-        cand, maskness, m = cand[ok], maskness[ok], m[ok]
-    mf = m.float()
-    inter = mf @ mf.T
-    n_i = counts[cand].float()
-    union = n_i[:, None] + n_i[None, :] - inter
-    kill = torch.where(union > 0, inter / union > nms_thr, torch.ones_like(union, dtype=torch.bool)).cpu().numpy()
-    n = len(kill)
-    dead = np.zeros(n, bool)
-    for i in range(n):
-        if not dead[i]:
-            dead[i + 1:] |= kill[i, i + 1:]
-    maskness = torch.where(torch.from_numpy(~dead).to(fk.device), maskness, torch.zeros_like(maskness))
-    maskness, by = torch.sort(maskness, descending=True, stable=True)
-    maskness, cand = maskness[:max_instance_num], cand[by[:max_instance_num]]
-    sel = maskness > nms_maskness_threshold
-    return cand[sel], maskness[sel]
+    (cand,), maskness = torch_select(lambda: masks[cand], maskness, [cand], coords, ext, instance_to_scene_max_ratio,
+                                     nms_thr, max_instance_num, nms_maskness_threshold, counts)
+    return cand, maskness
 
 
 def device_freemask(fk, coords, fq, ext, **p):
@@ -188,30 +199,9 @@ def torch_freemask_segments(fk, coords, ids, conn, ext, hard_mask_threshold, min
     maskness, by = torch.sort(maskness, descending=True, stable=True)
     rows, query, root = rows[by], query[by], root[by]
     vox = torch.cat([rows, rows.new_zeros((len(rows), 1))], 1)[:, torch.where(idx >= 0, idx, torch.full_like(idx, S))]
-    m = vox >= hard_mask_threshold
-    big, c = torch.iinfo(torch.int32).max, coords[:, :2].int()
-    ok = torch.ones(len(m), dtype=torch.bool, device=dev)
-    for d in range(2):
-        hi = torch.where(m, c[:, d][None, :], -big).amax(1)
-        lo = torch.where(m, c[:, d][None, :], big).amin(1)
-        ok &= ~((hi - lo).double() / float(ext[d]) > instance_to_scene_max_ratio)
-    if bool(ok.any()):
-        m, query, root, maskness = m[ok], query[ok], root[ok], maskness[ok]
-    mf = m.float()
-    inter = mf @ mf.T
-    n_i = mf.sum(1)
-    union = n_i[:, None] + n_i[None, :] - inter
-    kill = torch.where(union > 0, inter / union > nms_thr, torch.ones_like(union, dtype=torch.bool)).cpu().numpy()
-    dead = np.zeros(len(kill), bool)
-    for i in range(len(kill)):
-        if not dead[i]:
-            dead[i + 1:] |= kill[i, i + 1:]
-    maskness = torch.where(torch.from_numpy(~dead).to(dev), maskness, torch.zeros_like(maskness))
-    maskness, by = torch.sort(maskness, descending=True, stable=True)
-    by = by[:max_instance_num]
-    maskness, query, root = maskness[:max_instance_num], query[by], root[by]
-    sel = maskness > nms_maskness_threshold
-    return uniq[query[sel]], uniq[root[sel]], maskness[sel]
+    (query, root), maskness = torch_select(lambda: vox >= hard_mask_threshold, maskness, [query, root], coords, ext,
+                                           instance_to_scene_max_ratio, nms_thr, max_instance_num, nms_maskness_threshold)
+    return uniq[query], uniq[root], maskness
 
 
 def device_freemask_segments(fk, coords, ids, conn, ext, **p):

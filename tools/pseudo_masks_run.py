@@ -76,13 +76,26 @@ def synthetic_scene_files(n, out_dir, seed=500):
     return paths
 
 
+def pending_scene(path, out_dir):
+    """-> (scene name, path of its cloud file), or None when that file exists: the scene is done (reference :550-551)."""
+    name = os.path.splitext(os.path.basename(path))[0]
+    cloud_file = os.path.join(out_dir, f"{name}_cloud.npy")
+    return None if os.path.exists(cloud_file) else (name, cloud_file)
+
+
+def write_scene(out_dir, name, cloud_file, all_masks, full):
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"{name}_masks.npy"), all_masks)
+    np.save(cloud_file, full.astype(np.single))                     # written last: its presence marks "done"
+
+
 def process_scene(path, out_dir, device, ncut_args):
     """-> (scene name, number of masks, seconds) or None when the scene was already processed."""
     from unscene3d_amd.pseudo_masks import ncut, pipeline
-    name = os.path.splitext(os.path.basename(path))[0]
-    cloud_file = os.path.join(out_dir, f"{name}_cloud.npy")
-    if os.path.exists(cloud_file):                                  # reference :550-551
+    todo = pending_scene(path, out_dir)
+    if todo is None:
         return None
+    name, cloud_file = todo
     t0 = time.perf_counter()
     z = np.load(path)
     coords = torch.from_numpy(z["coords"].astype(np.int32)).to(device)
@@ -103,9 +116,7 @@ def process_scene(path, out_dir, device, ncut_args):
     voxel_masks = np.asarray(bip).T[inv] if len(bip) else np.zeros((len(inv), 0), bool)
     full = z["full_res_coords"].astype(np.float32)
     _, all_masks = pipeline.masks_to_full_resolution(coords, full, voxel_size, segment_ids.cpu().numpy(), voxel_masks)
-    os.makedirs(out_dir, exist_ok=True)
-    np.save(os.path.join(out_dir, f"{name}_masks.npy"), all_masks)
-    np.save(cloud_file, full.astype(np.single))                     # written last: its presence marks "done"
+    write_scene(out_dir, name, cloud_file, all_masks, full)
     return name, int(all_masks.shape[1]), time.perf_counter() - t0
 
 
@@ -113,10 +124,10 @@ def process_scene_freemask(path, out_dir, device, fm_args, modality="2d", resolu
     """FreeMask (voxel or segment mode) on one scene file -> (scene name, number of masks, seconds); None when already
     processed.  A scene without instances writes nothing (the reference prints and skips it)."""
     from unscene3d_amd.pseudo_masks import freemask as fm
-    name = os.path.splitext(os.path.basename(path))[0]
-    cloud_file = os.path.join(out_dir, f"{name}_cloud.npy")
-    if os.path.exists(cloud_file):
+    todo = pending_scene(path, out_dir)
+    if todo is None:
         return None
+    name, cloud_file = todo
     t0 = time.perf_counter()
     z = np.load(path)
     key = f"feats_{modality}"
@@ -139,9 +150,7 @@ def process_scene_freemask(path, out_dir, device, fm_args, modality="2d", resolu
         return name, 0, time.perf_counter() - t0
     full = z["full_res_coords"].astype(np.float32)
     all_masks = fm.soft_masks_to_full_resolution(r.key_coords, r.tensor_stride, full, voxel_size, r.soft_masks)
-    os.makedirs(out_dir, exist_ok=True)
-    np.save(os.path.join(out_dir, f"{name}_masks.npy"), all_masks)
-    np.save(cloud_file, full.astype(np.single))                     # written last: its presence marks "done"
+    write_scene(out_dir, name, cloud_file, all_masks, full)
     return name, int(all_masks.shape[1]), time.perf_counter() - t0
 
 

@@ -5,13 +5,15 @@ A mask is a threshold on one min-max-normalised cosine row, so nothing of size Q
 streaming matrix-core passes (csrc/freemask.hip) give bit-packed masks [Q, ceil(K/64)] with their sizes and maskness
 numerators, the extent filter and the greedy mask NMS work on the packed rows, and only the f32 rows of the (at most
 `max_instance_num`) survivors are formed at the end.  The sorts, the cuts and the selects between the kernels are torch
-operators on Q-sized vectors.
+operators on Q-sized vectors: `_select`, the one selection tail of both modes (stable sort by maskness, x/y extent
+filter, greedy NMS, stable sort, the two cuts); a mode hands it its candidates' rows, boxes and NMS.
 
 Where this differs from the reference, on purpose:
 * ties of the maskness sorts: `torch.argsort` leaves their order unspecified; here both sorts are stable, the lower
   query index comes first;
 * when NO mask passes the extent filter the reference goes on with all of them but hands `matrix_nms` the stale,
-  unsorted `sum_masks` of line 279; here the NMS always gets the counts that belong to its masks;
+  unsorted `sum_masks` of line 279; here the NMS always gets the counts that belong to its masks (`_select` hands its
+  NMS row indices, never counts);
 * the lift's rounding shift: the reference hard-codes `lr_coords + 2` ("at 1/4 resolution"); here it defaults to
   tensor_stride / 2 (= 2 at scale 4) and can be overridden.
 
@@ -32,8 +34,8 @@ Further deviations there, on purpose:
   the blob that slides into a popped blob's place (`pop(fused_id)`, then `fused_id += 1`), so a segment bridging three
   blobs can leave two connected blobs apart.  The rows of one query are ordered by their part's smallest segment index;
   the reference's blob order matters only for exact maskness ties;
-* (e) the NMS always gets the voxel counts of its own rows (voxel-mode deviation (b); here the stale counts would even
-  be segment counts);
+* (e) the NMS always gets the voxel counts of its own rows (the voxel-mode deviation above, kept by the same
+  `_select`; here the stale counts would even be segment counts);
 * (f) the viewer call (:210), the `.ply` dump and the PCA colouring are not ported;
 * (g) the segment column of `_cloud.npy` is not reproduced (the reference indexes input-voxel ids with key-voxel
   matches, :506).
@@ -68,7 +70,8 @@ class SceneMasks(NamedTuple):
     tensor_stride: int
 
 
-def _refuse(similarity_metric="cos", segment_ids=None, use_fps_sampling=False, frame_fusion="mean"):
+def _refuse(similarity_metric="cos", segment_ids=None, use_fps_sampling=False, frame_fusion="mean", **_):
+    """The refused keywords of either mode, by name: `_refuse(**kw)` reads them from a scene function's keywords."""
     if segment_ids is not None and len(segment_ids) > 0:
         raise NotImplementedError("segment_ids= is not taken here: that branch of the reference opens an interactive "
                                   "viewer (freemask_main.py:210) in the middle of the computation; segment mode runs "
@@ -177,27 +180,78 @@ def mask_extent(bits: torch.Tensor, key_coords: torch.Tensor):
     return lo, hi
 
 
-def mask_nms(bits: torch.Tensor, counts: torch.Tensor, order: torch.Tensor, nms_thr: float = 0.5) -> torch.Tensor:
+def mask_nms(bits: torch.Tensor, counts: torch.Tensor, order: torch.Tensor, nms_thr: float = 0.5,
+             weight=None) -> torch.Tensor:
     """Greedy mask NMS (reference matrix_nms(kernel='mask')): `order` lists rows of `bits` by descending score; a
     live mask kills every later live one with `union > 0 ? inter / union > nms_thr : true` (an f32 division of exact
-    integers).  -> keep bool[len(order)], by position in `order`."""
+    integers).  -> keep bool[len(order)], by position in `order`.
+    With `weight` i32[S], one per bit: inter = sum of weight over the AND of two rows, `counts` the rows' weighted
+    sizes.  Exact while sum(weight) < 2^24 (checked)."""
     require_device()
     _chk(bits, torch.int64, "bits")
     _chk(counts, torch.int32, "counts")
+    if weight is not None:
+        _chk(weight, torch.int32, "weight")
     order = order.to(device=bits.device, dtype=torch.int32).contiguous()
     n = order.numel()
     keep = torch.empty(n, dtype=torch.uint8, device=bits.device)
     if n == 0:
         return keep.bool()
-    if bits.dim() != 2 or counts.numel() != bits.shape[0] or bits.shape[1] == 0:
-        raise RuntimeError("mask_nms: bits [rows, W >= 1] and counts [rows] do not match")
+    if bits.dim() != 2 or counts.numel() != bits.shape[0] or bits.shape[1] == 0 or (
+            weight is not None and bits.shape[1] != (weight.numel() + 63) // 64):
+        raise RuntimeError("mask_nms: bits [rows, W >= 1], counts [rows] and weight [S], W = ceil(S/64), do not match")
     if int(order.min()) < 0 or int(order.max()) >= bits.shape[0]:
         raise RuntimeError("mask_nms: order out of range")
+    if weight is not None and (int(weight.min()) < 0 or int(weight.long().sum()) >= 1 << 24):
+        raise RuntimeError("mask_nms: weights must be >= 0 and sum to less than 2^24")
     nws = lib.usc_mask_bits_nms_ws_bytes(n)
     ws = _ws(nws, bits.device)
-    check(lib.usc_mask_bits_nms(_ptr(bits), _ptr(counts), bits.shape[1] * 64, _ptr(order), n, float(nms_thr),
-                                _ptr(keep), _ptr(ws), nws, _stream()), "usc_mask_bits_nms")
+    if weight is None:
+        check(lib.usc_mask_bits_nms(_ptr(bits), _ptr(counts), bits.shape[1] * 64, _ptr(order), n, float(nms_thr),
+                                    _ptr(keep), _ptr(ws), nws, _stream()), "usc_mask_bits_nms")
+    else:
+        check(lib.usc_mask_bits_nms_weighted(_ptr(bits), _ptr(counts), _ptr(weight), weight.numel(), _ptr(order), n,
+                                             float(nms_thr), _ptr(keep), _ptr(ws), nws, _stream()),
+              "usc_mask_bits_nms_weighted")
     return keep.bool()
+
+
+def mask_nms_weighted(bits, counts, weight, order, nms_thr: float = 0.5) -> torch.Tensor:
+    """`mask_nms(bits, counts, order, nms_thr, weight)`."""
+    return mask_nms(bits, counts, order, nms_thr, weight)
+
+
+def _select(maskness, rows, lo, hi, scene_extent, nms, *, instance_to_scene_max_ratio, max_instance_num,
+            nms_maskness_threshold):
+    """Selection steps (4) to (7) of either mode (:353-354, :375-412), torch operators only.  maskness f32[n] of the
+    candidates in candidate order, rows int[n]: every candidate's row in `lo`, `hi` i32[*, 3] and in what `nms` works on,
+    scene_extent [3], nms(rows in score order) -> keep bool.  -> (maskness f32[M], rows i64[M]) of the survivors in the
+    reference's output order, or None where the reference prints "No candidates left" and skips the scene.
+    `nms` gets the rows to judge and nothing else, so the counts it uses are those rows' own: the reference's stale
+    `sum_masks` of the "none left -> all stay" branch has no counterpart here."""
+    maskness, by = torch.sort(maskness, descending=True, stable=True)              # :354, ties: lower row first
+    rows = rows[by]
+    # extent filter (:375-395), x and y only, in f64 like numpy's int / int division
+    ext = (hi[rows, :2].long() - lo[rows, :2].long()).double()
+    scene = torch.as_tensor(scene_extent, device=maskness.device).double().flatten()[:2]
+    ok = ~((ext / scene) > instance_to_scene_max_ratio).any(1)
+    if bool(ok.any()):                                                             # none left -> all stay
+        rows, maskness = rows[ok], maskness[ok]
+    keep = nms(rows)                                                               # :398
+    maskness = torch.where(keep, maskness, torch.zeros_like(maskness))
+    maskness, by = torch.sort(maskness, descending=True, stable=True)              # :400-403
+    by = by[:max_instance_num]
+    maskness, rows = maskness[:max_instance_num], rows[by]
+    sel = maskness > nms_maskness_threshold                                        # :412
+    if not bool(sel.any()):
+        return None
+    return maskness[sel], rows[sel]
+
+
+def _empty(K, dev, n_index):
+    """The result of a scene the reference skips: no rows of K voxels, no maskness, `n_index` empty index vectors."""
+    return (torch.zeros((0, K), dtype=torch.float32, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
+            *(torch.zeros(0, dtype=torch.int64, device=dev) for _ in range(n_index)))
 
 
 def freemask(key_feats, key_coords, query_feats, scene_extent, *, hard_mask_threshold=0.35, min_mask_points=10,
@@ -209,93 +263,21 @@ def freemask(key_feats, key_coords, query_feats, scene_extent, *, hard_mask_thre
     tensors where the reference prints "No instances detected" / "No candidates left" and skips the scene."""
     _refuse(similarity_metric, segment_ids, use_fps_sampling, frame_fusion)
     dev = key_feats.device
-    K = key_feats.shape[0]
-    empty = (torch.zeros((0, K), dtype=torch.float32, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
-             torch.zeros(0, dtype=torch.int64, device=dev))
+    empty = _empty(key_feats.shape[0], dev, 1)
     cm, prep = _cosine_masks(key_feats, query_feats, hard_mask_threshold)
     cand = torch.nonzero(cm.counts > min_mask_points).flatten()                    # :271, ascending query index
     if cand.numel() == 0:
         return empty
     maskness = cm.soft_sums[cand] / cm.counts[cand]                                # :353 (f32 / integer)
-    maskness, by = torch.sort(maskness, descending=True, stable=True)              # :354, ties: lower query first
-    cand = cand[by]
-    # extent filter (:375-395), x and y only, in f64 like numpy's int / int division
     coords = key_coords[:, -3:].to(device=dev, dtype=torch.int32).contiguous()
     lo, hi = mask_extent(cm.bits, coords)
-    ext = (hi[cand, :2].long() - lo[cand, :2].long()).double()
-    scene = torch.as_tensor(scene_extent, device=dev).double().flatten()[:2]
-    ok = ~((ext / scene) > instance_to_scene_max_ratio).any(1)
-    if bool(ok.any()):
-        cand, maskness = cand[ok], maskness[ok]
-    keep = mask_nms(cm.bits, cm.counts, cand, nms_thr)                             # :398
-    maskness = torch.where(keep, maskness, torch.zeros_like(maskness))
-    maskness, by = torch.sort(maskness, descending=True, stable=True)              # :400-403
-    by = by[:max_instance_num]
-    maskness, cand = maskness[:max_instance_num], cand[by]
-    sel = maskness > nms_maskness_threshold                                        # :412
-    if not bool(sel.any()):
+    chosen = _select(maskness, cand, lo, hi, scene_extent, lambda order: mask_nms(cm.bits, cm.counts, order, nms_thr),
+                     instance_to_scene_max_ratio=instance_to_scene_max_ratio, max_instance_num=max_instance_num,
+                     nms_maskness_threshold=nms_maskness_threshold)
+    if chosen is None:
         return empty
-    maskness, cand = maskness[sel], cand[sel]
+    maskness, cand = chosen
     return soft_rows(key_feats, query_feats, cm.rowmin, cm.rowmax, cand, prep), maskness, cand
-
-
-def _pool_steps(resolution_scale):
-    steps = int(math.log2(resolution_scale))
-    if resolution_scale < 1 or 2 ** steps != resolution_scale:
-        raise ValueError(f"resolution_scale must be a power of two, got {resolution_scale}")
-    return steps
-
-
-def _scene_extent(coords):
-    c = coords[:, -3:]
-    return (c.amax(0) - c.amin(0)).float()
-
-
-def _from_keys(keys, steps, extent, kw):
-    from .. import MinkowskiEngine as ME
-    pool = ME.MinkowskiAvgPooling(kernel_size=2, stride=2, dimension=3)
-    queries = keys
-    for _ in range(steps):                                                         # :173-183
-        queries = pool(queries)
-    kf, qf = keys.F.detach().float().contiguous(), queries.F.detach().float().contiguous()
-    kc = keys.C[:, 1:].contiguous()
-    soft, maskness, qi = freemask(kf, kc, qf, extent, **kw)
-    return SceneMasks(soft, maskness, qi, kc, keys.tensor_stride[0])
-
-
-def freemask_scene(model, sinput, resolution_scale=2, **kw) -> SceneMasks:
-    """3D branch (:98-101, :171-183): keys = the backbone's `res_{scale}` feature map, queries = the keys
-    average-pooled log2(scale) more times."""
-    _refuse(kw.get("similarity_metric", "cos"), kw.get("segment_ids"), kw.get("use_fps_sampling", False),
-            kw.get("frame_fusion", "mean"))
-    steps = _pool_steps(resolution_scale)
-    with torch.no_grad():
-        _, feature_maps = model(sinput)
-        return _from_keys(feature_maps[f"res_{resolution_scale}"], steps, _scene_extent(sinput.C), kw)
-
-
-def freemask_from_voxel_feats(coords, feats, resolution_scale=2, **kw) -> SceneMasks:
-    """Image branch (:162-179): per-voxel features (e.g. encode_scene_feats_2d's) on the unique voxel coordinates
-    `coords` int[N,3] or [N,4] are average-pooled log2(scale) times to the keys, and as often again to the queries."""
-    from .. import MinkowskiEngine as ME
-    _refuse(kw.get("similarity_metric", "cos"), kw.get("segment_ids"), kw.get("use_fps_sampling", False),
-            kw.get("frame_fusion", "mean"))
-    steps = _pool_steps(resolution_scale)
-    require_device()
-    coords = coords.to(torch.int32)
-    if coords.shape[1] == 3:
-        coords = torch.cat([torch.zeros_like(coords[:, :1]), coords], 1)
-    with torch.no_grad():
-        keys = ME.SparseTensor(features=feats.float().contiguous(), coordinates=coords.contiguous(), device=feats.device)
-        pool = ME.MinkowskiAvgPooling(kernel_size=2, stride=2, dimension=3)
-        for _ in range(steps):
-            keys = pool(keys)
-        return _from_keys(keys, steps, _scene_extent(coords), kw)
-
-
-def freemask_scene_fn(scene, **kw) -> SceneMasks:
-    """`scene_fn` of PseudoMaskDriver: scene = dict with `coords`, `feats` and optionally `resolution_scale`."""
-    return freemask_from_voxel_feats(scene["coords"], scene["feats"], scene.get("resolution_scale", 2), **kw)
 
 
 # ---------------------------------------------------------------------------------------------------- segment mode
@@ -322,10 +304,6 @@ class SplitRows(NamedTuple):
     seg_counts: torch.Tensor  # i32[R]
     vox_counts: torch.Tensor  # i32[R]  sum of w over the part
     soft_sums: torch.Tensor   # f32[R]  sum of the soft values over the part, ascending segment index
-
-
-def _refuse_segments(similarity_metric="cos", use_fps_sampling=False, frame_fusion="mean"):
-    _refuse(similarity_metric, None, use_fps_sampling, frame_fusion)
 
 
 def segment_adjacency(seg_connectivity, unique_segments):
@@ -425,32 +403,6 @@ def mask_split(label, n_comp, seg_weight, soft, soft_row) -> SplitRows:
     return out
 
 
-def mask_nms_weighted(bits, counts, weight, order, nms_thr: float = 0.5) -> torch.Tensor:
-    """`mask_nms` with a weight per bit: inter = sum of weight over the AND of two rows, `counts` the rows' weighted
-    sizes.  Exact while sum(weight) < 2^24 (checked)."""
-    require_device()
-    _chk(bits, torch.int64, "bits")
-    _chk(counts, torch.int32, "counts")
-    _chk(weight, torch.int32, "weight")
-    order = order.to(device=bits.device, dtype=torch.int32).contiguous()
-    n = order.numel()
-    keep = torch.empty(n, dtype=torch.uint8, device=bits.device)
-    if n == 0:
-        return keep.bool()
-    if bits.dim() != 2 or counts.numel() != bits.shape[0] or bits.shape[1] != (weight.numel() + 63) // 64:
-        raise RuntimeError("mask_nms_weighted: bits [rows, ceil(S/64)], counts [rows] and weight [S] do not match")
-    if int(order.min()) < 0 or int(order.max()) >= bits.shape[0]:
-        raise RuntimeError("mask_nms_weighted: order out of range")
-    if int(weight.min()) < 0 or int(weight.long().sum()) >= 1 << 24:
-        raise RuntimeError("mask_nms_weighted: weights must be >= 0 and sum to less than 2^24")
-    nws = lib.usc_mask_bits_nms_ws_bytes(n)
-    ws = _ws(nws, bits.device)
-    check(lib.usc_mask_bits_nms_weighted(_ptr(bits), _ptr(counts), _ptr(weight), weight.numel(), _ptr(order), n,
-                                         float(nms_thr), _ptr(keep), _ptr(ws), nws, _stream()),
-          "usc_mask_bits_nms_weighted")
-    return keep.bool()
-
-
 def segment_features(key_feats, key_segment_ids):
     """:202-225 -> (seg_feats f32[S, C], unique_segments i64[S] sorted, idx i64[K]: the segment index of every key voxel,
     -1 for the voxels of a dropped (all-zero) segment)."""
@@ -489,7 +441,7 @@ def freemask_segments(key_feats, key_coords, key_segment_ids, seg_connectivity, 
     (or [K,4]: b,x,y,z), key_segment_ids i64[K] (the ids pooled to the keys' resolution), seg_connectivity int[P,2]
     (pairs of ids), scene_extent [3].  -> SegmentMasks in the reference's output order; empty tensors where the
     reference prints "No instances detected" / "No candidates left" and skips the scene."""
-    _refuse_segments(similarity_metric, use_fps_sampling, frame_fusion)
+    _refuse(similarity_metric, None, use_fps_sampling, frame_fusion)
     require_device()
     dev = key_feats.device
     K = key_feats.shape[0]
@@ -498,9 +450,7 @@ def freemask_segments(key_feats, key_coords, key_segment_ids, seg_connectivity, 
         raise RuntimeError("freemask_segments: key_segment_ids must have one id per key voxel")
     if K >= 1 << 24:
         raise RuntimeError("freemask_segments: K >= 2^24 key voxels: voxel counts would not be exact in f32")
-    empty = SegmentMasks(torch.zeros((0, K), dtype=torch.float32, device=dev),
-                         torch.zeros(0, dtype=torch.float32, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
-                         torch.zeros(0, dtype=torch.int64, device=dev))
+    empty = SegmentMasks(*_empty(K, dev, 2))
     if K == 0:
         return empty
     seg_feats, unique_segments, idx = segment_features(key_feats, ids)             # :202-228
@@ -525,30 +475,41 @@ def freemask_segments(key_feats, key_coords, key_segment_ids, seg_connectivity, 
     if part.numel() == 0:
         return empty
     maskness = sp.soft_sums[part] / sp.seg_counts[part]                            # :353, a segment-level mean
-    maskness, by = torch.sort(maskness, descending=True, stable=True)              # :354
-    part = part[by]
-    # extent of the remapped masks (:361-395): box union over the row's segments, x and y only, f64 like numpy
+    # boxes of the remapped masks (:361-395): the union of the boxes of a row's segments
     lo, _ = mask_extent(sp.bits, seg_lo)
     _, hi = mask_extent(sp.bits, seg_hi)
-    ext = (hi[part, :2].long() - lo[part, :2].long()).double()
-    scene = torch.as_tensor(scene_extent, device=dev).double().flatten()[:2]
-    ok = ~((ext / scene) > instance_to_scene_max_ratio).any(1)
-    if bool(ok.any()):
-        part, maskness = part[ok], maskness[ok]
-    keep = mask_nms_weighted(sp.bits, sp.vox_counts, w, part, nms_thr)             # :398 on voxel counts
-    maskness = torch.where(keep, maskness, torch.zeros_like(maskness))
-    maskness, by = torch.sort(maskness, descending=True, stable=True)              # :400-403
-    by = by[:max_instance_num]
-    maskness, part = maskness[:max_instance_num], part[by]
-    sel = maskness > nms_maskness_threshold                                        # :412
-    if not bool(sel.any()):
+    chosen = _select(maskness, part, lo, hi, scene_extent,
+                     lambda order: mask_nms(sp.bits, sp.vox_counts, order, nms_thr, w),     # :398 on voxel counts
+                     instance_to_scene_max_ratio=instance_to_scene_max_ratio, max_instance_num=max_instance_num,
+                     nms_maskness_threshold=nms_maskness_threshold)
+    if chosen is None:
         return empty
-    maskness, part = maskness[sel], part[sel]
+    maskness, part = chosen
     src, root = sp.src[part].long(), sp.root[part].long()
     seg_rows = torch.where(label[src] == root[:, None], soft[src], torch.zeros((), dtype=torch.float32, device=dev))
     seg_rows = torch.cat([seg_rows, torch.zeros((len(part), 1), dtype=torch.float32, device=dev)], 1)
     out = seg_rows[:, torch.where(idx >= 0, idx, torch.full_like(idx, S))]         # :361-368, the only [M, K] tensor
     return SegmentMasks(out.contiguous(), maskness, unique_segments[cand[src]], unique_segments[root])
+
+
+# ------------------------------------------------------------------------------------- scene level, both modes
+def _pool_steps(resolution_scale):
+    steps = int(math.log2(resolution_scale))
+    if resolution_scale < 1 or 2 ** steps != resolution_scale:
+        raise ValueError(f"resolution_scale must be a power of two, got {resolution_scale}")
+    return steps
+
+
+def _scene_extent(coords):
+    c = coords[:, -3:]
+    return (c.amax(0) - c.amin(0)).float()
+
+
+def _pool(x, steps, pooling):
+    pool = pooling(kernel_size=2, stride=2, dimension=3)
+    for _ in range(steps):
+        x = pool(x)
+    return x
 
 
 def _pool_segment_ids(segment_ids, like, steps):
@@ -564,54 +525,87 @@ def _pool_segment_ids(segment_ids, like, steps):
     if steps == 0:          # no pooling: the range check of the pooling operator still holds
         if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= ops.MAXPOOL_I32_ID_LIMIT):
             raise RuntimeError(f"segment ids outside [0, 2^24): {int(ids.min())} .. {int(ids.max())}")
-    pool = ME.MinkowskiMaxPooling(kernel_size=2, stride=2, dimension=3)
-    for _ in range(steps):
-        pooled = pool(pooled)
-    return pooled.F.reshape(-1).to(torch.int64)
+    return _pool(pooled, steps, ME.MinkowskiMaxPooling).F.reshape(-1).to(torch.int64)
 
 
-def _segments_from_keys(keys, key_ids, seg_connectivity, extent, kw):
+def _keys_from_voxel_feats(coords, feats, steps, unique_for=None):
+    """coords int[N,3] or [N,4], feats [N,d] -> (the fine tensor on them, the keys: it average-pooled `steps` times
+    (:162-179), the scene extent).  `unique_for` names the caller that needs one row per coordinate."""
+    from .. import MinkowskiEngine as ME
+    require_device()
+    coords = coords.to(torch.int32)
+    if coords.shape[1] == 3:
+        coords = torch.cat([torch.zeros_like(coords[:, :1]), coords], 1)
+    fine = ME.SparseTensor(features=feats.float().contiguous(), coordinates=coords.contiguous(), device=feats.device)
+    if unique_for and fine.F.shape[0] != coords.shape[0]:
+        raise RuntimeError(f"{unique_for}: coords must be unique")
+    return fine, _pool(fine, steps, ME.MinkowskiAvgPooling), _scene_extent(coords)
+
+
+def _keys_from_backbone(model, sinput, resolution_scale):
+    """:98-101: the backbone's `res_{scale}` feature map."""
+    _, feature_maps = model(sinput)
+    return feature_maps[f"res_{resolution_scale}"]
+
+
+def _from_keys(keys, steps, extent, kw, key_ids=None, seg_connectivity=None):
+    """Voxel mode (queries = the keys average-pooled `steps` more times, :173-183) or, with `key_ids`, segment mode."""
+    from .. import MinkowskiEngine as ME
     kf = keys.F.detach().float().contiguous()
     kc = keys.C[:, 1:].contiguous()
-    r = freemask_segments(kf, kc, key_ids, seg_connectivity, extent, **kw)
-    return SegmentSceneMasks(r.soft_masks, r.maskness, r.query_segment, r.part_root, kc, keys.tensor_stride[0])
+    if key_ids is None:
+        qf = _pool(keys, steps, ME.MinkowskiAvgPooling).F.detach().float().contiguous()
+        return SceneMasks(*freemask(kf, kc, qf, extent, **kw), kc, keys.tensor_stride[0])
+    return SegmentSceneMasks(*freemask_segments(kf, kc, key_ids, seg_connectivity, extent, **kw), kc,
+                             keys.tensor_stride[0])
+
+
+def freemask_scene(model, sinput, resolution_scale=2, **kw) -> SceneMasks:
+    """3D branch (:98-101, :171-183): keys = the backbone's `res_{scale}` feature map, queries = the keys
+    average-pooled log2(scale) more times."""
+    _refuse(**kw)
+    steps = _pool_steps(resolution_scale)
+    with torch.no_grad():
+        return _from_keys(_keys_from_backbone(model, sinput, resolution_scale), steps, _scene_extent(sinput.C), kw)
+
+
+def freemask_from_voxel_feats(coords, feats, resolution_scale=2, **kw) -> SceneMasks:
+    """Image branch (:162-179): per-voxel features (e.g. encode_scene_feats_2d's) on the unique voxel coordinates
+    `coords` int[N,3] or [N,4] are average-pooled log2(scale) times to the keys, and as often again to the queries."""
+    _refuse(**kw)
+    steps = _pool_steps(resolution_scale)
+    with torch.no_grad():
+        _, keys, extent = _keys_from_voxel_feats(coords, feats, steps)
+        return _from_keys(keys, steps, extent, kw)
+
+
+def freemask_scene_fn(scene, **kw) -> SceneMasks:
+    """`scene_fn` of PseudoMaskDriver: scene = dict with `coords`, `feats` and optionally `resolution_scale`."""
+    return freemask_from_voxel_feats(scene["coords"], scene["feats"], scene.get("resolution_scale", 2), **kw)
 
 
 def freemask_segments_scene(model, sinput, segment_ids, seg_connectivity, resolution_scale=2, **kw) -> SegmentSceneMasks:
     """3D branch: keys = the backbone's `res_{scale}` feature map; `segment_ids` int[N] are the ids of `sinput`'s
     voxels, max-pooled log2(scale) times onto the keys' coordinate map."""
-    _refuse_segments(kw.get("similarity_metric", "cos"), kw.get("use_fps_sampling", False), kw.get("frame_fusion", "mean"))
+    _refuse(**kw)
     steps = _pool_steps(resolution_scale)
     with torch.no_grad():
-        _, feature_maps = model(sinput)
-        keys = feature_maps[f"res_{resolution_scale}"]
+        keys = _keys_from_backbone(model, sinput, resolution_scale)
         key_ids = _pool_segment_ids(segment_ids, sinput, steps)
         if key_ids.numel() != keys.F.shape[0]:
             raise RuntimeError("freemask_segments_scene: the pooled ids and the feature map live on different maps")
-        return _segments_from_keys(keys, key_ids, seg_connectivity, _scene_extent(sinput.C), kw)
+        return _from_keys(keys, steps, _scene_extent(sinput.C), kw, key_ids, seg_connectivity)
 
 
 def freemask_segments_from_voxel_feats(coords, feats, segment_ids, seg_connectivity, resolution_scale=2,
                                        **kw) -> SegmentSceneMasks:
     """Image branch: per-voxel features on the unique voxel coordinates `coords` int[N,3] or [N,4] are average-pooled
     log2(scale) times to the keys, the ids `segment_ids` int[N] max-pooled as often over the same maps."""
-    from .. import MinkowskiEngine as ME
-    _refuse_segments(kw.get("similarity_metric", "cos"), kw.get("use_fps_sampling", False), kw.get("frame_fusion", "mean"))
+    _refuse(**kw)
     steps = _pool_steps(resolution_scale)
-    require_device()
-    coords = coords.to(torch.int32)
-    if coords.shape[1] == 3:
-        coords = torch.cat([torch.zeros_like(coords[:, :1]), coords], 1)
     with torch.no_grad():
-        fine = ME.SparseTensor(features=feats.float().contiguous(), coordinates=coords.contiguous(), device=feats.device)
-        if fine.F.shape[0] != coords.shape[0]:
-            raise RuntimeError("freemask_segments_from_voxel_feats: coords must be unique")
-        key_ids = _pool_segment_ids(segment_ids, fine, steps)
-        keys = fine
-        pool = ME.MinkowskiAvgPooling(kernel_size=2, stride=2, dimension=3)
-        for _ in range(steps):
-            keys = pool(keys)
-        return _segments_from_keys(keys, key_ids, seg_connectivity, _scene_extent(coords), kw)
+        fine, keys, extent = _keys_from_voxel_feats(coords, feats, steps, "freemask_segments_from_voxel_feats")
+        return _from_keys(keys, steps, extent, kw, _pool_segment_ids(segment_ids, fine, steps), seg_connectivity)
 
 
 def freemask_segments_scene_fn(scene, **kw) -> SegmentSceneMasks:
