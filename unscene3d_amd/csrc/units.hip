@@ -8,6 +8,10 @@
 // (mask-sorted / tile-compacted / row-order / pair-list form, weight transposes, split counts) that lived in
 // unscene3d_amd/ops.py is restated here so that both paths launch identical kernels.
 //
+// Inside this file each such decision is written once: plan_table_gemm (which table-form GEMM, with what scratch: sized
+// by table_gemm_ws, executed by table_gemm), wgrad_job / issue_wgrad (which weight-gradient kernel, on which operands:
+// inline, on the lane, held, or alone out of a deferred group) and forward_unit (the frame of the three forward units).
+//
 // Reference: models/modules/resnet_block.py:48-64 (conv -> norm -> relu / `out += residual`),
 // models/res16unet.py:231-297 (conv{0..4} / convtr{4..7} + bn + relu), models/modules/common.py:125-188.
 #include <stdlib.h>
@@ -44,38 +48,38 @@ inline bool sorted_ok(const usc_kmap* m, int cin, int cout) {
   return m->nbr && m->perm && m->tile_mask && m->K > 1 && m->K <= 32 && cin % 32 == 0 && cout % 32 == 0 && cin <= 4096;
 }
 
-// bytes the table-form GEMM needs (out rows n_out, W possibly to be transposed first)
-int64_t table_gemm_ws(const usc_kmap* m, int64_t n_out, int cin, int cout, int K, bool want_transposed) {
-  if (m->nbr && sorted_ok(m, cin, cout) && !table_is_compact(n_out, cin, cout, K))
-    return align_up(usc_spconv_sorted_ws_bytes(n_out, cin, cout, K), 256);
-  int64_t b = align_up(usc_spconv_gather_gemm_ws_bytes(n_out, cin, cout, K), 256);
-  if (want_transposed && !(m->nbr && table_is_compact(n_out, cin, cout, K))) b += align_up((int64_t)K * cin * cout * 4, 256);
-  return b;
+// What one table-form GEMM over the map's table launches and takes from the cursor (out rows n_out; wt: the mirrored
+// transpose of W is meant).  Sized by table_gemm_ws and executed by table_gemm, so the two cannot drift apart.
+struct TableGemmPlan {
+  bool sorted;          // the mask-sorted kernel; else the gather kernel (tile-compacted where usc_spconv_plan says so)
+  int64_t wt_bytes;     // first take: > 0 when an explicit usc_weight_transpose into it precedes the launch
+  int64_t gemm_bytes;   // second take: the kernel's own scratch (0: none taken)
+};
+TableGemmPlan plan_table_gemm(const usc_kmap* m, int64_t n_out, int cin, int cout, int K, bool wt) {
+  const bool compact = m->nbr && table_is_compact(n_out, cin, cout, K);
+  if (sorted_ok(m, cin, cout) && !compact) return {true, 0, usc_spconv_sorted_ws_bytes(n_out, cin, cout, K)};
+  // the transpose is folded into the tile-compacted kernel only
+  return {false, wt && !compact ? (int64_t)K * cin * cout * 4 : 0, usc_spconv_gather_gemm_ws_bytes(n_out, cin, cout, K)};
 }
 
-// out[o] (+)= sum_k in[nbr[k][o]] W[k]; `wt`: W is given as the forward [K, cout, cin] and the mirrored transpose
-// W'[k][c][n] = W[K-1-k][n][c] is meant (mirror only when K > 1).  `nbr` NULL: identity rows (1x1).
+// bytes the table-form GEMM needs
+int64_t table_gemm_ws(const usc_kmap* m, int64_t n_out, int cin, int cout, int K, bool wt) {
+  const TableGemmPlan pl = plan_table_gemm(m, n_out, cin, cout, K, wt);
+  return align_up(pl.wt_bytes, 256) + align_up(pl.gemm_bytes, 256);
+}
+
+// out[o] (+)= sum_k in[nbr[k][o]] W[k] over the map's table; `wt`: W is given as the forward [K, cout, cin] and the
+// mirrored transpose W'[k][c][n] = W[K-1-k][n][c] is meant (mirror only when K > 1).  No table: identity rows (1x1).
 // slices the split-K launch left un-reduced for whoever consumes `out` next (usc_spconv_sorted_gemm_ex)
 struct Slices { const float* partial = nullptr; int G = 0; };
 
-int table_gemm(const usc_kmap* m, const int32_t* nbr, const float* in, int64_t n_in, int cin, const float* W, int K,
-               int cout, int64_t n_out, const float* bias, float* out, int accumulate, int wt, WsCursor ws,
-               usc_stream_t s, Slices* left = nullptr) {
+int table_gemm(const usc_kmap* m, const float* in, int64_t n_in, int cin, const float* W, int K, int cout, int64_t n_out,
+               const float* bias, float* out, int accumulate, int wt, WsCursor ws, usc_stream_t s, Slices* left = nullptr) {
   if (left) *left = Slices{};
   if (n_out == 0) return USC_OK;
-  const bool compact = nbr && table_is_compact(n_out, cin, cout, K);
-  if (nbr && nbr == m->nbr && sorted_ok(m, cin, cout) && !compact) {
-    const int64_t b = usc_spconv_sorted_ws_bytes(n_out, cin, cout, K);
-    void* w = b > 0 ? ws.take(b) : nullptr;
-    USC_REQUIRE(b == 0 || w, "usc unit: workspace too small (sorted gemm)");
-    int32_t G = 0;
-    const int rc = usc_spconv_sorted_gemm_ex(in, n_in, cin, W, K, cout, nbr, m->perm, m->tile_mask, n_out, bias, out,
-                                             accumulate, wt, w, b, left ? &G : nullptr, s);
-    if (!rc && left && G > 0) { left->partial = (const float*)w; left->G = G; }
-    return rc;
-  }
-  if (wt && !compact) {
-    float* Wt = (float*)ws.take((int64_t)K * cin * cout * 4);
+  const TableGemmPlan pl = plan_table_gemm(m, n_out, cin, cout, K, wt != 0);
+  if (pl.wt_bytes > 0) {
+    float* Wt = (float*)ws.take(pl.wt_bytes);
     USC_REQUIRE(Wt, "usc unit: workspace too small (weight transpose)");
     // W is [K, cout, cin] as a forward weight; the product wants [K, cin, cout]
     int rc = usc_weight_transpose(W, K, cout, cin, K > 1 ? 1 : 0, Wt, s);
@@ -83,10 +87,61 @@ int table_gemm(const usc_kmap* m, const int32_t* nbr, const float* in, int64_t n
     W = Wt;
     wt = 0;
   }
-  const int64_t b = usc_spconv_gather_gemm_ws_bytes(n_out, cin, cout, K);
+  const int64_t b = pl.gemm_bytes;
   void* w = b > 0 ? ws.take(b) : nullptr;
-  USC_REQUIRE(b == 0 || w, "usc unit: workspace too small (gather gemm)");
-  return usc_spconv_gather_gemm(in, n_in, cin, W, K, cout, nbr, n_out, bias, out, accumulate, wt, w, b, s);
+  USC_REQUIRE(b == 0 || w, "usc unit: workspace too small (%s gemm)", pl.sorted ? "sorted" : "gather");
+  if (!pl.sorted) return usc_spconv_gather_gemm(in, n_in, cin, W, K, cout, m->nbr, n_out, bias, out, accumulate, wt, w, b, s);
+  int32_t G = 0;
+  const int rc = usc_spconv_sorted_gemm_ex(in, n_in, cin, W, K, cout, m->nbr, m->perm, m->tile_mask, n_out, bias, out,
+                                           accumulate, wt, w, b, left ? &G : nullptr, s);
+  if (!rc && left && G > 0) { left->partial = (const float*)w; left->G = G; }
+  return rc;
+}
+
+struct ConvShape { int64_t n_in, n_out; };   // rows of the convolution's input / output feature matrices
+inline ConvShape conv_shape(const usc_kmap* m, int kind) {
+  return kind == USC_CONV_UP ? ConvShape{m->n_out, m->n_in} : ConvShape{m->n_in, m->n_out};
+}
+
+// ---- a unit's weight gradient -------------------------------------------------------------------------------------
+// dW[k] (+)= sum over the pairs of offset k of x[a]^T dy[b], described completely: built in ONE place (wgrad_job) and
+// launched in ONE place (issue_wgrad), wherever it runs — at once in the caller's scratch, on the lane, noted by the
+// lane's hold, or as the lone launch of a deferred group.
+struct WgradJob {
+  const float* x; const float* dy; float* dW;
+  const int32_t* a_idx; const int32_t* b_idx; const int64_t* koff;   // the pair lists; all NULL: identity rows (K = 1)
+  int64_t rows; int cin, cout, K;
+  int64_t list_bytes;                                                // scratch of the pair-list kernel
+  const int32_t* nbr; int64_t n_out, table_bytes;                    // nbr set: the table form may be taken, with its scratch
+};
+WgradJob wgrad_job(const usc_kmap* m, int kind, ConvShape sh, const float* x, const float* dy, float* dW, int cin, int cout) {
+  WgradJob j{};
+  j.x = x; j.dy = dy; j.dW = dW; j.cin = cin; j.cout = cout;
+  if (m->nbr) {               // the pair lists, in and out swapped for the transposed conv
+    const bool up = kind == USC_CONV_UP;
+    j.a_idx = up ? m->pair_out : m->pair_in;
+    j.b_idx = up ? m->pair_in : m->pair_out;
+    j.koff = m->koff; j.K = m->K; j.rows = m->pair_capacity;
+  } else {                    // no table: identity rows
+    j.K = 1; j.rows = sh.n_in;
+  }
+  j.list_bytes = usc_spconv_wgrad_ws_bytes_rows(m->K, cin, cout, j.rows);
+  // the stem (3 -> 32 channels) has a table-form kernel, on the lane too: it is the LAST weight gradient of the backward
+  // pass — the lane's tail, which the step waits for — and the pair-list kernel needs 110 us for it, the table form 57
+  // (round 6: the lane branch used to send everything through usc_spconv_wgrad)
+  if (kind == USC_CONV_SAME && m->nbr && cin <= 4 && cout == 32 && m->K <= 32) {
+    j.nbr = m->nbr; j.n_out = sh.n_out;
+    j.table_bytes = usc_spconv_wgrad_table_ws_bytes(m->K, cin, cout);
+  }
+  return j;
+}
+// ws / ws_bytes: the scratch the launch may use — the lane's own on the lane, what is left of the caller's when issued
+// inline (an asymmetry kept as it was: "the table form fits" is asked of whichever of the two the job runs in).  The
+// caller has made sure that the pair-list form fits; the table form is taken where it fits too.
+int issue_wgrad(const WgradJob& j, int accumulate, void* ws, int64_t ws_bytes, usc_stream_t s) {
+  if (j.nbr && j.table_bytes <= ws_bytes)
+    return usc_spconv_wgrad_table(j.x, j.cin, j.dy, j.cout, j.nbr, j.K, j.n_out, j.dW, accumulate, ws, j.table_bytes, s);
+  return usc_spconv_wgrad(j.x, j.cin, j.dy, j.cout, j.K, j.a_idx, j.b_idx, j.koff, j.rows, j.dW, accumulate, ws, j.list_bytes, s);
 }
 
 // ---- the weight-gradient lane -----------------------------------------------------------------------------------
@@ -99,14 +154,11 @@ int table_gemm(const usc_kmap* m, const int32_t* nbr, const float* in, int64_t n
 // returns; the input-gradient chain — the critical path of the backward pass — carries on, and the latency-bound
 // weight-gradient launches of the coarse levels fill the CUs it leaves idle.  The caller joins once, when the
 // gradients are needed (usc_wgrad_lane_join), keeps x / dy / dW alive until then, and gives the lane its own scratch.
-// One weight gradient that has been handed to the lane but not launched yet (usc_wgrad_lane_hold).
-struct HeldWgrad { const float* x; const float* dy; float* dW; const int32_t* a_idx; const int32_t* b_idx; const int64_t* koff;
-                   int64_t rows, ws_bytes; int cin, cout, K; };
 struct Lane { hipStream_t st = nullptr; hipEvent_t fork = nullptr, join = nullptr; void* ws = nullptr; int64_t ws_bytes = 0;
               int64_t max_rows = 0; bool dirty = false;
               // hold: weight gradients of maps with >= hold_min_rows rows are only NOTED until the caller's chain reaches a map
               // with <= release_max_rows rows (or the hold is lifted); from then on everything goes to the lane at once
-              bool hold = false; int64_t hold_min_rows = 0, release_max_rows = 0; std::vector<HeldWgrad> held; };
+              bool hold = false; int64_t hold_min_rows = 0, release_max_rows = 0; std::vector<WgradJob> held; };
 Lane g_lane[16];
 Lane* lane_for_current_device() {
   int dev = 0;
@@ -125,18 +177,10 @@ int lane_release(Lane* lane, usc_stream_t s) {
   }
   int rc = USC_OK;
   lane->dirty = true;
-  for (const HeldWgrad& h : lane->held) {
-    rc = usc_spconv_wgrad(h.x, h.cin, h.dy, h.cout, h.K, h.a_idx, h.b_idx, h.koff, h.rows, h.dW, 1, lane->ws, h.ws_bytes,
-                          (usc_stream_t)lane->st);
-    if (rc) break;
-  }
+  for (size_t i = 0; i < lane->held.size() && !rc; ++i)
+    rc = issue_wgrad(lane->held[i], 1, lane->ws, lane->ws_bytes, (usc_stream_t)lane->st);
   lane->held.clear();
   return rc;
-}
-
-struct ConvShape { int64_t n_in, n_out; };   // rows of the convolution's input / output feature matrices
-inline ConvShape conv_shape(const usc_kmap* m, int kind) {
-  return kind == USC_CONV_UP ? ConvShape{m->n_out, m->n_in} : ConvShape{m->n_in, m->n_out};
 }
 
 int check_map(const usc_kmap* m, int kind, int cin, int cout, const char* who) {
@@ -147,7 +191,6 @@ int check_map(const usc_kmap* m, int kind, int cin, int cout, const char* who) {
   USC_REQUIRE(kind != USC_CONV_SAME || m->n_in == m->n_out, "%s: a stride-1 map has n_in == n_out", who);
   return USC_OK;
 }
-
 
 // ---- element-wise steps of a step program ---------------------------------------------------------------------------
 // dst[r][0:ca] = a[r][:], dst[r][ca:ca+cb] = b[r][:]   (float4 lanes; ca, cb multiples of 4)
@@ -206,15 +249,327 @@ int flush_deferred(DeferredWgrads& q, void* ws, int64_t ws_bytes, usc_stream_t s
   if (q.n >= 2 && usc_spconv_wgrad_group_ok(q.n, q.cin, q.cout, m->K, m->pair_capacity)) {
     rc = usc_spconv_wgrad_group(q.n, q.a, q.b, q.dW, q.cin, q.cout, m->K, m->pair_in, m->pair_out, m->koff, m->pair_capacity, 1, s);
   } else {
-    const int64_t b = usc_spconv_wgrad_ws_bytes_rows(m->K, q.cin, q.cout, m->pair_capacity);
-    if (b > ws_bytes) { set_error("usc_program_run: workspace too small (weight gradient)"); rc = USC_ERR_ARG; }
-    for (int r = 0; r < q.n && !rc; ++r)
-      rc = usc_spconv_wgrad(q.a[r], q.cin, q.b[r], q.cout, m->K, m->pair_in, m->pair_out, m->koff, m->pair_capacity, q.dW[r], 1, ws, b, s);
+    // too few for the grouped grid: each its usual launch (only stride-1 table maps are deferred)
+    WgradJob j = wgrad_job(m, USC_CONV_SAME, conv_shape(m, USC_CONV_SAME), nullptr, nullptr, nullptr, q.cin, q.cout);
+    if (j.list_bytes > ws_bytes) { set_error("usc_program_run: workspace too small (weight gradient)"); rc = USC_ERR_ARG; }
+    for (int r = 0; r < q.n && !rc; ++r) {
+      j.x = q.a[r]; j.dy = q.b[r]; j.dW = q.dW[r];
+      rc = issue_wgrad(j, 1, ws, ws_bytes, s);
+    }
   }
   q.n = 0;
   q.map = nullptr;
   return rc;
 }
+
+// ---- the bf16 matrix-core precisions of a unit (spconv_bf16.hip): one plane for inference, 2 or 3 for training --------
+// the input gradient is the same product over the mirrored transpose: operand shape cout -> cin
+bool split_dgrad_ok(const usc_kmap* m, int cin, int cout, int planes) {
+  return usc_spconv_gather_gemm_split_ws_bytes(m->n_in, cout, cin, m->K, planes) >= 0;
+}
+// scratch of one split product: the operand's planes, the packed weight planes, the kernel's own
+int64_t split_gemm_ws(const usc_kmap* m, int64_t n_src, int c_src, int c_dst, int planes) {
+  const int64_t g = usc_spconv_gather_gemm_split_ws_bytes(m->n_out, c_src, c_dst, m->K, planes);
+  return align_up(n_src * c_src * planes * 2, 256) + align_up((int64_t)planes * m->K * c_src * c_dst * 2, 256) +
+         align_up(g > 0 ? g : 16, 256);
+}
+// dst[o] (+)= sum_k sum_{i+j<P} src_i[nbr[k][o]] W_j[k].  src is converted on every call, on the caller's stream; so is W
+// f32[K][cin][cout], unless the caller has it packed (Wp, one plane).  transposed: the product over the mirrored
+// transpose of W, src has cout channels and dst cin.  up: the transposed conv of a stride-2 map, where every fine row has
+// one parent: the child table read backwards is the gather table over the fine rows.
+// Scratch, in this order: the operand's planes, the packed weight planes, the kernel's own, the table.
+int planes_gemm(const usc_kmap* m, int P, const float* src, int64_t n_src, int c_src, const float* W,
+                const uint16_t* Wp, int c_dst, int64_t n_dst, int transposed, bool up, float* dst, int accumulate,
+                WsCursor cur, usc_stream_t s, const char* who) {
+  const int K = m->K;
+  const int64_t gb = P == 1 ? usc_spconv_gather_gemm_bf16_ws_bytes(n_dst, c_src, c_dst, K)
+                            : usc_spconv_gather_gemm_split_ws_bytes(n_dst, c_src, c_dst, K, P);
+  USC_REQUIRE(gb >= 0, "%s: shape not covered by the bf16 kernels (P=%d, K=%d, %d -> %d channels)", who, P, K, c_src, c_dst);
+  uint16_t* xs = (uint16_t*)cur.take(n_src * c_src * P * 2);
+  uint16_t* wp = Wp ? nullptr : (uint16_t*)cur.take((int64_t)P * K * c_src * c_dst * 2);
+  void* gws = gb > 0 ? cur.take(gb) : nullptr;
+  int32_t* table = up ? (int32_t*)cur.take((int64_t)K * n_dst * 4) : nullptr;
+  USC_REQUIRE(xs && (Wp || wp) && (gb == 0 || gws) && (!up || table), "%s: workspace too small %s", who,
+              P == 1 ? "(usc_unit_bf16_ws_bytes)" : "for the split precision (usc_unit_split_ws_bytes)");
+  int rc = P == 1 ? usc_cast_bf16(src, n_src * c_src, xs, s) : usc_split_bf16_rows(src, n_src, c_src, P, xs, s);
+  if (rc) return rc;
+  if (!Wp) {
+    rc = transposed ? usc_spconv_pack_w_split(W, K, c_dst, c_src, P, 1, wp, s)
+                    : usc_spconv_pack_w_split(W, K, c_src, c_dst, P, 0, wp, s);
+    if (rc) return rc;
+    Wp = wp;
+  }
+  const int32_t* nbr = m->nbr;
+  if (up) {
+    rc = spconv_up_table(m->nbr, K, m->n_out, n_dst, table, as_stream(s));
+    if (rc) return rc;
+    nbr = table;
+  }
+  return P == 1 ? usc_spconv_gather_gemm_bf16(xs, n_src, c_src, Wp, K, c_dst, nbr, n_dst, nullptr, dst, accumulate, gws, gb, s)
+                : usc_spconv_gather_gemm_split(xs, n_src, c_src, Wp, K, c_dst, P, nbr, n_dst, nullptr, dst, accumulate, gws, gb, s);
+}
+
+void conv_ws_parts(const usc_kmap* m, int kind, int cin, int cout, int64_t* fwd, int64_t* dgrad, int64_t* wg) {
+  const int K = m->K;
+  const ConvShape sh = conv_shape(m, kind);
+  const int64_t wbytes = align_up((int64_t)K * cin * cout * 4, 256);
+  *fwd = kind == USC_CONV_UP ? 0 : table_gemm_ws(m, sh.n_out, cin, cout, K, false);      // UP: pair-list form, no scratch
+  if (kind == USC_CONV_SAME) *dgrad = table_gemm_ws(m, sh.n_in, cout, cin, K, true);
+  else if (kind == USC_CONV_DOWN) *dgrad = wbytes;                                       // transposed weights for the pair-list form
+  else *dgrad = wbytes + table_gemm_ws(m, sh.n_in, cout, cin, K, false);
+  *dgrad = align_up(*dgrad + 256, 256);
+  const WgradJob j = wgrad_job(m, kind, sh, nullptr, nullptr, nullptr, cin, cout);       // whichever form it takes fits
+  *wg = align_up(j.nbr && j.table_bytes > j.list_bytes ? j.table_bytes : j.list_bytes, 256);
+}
+
+int conv_forward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
+                      const float* bias, float* y, void* ws, int64_t ws_bytes, usc_stream_t s, Slices* left) {
+  if (left) *left = Slices{};
+  int rc = check_map(m, kind, cin, cout, "usc_conv_forward");
+  if (rc) return rc;
+  const ConvShape sh = conv_shape(m, kind);
+  if (sh.n_out == 0) return USC_OK;
+  USC_REQUIRE(x && W && y, "usc_conv_forward: null pointer");
+  WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
+  if (kind == USC_CONV_UP) {
+    // every fine row has exactly one parent: out[fine] = in[coarse] W[k]
+    USC_REQUIRE(m->pair_in && m->pair_out && m->koff, "usc_conv_forward: transposed conv needs the pair lists");
+    USC_REQUIRE(!bias, "usc_conv_forward: bias is not supported on the pair-list form");
+    return usc_spconv_pairs_gemm(x, cin, W, m->K, cout, m->pair_out, m->pair_in, m->koff, sh.n_out, y, s);
+  }
+  return table_gemm(m, x, sh.n_in, cin, W, m->K, cout, sh.n_out, bias, y, 0, 0, cur, s, left);
+}
+
+// the input gradient of a convolution whose split-K slices are still to be summed: dx = (accumulate ? dx : 0) + sum of
+// the G slices; consumed by the batch norm backward of the unit whose output gradient dx is (tile form), or reduced by
+// flush_pending
+struct Pending { float* dx = nullptr; const float* partial = nullptr; int G = 0; int64_t n = 0; int c = 0; int accumulate = 0; };
+
+int flush_pending(Pending& p, usc_stream_t s) {
+  if (p.G <= 0) return USC_OK;
+  const int rc = usc_group_reduce(p.partial, p.G, p.n, p.c, nullptr, p.accumulate, p.dx, s);
+  p = Pending{};
+  return rc;
+}
+
+int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
+                       const float* dy, float* dx, int32_t dx_accumulate, float* dW, int32_t dW_accumulate, void* ws,
+                       int64_t ws_bytes, usc_stream_t s, Pending* out, int planes = 0) {
+  if (out) *out = Pending{};
+  int rc = check_map(m, kind, cin, cout, "usc_conv_backward");
+  if (rc) return rc;
+  const ConvShape sh = conv_shape(m, kind);
+  const int K = m->K;
+  USC_REQUIRE(x && W && dy, "usc_conv_backward: null pointer");
+  WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
+  WgradJob job = wgrad_job(m, kind, sh, x, dy, dW, cin, cout);
+  // lane: the weight gradient queued on the lane stream, joined by the caller at the end of the backward pass
+  if (dW && dW_accumulate && x && dy) {
+    Lane* lane = lane_for_current_device();
+    const bool lane_ok = lane && sh.n_in > 0 && sh.n_in <= lane->max_rows && sh.n_out <= lane->max_rows &&
+                         job.list_bytes <= lane->ws_bytes && (!m->nbr || (m->pair_in && m->pair_out && m->koff));
+    const int64_t big = sh.n_in > sh.n_out ? sh.n_in : sh.n_out;
+    // the chain has reached a map too small to fill the chip: what was held runs beside it from here on
+    if (lane && lane->hold && big <= lane->release_max_rows) { rc = lane_release(lane, s); if (rc) return rc; }
+    if (lane_ok && lane->hold && big >= lane->hold_min_rows) {
+      // an asymmetry kept as it was: what is held goes through the pair-list kernel when it is released, the stem too (the
+      // shipped schedule never holds the stem, but usc_wgrad_lane_hold is public)
+      job.nbr = nullptr;
+      lane->held.push_back(job);
+      dW = nullptr;          // noted; launched by lane_release
+    } else if (lane_ok &&
+        hipEventRecord(lane->fork, as_stream(s)) == hipSuccess && hipStreamWaitEvent(lane->st, lane->fork, 0) == hipSuccess) {
+      lane->dirty = true;
+      rc = issue_wgrad(job, 1, lane->ws, lane->ws_bytes, (usc_stream_t)lane->st);
+      if (rc) return rc;
+      dW = nullptr;          // done (queued); the rest of this call is the input gradient on the caller's stream
+    }
+  }
+  int64_t dgrad_bytes = 0;
+  // slices may stay behind only when the consumer can take them (tile-form batch norm on the input map) and nothing in
+  // this call overwrites them: the weight gradient then takes its scratch behind the input gradient's region
+  Slices left;
+  // split precision: the input gradient on the bf16 matrix cores where the transposed shape (cout -> cin) is covered
+  const bool split_dx = planes > 0 && kind == USC_CONV_SAME && split_dgrad_ok(m, cin, cout, planes);
+  const bool may_defer = !split_dx && out && dx && tile_rows_ok(sh.n_in, cin);
+  if (may_defer) {
+    int64_t f_, w_;
+    conv_ws_parts(m, kind, cin, cout, &f_, &dgrad_bytes, &w_);
+    if (dgrad_bytes + w_ > cur.bytes) dgrad_bytes = 0;
+  }
+  Slices* want = (may_defer && dgrad_bytes > 0) ? &left : nullptr;
+  if (dx && sh.n_in > 0) {
+    if (split_dx) {
+      rc = planes_gemm(m, planes, dy, sh.n_out, cout, W, nullptr, cin, sh.n_in, 1, false, dx, dx_accumulate, cur, s,
+                       "usc_conv_backward");
+    } else if (kind == USC_CONV_SAME) {
+      // stride-1 map: the mirrored offset reaches the rows that read row i; transpose folded where the kernel can
+      rc = table_gemm(m, dy, sh.n_out, cout, W, K, cin, sh.n_in, nullptr, dx, dx_accumulate, 1, cur, s, want);
+    } else {
+      const bool down = kind == USC_CONV_DOWN;
+      USC_REQUIRE(!down || !dx_accumulate, "usc_conv_backward: accumulate is not supported on the pair-list form");
+      USC_REQUIRE(!down || (m->pair_in && m->pair_out && m->koff), "usc_conv_backward: strided conv needs the pair lists");
+      float* Wt = (float*)cur.take((int64_t)K * cin * cout * 4);
+      USC_REQUIRE(Wt, "usc_conv_backward: workspace too small");
+      rc = usc_weight_transpose(W, K, cin, cout, 0, Wt, s);
+      // DOWN: the pair lists read backwards.  UP: dx[coarse] = sum_k dy[child k of coarse] W[k]^T, the child table again
+      if (!rc) rc = down ? usc_spconv_pairs_gemm(dy, cout, Wt, K, cin, m->pair_out, m->pair_in, m->koff, sh.n_in, dx, s)
+                         : table_gemm(m, dy, sh.n_out, cout, Wt, K, cin, sh.n_in, nullptr, dx, dx_accumulate, 0, cur, s, want);
+    }
+    if (!rc && left.G > 0) {
+      out->dx = dx; out->partial = left.partial; out->G = left.G; out->n = sh.n_in; out->c = cin; out->accumulate = dx_accumulate;
+    }
+    if (rc) dW = nullptr;   // skip the weight gradient
+  }
+  if (dW) {
+    // the weight gradient reuses the scratch from the start (stream order), or takes it behind the slices left above
+    WsCursor wc{(char*)ws, ws ? ws_bytes : 0, left.G > 0 ? dgrad_bytes : 0};
+    void* w = wc.take(job.list_bytes);
+    if (!w) { set_error("usc_conv_backward: workspace too small (weight gradient)"); return USC_ERR_ARG; }
+    rc = issue_wgrad(job, dW_accumulate, w, (char*)ws + ws_bytes - (char*)w, s);
+  }
+  return rc;
+}
+
+// the batch norm's tile form (coarse levels) takes a forward unit's output when the statistics are the batch's
+bool bn_tile_form(const usc_bn* bn, int64_t n, int c, int64_t sb) {
+  return bn->training && tile_rows_ok(n, c) && sb >= usc_bn_tile_ws_bytes(c);
+}
+
+// the end of every forward unit: statistics of y (the batch's, or the running ones in eval mode), then scale and shift
+// (+ residual) (+ ReLU).  tile: the caller allows the tile form (bn_tile_form), which sums the split-K slices the
+// convolution left behind on its way (none: y is finished).
+int bn_act_tail(const char* who, const usc_bn* bn, bool tile, Slices left, float* y, int64_t n, int cout,
+                const float* residual, int relu, float* stats, float* out, void* sws, int64_t sb, usc_stream_t s) {
+  float* mean = stats, *invstd = stats + cout, *scale = stats + 2 * cout, *shift = stats + 3 * cout;
+  if (tile)
+    return usc_bn_tile_forward(left.partial, left.G, y, n, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean,
+                               bn->running_var, bn->num_batches_tracked, mean, invstd, scale, shift, residual, relu, out, sws,
+                               sb, s);
+  int rc;
+  if (bn->training) {
+    rc = usc_bn_forward_stats(y, n, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean, bn->running_var,
+                              bn->num_batches_tracked, mean, invstd, scale, shift, sws, sb, s);
+  } else {
+    USC_REQUIRE(bn->running_mean && bn->running_var, "%s: eval mode needs running statistics", who);
+    rc = usc_bn_eval_stats(bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->eps, cout, mean, invstd, scale,
+                           shift, s);
+  }
+  if (rc) return rc;
+  return usc_bn_apply(y, scale, shift, residual, relu, out, n, cout, s);
+}
+
+// The frame of a forward unit behind the three entry points: the shared checks, the cursor, the batch norm's partials
+// FIRST, the convolution, bn_act_tail.  The entry points differ in their error texts and in how y is produced:
+struct FwdForm {
+  const char* who;       // the entry point
+  const char* map_who;   // the name the map is checked under (the f32 unit reports usc_conv_forward's checks)
+  const char* ws_note;   // what follows "workspace too small"
+  int P;                 // 0: f32 (conv_forward_impl); 1: packed bf16 weights Wp (inference); 2, 3: split planes of W
+};
+int forward_unit(const FwdForm& f, const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W,
+                 const uint16_t* Wp, int32_t cout, const usc_bn* bn, const float* residual, int32_t relu, float* y,
+                 float* stats, float* out, void* ws, int64_t ws_bytes, usc_stream_t s) {
+  int rc = check_map(m, kind, cin, cout, f.map_who);
+  if (rc) return rc;
+  USC_REQUIRE(bn && bn->c == cout, "%s: batch-norm width must equal the conv's output width", f.who);
+  USC_REQUIRE(y && stats && out && bn->gamma && bn->beta, "%s: null pointer", f.who);
+  const ConvShape sh = conv_shape(m, kind);
+  if (f.P) {
+    const int64_t gb = f.P == 1 ? usc_spconv_gather_gemm_bf16_ws_bytes(sh.n_out, cin, cout, m->K)
+                                : usc_spconv_gather_gemm_split_ws_bytes(sh.n_out, cin, cout, m->K, f.P);
+    USC_REQUIRE(gb >= 0, "%s: shape not covered (K=%d, %d -> %d channels)", f.who, m->K, cin, cout);
+  }
+  if (sh.n_out == 0) return USC_OK;
+  if (f.P) {
+    USC_REQUIRE(x && (f.P == 1 ? (const void*)Wp : (const void*)W), "%s: null pointer", f.who);
+    USC_REQUIRE(m->nbr || kind == USC_CONV_SAME, "%s: strided maps need the child table", f.who);
+  }
+  WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
+  const int64_t sb = usc_colstats_ws_bytes(sh.n_out, cout);
+  void* sws = cur.take(sb);                       // BN partials first: the conv's scratch takes the rest
+  USC_REQUIRE(sws, "%s: workspace too small%s", f.who, f.ws_note);
+  // tile form (coarse levels, not in inference): the f32 convolution leaves its split-K slices behind, two launches do
+  // the rest; after the split precision it finds y finished (no slices)
+  const bool tile = f.P != 1 && bn_tile_form(bn, sh.n_out, cout, sb);
+  Slices left;
+  if (f.P == 0) rc = conv_forward_impl(m, kind, x, cin, W, cout, nullptr, y, cur.rest(), cur.left(), s, tile ? &left : nullptr);
+  else rc = planes_gemm(m, f.P, x, sh.n_in, cin, W, Wp, cout, sh.n_out, 0, kind == USC_CONV_UP, y, 0, cur, s, f.who);
+  if (rc) return rc;
+  return bn_act_tail(f.who, bn, tile, left, y, sh.n_out, cout, residual, relu, stats, out, sws, sb, s);
+}
+
+// in: slices of THIS unit's output gradient (in->dx == dout) left by the previous step, or NULL / empty;
+// out: receives the slices of this unit's input gradient when they may stay un-reduced (else left empty)
+int unit_backward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
+                       const usc_bn* bn, const float* y, const float* stats, const float* out_relu,
+                       const float* dout, float* dy, float* dres, float* dx, int32_t dx_accumulate, float* dW,
+                       int32_t dW_accumulate, float* dgamma, float* dbeta, int32_t dbn_accumulate, void* ws,
+                       int64_t ws_bytes, usc_stream_t s, Pending* in, Pending* out, int planes = 0) {
+  if (out) *out = Pending{};
+  USC_REQUIRE(bn && bn->c == cout, "usc_conv_bn_act_backward: batch-norm width must equal the conv's output width");
+  USC_REQUIRE(y && stats && dout && dy && dgamma && dbeta && bn->gamma, "usc_conv_bn_act_backward: null pointer");
+  const ConvShape sh = conv_shape(m, kind);
+  if (sh.n_out == 0) return USC_OK;
+  // split precision: the planes and packs are taken behind the batch norm backward; a short scratch is refused here,
+  // before anything is launched (dy, dgamma, dbeta untouched)
+  if (planes > 0)
+    USC_REQUIRE(ws && ws_bytes >= usc_unit_split_ws_bytes(m, kind, cin, cout, planes),
+                "usc_conv_bn_act_backward_split: workspace too small (usc_unit_split_ws_bytes)");
+  WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
+  const int64_t sb = usc_colstats_ws_bytes(sh.n_out, cout);
+  void* sws = cur.take(sb);
+  float* red = (float*)cur.take(2 * (int64_t)cout * 4);   // mean_g | mean_gxhat
+  USC_REQUIRE(sws && red, "usc_conv_bn_act_backward: workspace too small");
+  const float* mean = stats, *invstd = stats + cout;
+  int rc;
+  const bool has_in = in && in->G > 0;
+  if (has_in) USC_REQUIRE(in->dx == dout && in->n == sh.n_out && in->c == cout, "usc unit: pending slices do not belong to this unit");
+  if (tile_rows_ok(sh.n_out, cout) && sb >= usc_bn_tile_ws_bytes(cout)) {
+    rc = usc_bn_tile_backward(has_in ? in->partial : nullptr, has_in ? in->G : 0, has_in ? in->accumulate : 0, (float*)dout, y,
+                              out_relu, mean, invstd, bn->gamma, sh.n_out, cout, bn->training, dbn_accumulate, dgamma,
+                              dbeta, dy, dres, sws, sb, s);
+    if (has_in) *in = Pending{};
+    if (rc) return rc;
+  } else {
+    if (has_in) { rc = flush_pending(*in, s); if (rc) return rc; }
+    rc = usc_bn_backward_reduce(y, dout, out_relu, mean, invstd, sh.n_out, cout, bn->training, dbn_accumulate, dgamma,
+                                dbeta, red, red + cout, sws, sb, s);
+    if (rc) return rc;
+    rc = usc_bn_backward_dx(y, dout, out_relu, mean, invstd, bn->gamma, red, red + cout, dy, dres, sh.n_out, cout, s);
+    if (rc) return rc;
+  }
+  return conv_backward_impl(m, kind, x, cin, W, cout, dy, dx, dx_accumulate, dW, dW_accumulate, cur.rest(), cur.left(), s, out,
+                            planes);
+}
+
+int check_split(const usc_kmap* m, int32_t kind, int32_t P, const char* who) {
+  USC_REQUIRE(m, "%s: null kernel map", who);
+  USC_REQUIRE(P == 2 || P == 3, "%s: P must be 2 or 3 (got %d)", who, P);
+  USC_REQUIRE(kind == USC_CONV_SAME, "%s: the split precision covers stride-1 units only", who);
+  return USC_OK;
+}
+
+int64_t program_half_bytes(const usc_step* steps, int32_t n_steps) {
+  int64_t need = 256;
+  if (!steps) return need;
+  for (int i = 0; i < n_steps; ++i) {
+    const usc_step& t = steps[i];
+    if ((t.op == USC_STEP_UNIT_FWD || t.op == USC_STEP_UNIT_BWD) && t.map) {
+      int64_t b = usc_unit_ws_bytes(t.map, t.kind, t.cin, t.cout);
+      if (t.split_planes) {                        // (an uncovered shape is reported by the step itself)
+        const int64_t sb = usc_unit_split_ws_bytes(t.map, t.kind, t.cin, t.cout, t.split_planes);
+        if (sb > b) b = sb;
+      }
+      if (b > need) need = b;
+    } else if (t.op == USC_STEP_UNIT_FWD_BF16 && t.map) {
+      const int64_t b = usc_unit_bf16_ws_bytes(t.map, t.kind, t.cin, t.cout);
+      if (b > need) need = b;
+    }
+  }
+  return align_up(need, 256);
+}
+
 }  // namespace
 
 extern "C" {
@@ -284,76 +639,6 @@ int usc_wgrad_lane_join(usc_stream_t s) {
   return USC_OK;
 }
 
-// ---- the bf16 matrix-core precisions of a unit (spconv_bf16.hip): one plane for inference, 2 or 3 for training --------
-// the input gradient is the same product over the mirrored transpose: operand shape cout -> cin
-static bool split_dgrad_ok(const usc_kmap* m, int cin, int cout, int planes) {
-  return usc_spconv_gather_gemm_split_ws_bytes(m->n_in, cout, cin, m->K, planes) >= 0;
-}
-// scratch of one split product: the operand's planes, the packed weight planes, the kernel's own
-static int64_t split_gemm_ws(const usc_kmap* m, int64_t n_src, int c_src, int c_dst, int planes) {
-  const int64_t g = usc_spconv_gather_gemm_split_ws_bytes(m->n_out, c_src, c_dst, m->K, planes);
-  return align_up(n_src * c_src * planes * 2, 256) + align_up((int64_t)planes * m->K * c_src * c_dst * 2, 256) +
-         align_up(g > 0 ? g : 16, 256);
-}
-// dst[o] (+)= sum_k sum_{i+j<P} src_i[nbr[k][o]] W_j[k].  src is converted on every call, on the caller's stream; so is W
-// f32[K][cin][cout], unless the caller has it packed (Wp, one plane).  transposed: the product over the mirrored
-// transpose of W, src has cout channels and dst cin.  up: the transposed conv of a stride-2 map, where every fine row has
-// one parent: the child table read backwards is the gather table over the fine rows.
-// Scratch, in this order: the operand's planes, the packed weight planes, the kernel's own, the table.
-static int planes_gemm(const usc_kmap* m, int P, const float* src, int64_t n_src, int c_src, const float* W,
-                       const uint16_t* Wp, int c_dst, int64_t n_dst, int transposed, bool up, float* dst, int accumulate,
-                       WsCursor cur, usc_stream_t s, const char* who) {
-  const int K = m->K;
-  const int64_t gb = P == 1 ? usc_spconv_gather_gemm_bf16_ws_bytes(n_dst, c_src, c_dst, K)
-                            : usc_spconv_gather_gemm_split_ws_bytes(n_dst, c_src, c_dst, K, P);
-  USC_REQUIRE(gb >= 0, "%s: shape not covered by the bf16 kernels (P=%d, K=%d, %d -> %d channels)", who, P, K, c_src, c_dst);
-  uint16_t* xs = (uint16_t*)cur.take(n_src * c_src * P * 2);
-  uint16_t* wp = Wp ? nullptr : (uint16_t*)cur.take((int64_t)P * K * c_src * c_dst * 2);
-  void* gws = gb > 0 ? cur.take(gb) : nullptr;
-  int32_t* table = up ? (int32_t*)cur.take((int64_t)K * n_dst * 4) : nullptr;
-  USC_REQUIRE(xs && (Wp || wp) && (gb == 0 || gws) && (!up || table), "%s: workspace too small %s", who,
-              P == 1 ? "(usc_unit_bf16_ws_bytes)" : "for the split precision (usc_unit_split_ws_bytes)");
-  int rc = P == 1 ? usc_cast_bf16(src, n_src * c_src, xs, s) : usc_split_bf16_rows(src, n_src, c_src, P, xs, s);
-  if (rc) return rc;
-  if (!Wp) {
-    rc = transposed ? usc_spconv_pack_w_split(W, K, c_dst, c_src, P, 1, wp, s)
-                    : usc_spconv_pack_w_split(W, K, c_src, c_dst, P, 0, wp, s);
-    if (rc) return rc;
-    Wp = wp;
-  }
-  const int32_t* nbr = m->nbr;
-  if (up) {
-    rc = spconv_up_table(m->nbr, K, m->n_out, n_dst, table, as_stream(s));
-    if (rc) return rc;
-    nbr = table;
-  }
-  return P == 1 ? usc_spconv_gather_gemm_bf16(xs, n_src, c_src, Wp, K, c_dst, nbr, n_dst, nullptr, dst, accumulate, gws, gb, s)
-                : usc_spconv_gather_gemm_split(xs, n_src, c_src, Wp, K, c_dst, P, nbr, n_dst, nullptr, dst, accumulate, gws, gb, s);
-}
-
-static void conv_ws_parts(const usc_kmap* m, int kind, int cin, int cout, int64_t* fwd, int64_t* dgrad, int64_t* wg) {
-  const int K = m->K;
-  const ConvShape sh = conv_shape(m, kind);
-  const int64_t wbytes = align_up((int64_t)K * cin * cout * 4, 256);
-  if (kind == USC_CONV_SAME) {
-    *fwd = table_gemm_ws(m, sh.n_out, cin, cout, K, false);
-    *dgrad = table_gemm_ws(m, sh.n_in, cout, cin, K, true);
-  } else if (kind == USC_CONV_DOWN) {
-    *fwd = table_gemm_ws(m, sh.n_out, cin, cout, K, false);
-    *dgrad = wbytes;                                            // transposed weights for the pair-list form
-  } else {
-    *fwd = 0;                                                   // pair-list form, no scratch
-    *dgrad = wbytes + table_gemm_ws(m, sh.n_in, cout, cin, K, false);
-  }
-  *dgrad = align_up(*dgrad + 256, 256);
-  const int64_t rows = m->nbr ? m->pair_capacity : sh.n_in;
-  *wg = align_up(usc_spconv_wgrad_ws_bytes_rows(K, cin, cout, rows), 256);
-  if (kind == USC_CONV_SAME && m->nbr && cin <= 4 && cout == 32) {      // the stem: table-form weight gradient
-    const int64_t t = align_up(usc_spconv_wgrad_table_ws_bytes(K, cin, cout), 256);
-    if (t > *wg) *wg = t;
-  }
-}
-
 int64_t usc_conv_ws_bytes(const usc_kmap* m, int32_t kind, int32_t cin, int32_t cout) {
   if (!m) return 0;
   int64_t fwd, dgrad, wg;
@@ -362,47 +647,10 @@ int64_t usc_conv_ws_bytes(const usc_kmap* m, int32_t kind, int32_t cin, int32_t 
   return (fwd > bwd ? fwd : bwd) + 256;
 }
 
-static int conv_forward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
-                             const float* bias, float* y, void* ws, int64_t ws_bytes, usc_stream_t s, Slices* left);
-
 int usc_conv_forward(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
                      const float* bias, float* y, void* ws, int64_t ws_bytes, usc_stream_t s) {
   return conv_forward_impl(m, kind, x, cin, W, cout, bias, y, ws, ws_bytes, s, nullptr);
 }
-
-static int conv_forward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
-                             const float* bias, float* y, void* ws, int64_t ws_bytes, usc_stream_t s, Slices* left) {
-  if (left) *left = Slices{};
-  int rc = check_map(m, kind, cin, cout, "usc_conv_forward");
-  if (rc) return rc;
-  const ConvShape sh = conv_shape(m, kind);
-  if (sh.n_out == 0) return USC_OK;
-  USC_REQUIRE(x && W && y, "usc_conv_forward: null pointer");
-  WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
-  if (kind == USC_CONV_UP) {
-    // every fine row has exactly one parent: out[fine] = in[coarse] W[k]
-    USC_REQUIRE(m->pair_in && m->pair_out && m->koff, "usc_conv_forward: transposed conv needs the pair lists");
-    USC_REQUIRE(!bias, "usc_conv_forward: bias is not supported on the pair-list form");
-    return usc_spconv_pairs_gemm(x, cin, W, m->K, cout, m->pair_out, m->pair_in, m->koff, sh.n_out, y, s);
-  }
-  return table_gemm(m, m->nbr, x, sh.n_in, cin, W, m->K, cout, sh.n_out, bias, y, 0, 0, cur, s, left);
-}
-
-// the input gradient of a convolution whose split-K slices are still to be summed: dx = (accumulate ? dx : 0) + sum of
-// the G slices; consumed by the batch norm backward of the unit whose output gradient dx is (tile form), or reduced by
-// flush_pending
-struct Pending { float* dx = nullptr; const float* partial = nullptr; int G = 0; int64_t n = 0; int c = 0; int accumulate = 0; };
-
-static int flush_pending(Pending& p, usc_stream_t s) {
-  if (p.G <= 0) return USC_OK;
-  const int rc = usc_group_reduce(p.partial, p.G, p.n, p.c, nullptr, p.accumulate, p.dx, s);
-  p = Pending{};
-  return rc;
-}
-
-static int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
-                              const float* dy, float* dx, int32_t dx_accumulate, float* dW, int32_t dW_accumulate, void* ws,
-                              int64_t ws_bytes, usc_stream_t s, Pending* out, int planes = 0);
 
 int usc_conv_backward(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
                       const float* dy, float* dx, int32_t dx_accumulate, float* dW, int32_t dW_accumulate, void* ws,
@@ -410,167 +658,17 @@ int usc_conv_backward(const usc_kmap* m, int32_t kind, const float* x, int32_t c
   return conv_backward_impl(m, kind, x, cin, W, cout, dy, dx, dx_accumulate, dW, dW_accumulate, ws, ws_bytes, s, nullptr);
 }
 
-static int conv_backward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
-                              const float* dy, float* dx, int32_t dx_accumulate, float* dW, int32_t dW_accumulate, void* ws,
-                              int64_t ws_bytes, usc_stream_t s, Pending* out, int planes) {
-  if (out) *out = Pending{};
-  int rc = check_map(m, kind, cin, cout, "usc_conv_backward");
-  if (rc) return rc;
-  const ConvShape sh = conv_shape(m, kind);
-  const int K = m->K;
-  USC_REQUIRE(x && W && dy, "usc_conv_backward: null pointer");
-  WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
-  // lane: the weight gradient queued on the lane stream, joined by the caller at the end of the backward pass
-  if (dW && dW_accumulate && x && dy) {
-    Lane* lane = lane_for_current_device();
-    const int64_t rows = m->nbr ? m->pair_capacity : sh.n_in;
-    const int64_t b = usc_spconv_wgrad_ws_bytes_rows(K, cin, cout, rows);
-    const bool lane_ok = lane && sh.n_in > 0 && sh.n_in <= lane->max_rows && sh.n_out <= lane->max_rows &&
-                         b <= lane->ws_bytes && (!m->nbr || (m->pair_in && m->pair_out && m->koff));
-    const int64_t big = sh.n_in > sh.n_out ? sh.n_in : sh.n_out;
-    // the chain has reached a map too small to fill the chip: what was held runs beside it from here on
-    if (lane && lane->hold && big <= lane->release_max_rows) { rc = lane_release(lane, s); if (rc) return rc; }
-    if (lane_ok && lane->hold && big >= lane->hold_min_rows) {
-      HeldWgrad h{x, dy, dW, nullptr, nullptr, nullptr, m->nbr ? rows : sh.n_in, b, cin, cout, m->nbr ? K : 1};
-      if (m->nbr) {
-        h.a_idx = kind == USC_CONV_UP ? m->pair_out : m->pair_in;
-        h.b_idx = kind == USC_CONV_UP ? m->pair_in : m->pair_out;
-        h.koff = m->koff;
-      }
-      lane->held.push_back(h);
-      dW = nullptr;          // noted; launched by lane_release
-    } else if (lane_ok &&
-        hipEventRecord(lane->fork, as_stream(s)) == hipSuccess && hipStreamWaitEvent(lane->st, lane->fork, 0) == hipSuccess) {
-      usc_stream_t ls = (usc_stream_t)lane->st;
-      lane->dirty = true;
-      // the stem (3 -> 32 channels) keeps its table-form kernel on the lane too: it is the LAST weight gradient of the
-      // backward pass — the lane's tail, which the step waits for — and the pair-list kernel needs 110 us for it, the table
-      // form 57 (round 6: the lane branch used to send everything through usc_spconv_wgrad)
-      const int64_t bt = usc_spconv_wgrad_table_ws_bytes(K, cin, cout);
-      if (kind == USC_CONV_SAME && m->nbr && cin <= 4 && cout == 32 && K <= 32 && bt <= lane->ws_bytes)
-        rc = usc_spconv_wgrad_table(x, cin, dy, cout, m->nbr, K, sh.n_out, dW, 1, lane->ws, bt, ls);
-      else if (!m->nbr)
-        rc = usc_spconv_wgrad(x, cin, dy, cout, 1, nullptr, nullptr, nullptr, sh.n_in, dW, 1, lane->ws, b, ls);
-      else if (kind == USC_CONV_UP)
-        rc = usc_spconv_wgrad(x, cin, dy, cout, K, m->pair_out, m->pair_in, m->koff, rows, dW, 1, lane->ws, b, ls);
-      else
-        rc = usc_spconv_wgrad(x, cin, dy, cout, K, m->pair_in, m->pair_out, m->koff, rows, dW, 1, lane->ws, b, ls);
-      if (rc) return rc;
-      dW = nullptr;          // done (queued); the rest of this call is the input gradient on the caller's stream
-    }
-  }
-  int64_t dgrad_bytes = 0;
-  // slices may stay behind only when the consumer can take them (tile-form batch norm on the input map) and nothing in
-  // this call overwrites them: the weight gradient then takes its scratch behind the input gradient's region
-  Slices left;
-  // split precision: the input gradient on the bf16 matrix cores where the transposed shape (cout -> cin) is covered
-  const bool split_dx = planes > 0 && kind == USC_CONV_SAME && split_dgrad_ok(m, cin, cout, planes);
-  const bool may_defer = !split_dx && out && dx && tile_rows_ok(sh.n_in, cin);
-  if (may_defer) {
-    int64_t f_, w_;
-    conv_ws_parts(m, kind, cin, cout, &f_, &dgrad_bytes, &w_);
-    if (dgrad_bytes + w_ > cur.bytes) dgrad_bytes = 0;
-  }
-  Slices* want = (may_defer && dgrad_bytes > 0) ? &left : nullptr;
-  if (dx && sh.n_in > 0) {
-    if (split_dx) {
-      rc = planes_gemm(m, planes, dy, sh.n_out, cout, W, nullptr, cin, sh.n_in, 1, false, dx, dx_accumulate, cur, s,
-                       "usc_conv_backward");
-    } else if (kind == USC_CONV_SAME) {
-      // stride-1 map: the mirrored offset reaches the rows that read row i; transpose folded where the kernel can
-      rc = table_gemm(m, m->nbr, dy, sh.n_out, cout, W, K, cin, sh.n_in, nullptr, dx, dx_accumulate, 1, cur, s, want);
-    } else if (kind == USC_CONV_DOWN) {
-      USC_REQUIRE(!dx_accumulate, "usc_conv_backward: accumulate is not supported on the pair-list form");
-      USC_REQUIRE(m->pair_in && m->pair_out && m->koff, "usc_conv_backward: strided conv needs the pair lists");
-      float* Wt = (float*)cur.take((int64_t)K * cin * cout * 4);
-      USC_REQUIRE(Wt, "usc_conv_backward: workspace too small");
-      rc = usc_weight_transpose(W, K, cin, cout, 0, Wt, s);
-      if (!rc) rc = usc_spconv_pairs_gemm(dy, cout, Wt, K, cin, m->pair_out, m->pair_in, m->koff, sh.n_in, dx, s);
-    } else {
-      float* Wt = (float*)cur.take((int64_t)K * cin * cout * 4);
-      USC_REQUIRE(Wt, "usc_conv_backward: workspace too small");
-      rc = usc_weight_transpose(W, K, cin, cout, 0, Wt, s);
-      // dx[coarse] = sum_k dy[child k of coarse] W[k]^T: the child table again, gather form
-      if (!rc) rc = table_gemm(m, m->nbr, dy, sh.n_out, cout, Wt, K, cin, sh.n_in, nullptr, dx, dx_accumulate, 0, cur, s, want);
-    }
-    if (!rc && left.G > 0) {
-      out->dx = dx; out->partial = left.partial; out->G = left.G; out->n = sh.n_in; out->c = cin; out->accumulate = dx_accumulate;
-    }
-    if (rc) dW = nullptr;   // skip the weight gradient
-  }
-  if (dW) {
-    // the weight gradient reuses the scratch from the start (stream order), or takes it behind the slices left above
-    WsCursor wc{(char*)ws, ws ? ws_bytes : 0, left.G > 0 ? dgrad_bytes : 0};
-    const int64_t rows = m->nbr ? m->pair_capacity : sh.n_in;
-    const int64_t b = usc_spconv_wgrad_ws_bytes_rows(K, cin, cout, rows);
-    void* w = wc.take(b);
-    if (!w) set_error("usc_conv_backward: workspace too small (weight gradient)");
-    const int64_t bt = usc_spconv_wgrad_table_ws_bytes(K, cin, cout);
-    if (!w) rc = USC_ERR_ARG;
-    else if (kind == USC_CONV_SAME && m->nbr && cin <= 4 && cout == 32 && K <= 32 && (char*)w + bt <= (char*)ws + ws_bytes)
-      rc = usc_spconv_wgrad_table(x, cin, dy, cout, m->nbr, K, sh.n_out, dW, dW_accumulate, w, bt, s);
-    else if (!m->nbr)
-      rc = usc_spconv_wgrad(x, cin, dy, cout, 1, nullptr, nullptr, nullptr, sh.n_in, dW, dW_accumulate, w, b, s);
-    else if (kind == USC_CONV_UP)
-      rc = usc_spconv_wgrad(x, cin, dy, cout, K, m->pair_out, m->pair_in, m->koff, rows, dW, dW_accumulate, w, b, s);
-    else
-      rc = usc_spconv_wgrad(x, cin, dy, cout, K, m->pair_in, m->pair_out, m->koff, rows, dW, dW_accumulate, w, b, s);
-  }
-  return rc;
-}
-
 int64_t usc_unit_ws_bytes(const usc_kmap* m, int32_t kind, int32_t cin, int32_t cout) {
   return usc_conv_ws_bytes(m, kind, cin, cout) + align_up(usc_colstats_ws_bytes(0, cout), 256) +
          align_up(2 * (int64_t)cout * 4, 256) + 256;
 }
 
-// the batch norm's tile form (coarse levels) takes a forward unit's output when the statistics are the batch's
-static bool bn_tile_form(const usc_bn* bn, int64_t n, int c, int64_t sb) {
-  return bn->training && tile_rows_ok(n, c) && sb >= usc_bn_tile_ws_bytes(c);
-}
-
-// the end of every forward unit: statistics of y (the batch's, or the running ones in eval mode), then scale and shift
-// (+ residual) (+ ReLU).  tile: the caller allows the tile form (bn_tile_form), which sums the split-K slices the
-// convolution left behind on its way (none: y is finished).
-static int bn_act_tail(const char* who, const usc_bn* bn, bool tile, Slices left, float* y, int64_t n, int cout,
-                       const float* residual, int relu, float* stats, float* out, void* sws, int64_t sb, usc_stream_t s) {
-  float* mean = stats, *invstd = stats + cout, *scale = stats + 2 * cout, *shift = stats + 3 * cout;
-  if (tile)
-    return usc_bn_tile_forward(left.partial, left.G, y, n, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean,
-                               bn->running_var, bn->num_batches_tracked, mean, invstd, scale, shift, residual, relu, out, sws,
-                               sb, s);
-  int rc;
-  if (bn->training) {
-    rc = usc_bn_forward_stats(y, n, cout, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean, bn->running_var,
-                              bn->num_batches_tracked, mean, invstd, scale, shift, sws, sb, s);
-  } else {
-    USC_REQUIRE(bn->running_mean && bn->running_var, "%s: eval mode needs running statistics", who);
-    rc = usc_bn_eval_stats(bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->eps, cout, mean, invstd, scale,
-                           shift, s);
-  }
-  if (rc) return rc;
-  return usc_bn_apply(y, scale, shift, residual, relu, out, n, cout, s);
-}
-
 int usc_conv_bn_act_forward(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
                             const usc_bn* bn, const float* residual, int32_t relu, float* y, float* stats, float* out,
                             void* ws, int64_t ws_bytes, usc_stream_t s) {
-  USC_REQUIRE(bn && bn->c == cout, "usc_conv_bn_act_forward: batch-norm width must equal the conv's output width");
-  USC_REQUIRE(y && stats && out && bn->gamma && bn->beta, "usc_conv_bn_act_forward: null pointer");
-  const ConvShape sh = conv_shape(m, kind);
-  WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
-  const int64_t sb = usc_colstats_ws_bytes(sh.n_out, cout);
-  void* sws = cur.take(sb);                       // BN partials first: the conv's scratch takes the rest
-  USC_REQUIRE(sws, "usc_conv_bn_act_forward: workspace too small");
-  // tile form (coarse levels): the convolution leaves its split-K slices behind, two launches do the rest
-  const bool tile = bn_tile_form(bn, sh.n_out, cout, sb);
-  Slices left;
-  int rc = conv_forward_impl(m, kind, x, cin, W, cout, nullptr, y, cur.rest(), cur.left(), s, tile ? &left : nullptr);
-  if (rc) return rc;
-  if (sh.n_out == 0) return USC_OK;
-  return bn_act_tail("usc_conv_bn_act_forward", bn, tile, left, y, sh.n_out, cout, residual, relu, stats, out, sws, sb, s);
+  return forward_unit({"usc_conv_bn_act_forward", "usc_conv_forward", "", 0}, m, kind, x, cin, W, nullptr, cout, bn, residual,
+                      relu, y, stats, out, ws, ws_bytes, s);
 }
-
 
 int64_t usc_unit_bf16_ws_bytes(const usc_kmap* m, int32_t kind, int32_t cin, int32_t cout) {
   if (!m) return 0;
@@ -585,33 +683,10 @@ int64_t usc_unit_bf16_ws_bytes(const usc_kmap* m, int32_t kind, int32_t cin, int
 int usc_conv_bn_act_forward_bf16(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const uint16_t* Wp,
                                  int32_t cout, const usc_bn* bn, const float* residual, int32_t relu, float* y,
                                  float* stats, float* out, void* ws, int64_t ws_bytes, usc_stream_t s) {
-  int rc = check_map(m, kind, cin, cout, "usc_conv_bn_act_forward_bf16");
-  if (rc) return rc;
-  USC_REQUIRE(bn && bn->c == cout, "usc_conv_bn_act_forward_bf16: batch-norm width must equal the conv's output width");
-  USC_REQUIRE(y && stats && out && bn->gamma && bn->beta, "usc_conv_bn_act_forward_bf16: null pointer");
-  const ConvShape sh = conv_shape(m, kind);
-  const int64_t gb = usc_spconv_gather_gemm_bf16_ws_bytes(sh.n_out, cin, cout, m->K);
-  USC_REQUIRE(gb >= 0, "usc_conv_bn_act_forward_bf16: shape not covered (K=%d, %d -> %d channels)", m->K, cin, cout);
-  if (sh.n_out == 0) return USC_OK;
-  USC_REQUIRE(x && Wp, "usc_conv_bn_act_forward_bf16: null pointer");
-  USC_REQUIRE(m->nbr || kind == USC_CONV_SAME, "usc_conv_bn_act_forward_bf16: strided maps need the child table");
-  WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
-  const int64_t sb = usc_colstats_ws_bytes(sh.n_out, cout);
-  void* sws = cur.take(sb);
-  USC_REQUIRE(sws, "usc_conv_bn_act_forward_bf16: workspace too small (usc_unit_bf16_ws_bytes)");
-  rc = planes_gemm(m, 1, x, sh.n_in, cin, nullptr, Wp, cout, sh.n_out, 0, kind == USC_CONV_UP, y, 0, cur, s,
-                   "usc_conv_bn_act_forward_bf16");
-  if (rc) return rc;
-  // (inference: the tile form is not taken)
-  return bn_act_tail("usc_conv_bn_act_forward_bf16", bn, false, Slices{}, y, sh.n_out, cout, residual, relu, stats, out, sws,
-                     sb, s);
+  const char* who = "usc_conv_bn_act_forward_bf16";
+  return forward_unit({who, who, " (usc_unit_bf16_ws_bytes)", 1}, m, kind, x, cin, nullptr, Wp, cout, bn, residual, relu, y,
+                      stats, out, ws, ws_bytes, s);
 }
-
-static int unit_backward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
-                              const usc_bn* bn, const float* y, const float* stats, const float* out_relu,
-                              const float* dout, float* dy, float* dres, float* dx, int32_t dx_accumulate, float* dW,
-                              int32_t dW_accumulate, float* dgamma, float* dbeta, int32_t dbn_accumulate, void* ws,
-                              int64_t ws_bytes, usc_stream_t s, Pending* in, Pending* out, int planes = 0);
 
 int usc_conv_bn_act_backward(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
                              const usc_bn* bn, const float* y, const float* stats, const float* out_relu,
@@ -620,57 +695,6 @@ int usc_conv_bn_act_backward(const usc_kmap* m, int32_t kind, const float* x, in
                              int64_t ws_bytes, usc_stream_t s) {
   return unit_backward_impl(m, kind, x, cin, W, cout, bn, y, stats, out_relu, dout, dy, dres, dx, dx_accumulate, dW,
                             dW_accumulate, dgamma, dbeta, dbn_accumulate, ws, ws_bytes, s, nullptr, nullptr);
-}
-
-// in: slices of THIS unit's output gradient (in->dx == dout) left by the previous step, or NULL / empty;
-// out: receives the slices of this unit's input gradient when they may stay un-reduced (else left empty)
-static int unit_backward_impl(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
-                              const usc_bn* bn, const float* y, const float* stats, const float* out_relu,
-                              const float* dout, float* dy, float* dres, float* dx, int32_t dx_accumulate, float* dW,
-                              int32_t dW_accumulate, float* dgamma, float* dbeta, int32_t dbn_accumulate, void* ws,
-                              int64_t ws_bytes, usc_stream_t s, Pending* in, Pending* out, int planes) {
-  if (out) *out = Pending{};
-  USC_REQUIRE(bn && bn->c == cout, "usc_conv_bn_act_backward: batch-norm width must equal the conv's output width");
-  USC_REQUIRE(y && stats && dout && dy && dgamma && dbeta && bn->gamma, "usc_conv_bn_act_backward: null pointer");
-  const ConvShape sh = conv_shape(m, kind);
-  if (sh.n_out == 0) return USC_OK;
-  // split precision: the planes and packs are taken behind the batch norm backward; a short scratch is refused here,
-  // before anything is launched (dy, dgamma, dbeta untouched)
-  if (planes > 0)
-    USC_REQUIRE(ws && ws_bytes >= usc_unit_split_ws_bytes(m, kind, cin, cout, planes),
-                "usc_conv_bn_act_backward_split: workspace too small (usc_unit_split_ws_bytes)");
-  WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
-  const int64_t sb = usc_colstats_ws_bytes(sh.n_out, cout);
-  void* sws = cur.take(sb);
-  float* red = (float*)cur.take(2 * (int64_t)cout * 4);   // mean_g | mean_gxhat
-  USC_REQUIRE(sws && red, "usc_conv_bn_act_backward: workspace too small");
-  const float* mean = stats, *invstd = stats + cout;
-  int rc;
-  const bool has_in = in && in->G > 0;
-  if (has_in) USC_REQUIRE(in->dx == dout && in->n == sh.n_out && in->c == cout, "usc unit: pending slices do not belong to this unit");
-  if (tile_rows_ok(sh.n_out, cout) && sb >= usc_bn_tile_ws_bytes(cout)) {
-    rc = usc_bn_tile_backward(has_in ? in->partial : nullptr, has_in ? in->G : 0, has_in ? in->accumulate : 0, (float*)dout, y,
-                              out_relu, mean, invstd, bn->gamma, sh.n_out, cout, bn->training, dbn_accumulate, dgamma,
-                              dbeta, dy, dres, sws, sb, s);
-    if (has_in) *in = Pending{};
-    if (rc) return rc;
-  } else {
-    if (has_in) { rc = flush_pending(*in, s); if (rc) return rc; }
-    rc = usc_bn_backward_reduce(y, dout, out_relu, mean, invstd, sh.n_out, cout, bn->training, dbn_accumulate, dgamma,
-                                dbeta, red, red + cout, sws, sb, s);
-    if (rc) return rc;
-    rc = usc_bn_backward_dx(y, dout, out_relu, mean, invstd, bn->gamma, red, red + cout, dy, dres, sh.n_out, cout, s);
-    if (rc) return rc;
-  }
-  return conv_backward_impl(m, kind, x, cin, W, cout, dy, dx, dx_accumulate, dW, dW_accumulate, cur.rest(), cur.left(), s, out,
-                            planes);
-}
-
-static int check_split(const usc_kmap* m, int32_t kind, int32_t P, const char* who) {
-  USC_REQUIRE(m, "%s: null kernel map", who);
-  USC_REQUIRE(P == 2 || P == 3, "%s: P must be 2 or 3 (got %d)", who, P);
-  USC_REQUIRE(kind == USC_CONV_SAME, "%s: the split precision covers stride-1 units only", who);
-  return USC_OK;
 }
 
 int64_t usc_unit_split_ws_bytes(const usc_kmap* m, int32_t kind, int32_t cin, int32_t cout, int32_t P) {
@@ -687,26 +711,11 @@ int64_t usc_unit_split_ws_bytes(const usc_kmap* m, int32_t kind, int32_t cin, in
 int usc_conv_bn_act_forward_split(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
                                   int32_t P, const usc_bn* bn, const float* residual, int32_t relu, float* y, float* stats,
                                   float* out, void* ws, int64_t ws_bytes, usc_stream_t s) {
-  int rc = check_split(m, kind, P, "usc_conv_bn_act_forward_split");
+  const char* who = "usc_conv_bn_act_forward_split";
+  const int rc = check_split(m, kind, P, who);
   if (rc) return rc;
-  rc = check_map(m, kind, cin, cout, "usc_conv_bn_act_forward_split");
-  if (rc) return rc;
-  USC_REQUIRE(bn && bn->c == cout, "usc_conv_bn_act_forward_split: batch-norm width must equal the conv's output width");
-  USC_REQUIRE(y && stats && out && bn->gamma && bn->beta, "usc_conv_bn_act_forward_split: null pointer");
-  const ConvShape sh = conv_shape(m, kind);
-  USC_REQUIRE(usc_spconv_gather_gemm_split_ws_bytes(sh.n_out, cin, cout, m->K, P) >= 0,
-              "usc_conv_bn_act_forward_split: shape not covered (K=%d, %d -> %d channels)", m->K, cin, cout);
-  if (sh.n_out == 0) return USC_OK;
-  USC_REQUIRE(x && W, "usc_conv_bn_act_forward_split: null pointer");
-  WsCursor cur{(char*)ws, ws ? ws_bytes : 0, 0};
-  const int64_t sb = usc_colstats_ws_bytes(sh.n_out, cout);
-  void* sws = cur.take(sb);
-  USC_REQUIRE(sws, "usc_conv_bn_act_forward_split: workspace too small (usc_unit_split_ws_bytes)");
-  rc = planes_gemm(m, P, x, sh.n_in, cin, W, nullptr, cout, sh.n_out, 0, false, y, 0, cur, s, "usc_conv_bn_act_forward_split");
-  if (rc) return rc;
-  // the same forms as usc_conv_bn_act_forward; the tile form finds y finished (no slices)
-  return bn_act_tail("usc_conv_bn_act_forward_split", bn, bn_tile_form(bn, sh.n_out, cout, sb), Slices{}, y, sh.n_out, cout,
-                     residual, relu, stats, out, sws, sb, s);
+  return forward_unit({who, who, " (usc_unit_split_ws_bytes)", P}, m, kind, x, cin, W, nullptr, cout, bn, residual, relu, y,
+                      stats, out, ws, ws_bytes, s);
 }
 
 int usc_conv_bn_act_backward_split(const usc_kmap* m, int32_t kind, const float* x, int32_t cin, const float* W, int32_t cout,
@@ -721,26 +730,6 @@ int usc_conv_bn_act_backward_split(const usc_kmap* m, int32_t kind, const float*
 }
 
 int32_t usc_step_size(void) { return (int32_t)sizeof(usc_step); }
-
-static int64_t program_half_bytes(const usc_step* steps, int32_t n_steps) {
-  int64_t need = 256;
-  if (!steps) return need;
-  for (int i = 0; i < n_steps; ++i) {
-    const usc_step& t = steps[i];
-    if ((t.op == USC_STEP_UNIT_FWD || t.op == USC_STEP_UNIT_BWD) && t.map) {
-      int64_t b = usc_unit_ws_bytes(t.map, t.kind, t.cin, t.cout);
-      if (t.split_planes) {                        // (an uncovered shape is reported by the step itself)
-        const int64_t sb = usc_unit_split_ws_bytes(t.map, t.kind, t.cin, t.cout, t.split_planes);
-        if (sb > b) b = sb;
-      }
-      if (b > need) need = b;
-    } else if (t.op == USC_STEP_UNIT_FWD_BF16 && t.map) {
-      const int64_t b = usc_unit_bf16_ws_bytes(t.map, t.kind, t.cin, t.cout);
-      if (b > need) need = b;
-    }
-  }
-  return align_up(need, 256);
-}
 
 // two halves: step i works in half i & 1, so the input-gradient slices a backward step leaves for the next one survive it
 int64_t usc_program_ws_bytes(const usc_step* steps, int32_t n_steps) { return 2 * program_half_bytes(steps, n_steps) + 256; }
@@ -766,13 +755,10 @@ int usc_program_run(const usc_step* steps, int32_t begin, int32_t end, void* ws_
     }
     switch (t.op) {
       case USC_STEP_UNIT_FWD:
-        if (t.split_planes) {
-          rc = usc_conv_bn_act_forward_split(t.map, t.kind, t.x, t.cin, t.W, t.cout, t.split_planes, t.bn, t.residual, t.relu,
-                                             t.y, t.stats, t.out, ws, ws_bytes, s);
-          break;
-        }
-        rc = usc_conv_bn_act_forward(t.map, t.kind, t.x, t.cin, t.W, t.cout, t.bn, t.residual, t.relu, t.y, t.stats, t.out,
-                                     ws, ws_bytes, s);
+        rc = t.split_planes ? usc_conv_bn_act_forward_split(t.map, t.kind, t.x, t.cin, t.W, t.cout, t.split_planes, t.bn,
+                                                            t.residual, t.relu, t.y, t.stats, t.out, ws, ws_bytes, s)
+                            : usc_conv_bn_act_forward(t.map, t.kind, t.x, t.cin, t.W, t.cout, t.bn, t.residual, t.relu, t.y,
+                                                      t.stats, t.out, ws, ws_bytes, s);
         break;
       case USC_STEP_UNIT_FWD_BF16:
         rc = usc_conv_bn_act_forward_bf16(t.map, t.kind, t.x, t.cin, (const uint16_t*)t.W, t.cout, t.bn, t.residual, t.relu,

@@ -450,8 +450,7 @@ class _Trunk(torch.autograd.Function):
         if lane is not None:
             for t in gar.chunks:
                 t.record_stream(lane[0])
-            key = dev.index if dev.index is not None else torch.cuda.current_device()
-            units.queue_lane_join(key)
+            units.queue_lane_join(units._dev_key(dev))
         ctx.state = None
         return (None, None, None, None, None, None, None) + (None,) * len(pl.params)
 

@@ -54,9 +54,14 @@ _LANE = {}     # device index -> (stream, scratch tensor) handed to usc_set_wgra
 _LANE_JOIN_QUEUED = {}     # device index -> id of the graph task whose end-of-backward lane join has been queued
 
 
+def _dev_key(device=None):
+    """Index of `device` in the per-device tables below (the current device when it names none)."""
+    return torch.cuda.current_device() if device is None or device.index is None else device.index
+
+
 def _lane(device):
     """(stream, scratch) of the device's weight-gradient lane, or None when it is switched off."""
-    key = device.index if device.index is not None else torch.cuda.current_device()
+    key = _dev_key(device)
     if key not in _LANE:
         if LANE_MAX_ROWS > 0:
             from . import streams           # a stream measured to run beside the compute stream (streams.py)
@@ -85,8 +90,7 @@ def set_lane_max_rows(max_rows: int):
 
 def join_lane(device=None):
     """The current stream waits for every weight gradient queued on the lane so far (no-op without a lane)."""
-    key = torch.cuda.current_device() if device is None or device.index is None else device.index
-    if _LANE.get(key) is not None:
+    if _LANE.get(_dev_key(device)) is not None:
         check(lib.usc_wgrad_lane_join(ops._stream()), "usc_wgrad_lane_join")
 
 
@@ -95,8 +99,7 @@ def lane_stream_behind_current(device=None):
     None without a lane.  Work issued on it from here on — a gradient bucket's collective (ddp.BucketedGradReducer) — is
     ordered behind the lane's weight gradients AND the current stream's, and the current stream waits for neither.
     Weight gradients still held by the lane's schedule (usc_wgrad_lane_hold) are released first."""
-    key = torch.cuda.current_device() if device is None or device.index is None else device.index
-    ent = _LANE.get(key)
+    ent = _LANE.get(_dev_key(device))
     if ent is None:
         return None
     if lib.usc_wgrad_lane_holding():
@@ -111,8 +114,7 @@ def lane_event(device=None, release=True):
     """An event behind every weight gradient queued on the lane so far (held ones are released first unless release=False),
     or None without a lane: what a gradient bucket's collective on another stream has to wait for
     (ddp.BucketedGradReducer._launch), or the early optimizer step of parameters whose gradients are final."""
-    key = torch.cuda.current_device() if device is None or device.index is None else device.index
-    ent = _LANE.get(key)
+    ent = _LANE.get(_dev_key(device))
     if ent is None:
         return None
     if release and lib.usc_wgrad_lane_holding():
@@ -150,8 +152,7 @@ def _lane_hold(device, n_in, n_out, in_place_dW, *tensors):
         return False
     for t in tensors:
         t.record_stream(lane[0])
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    queue_lane_join(key)
+    queue_lane_join(_dev_key(device))
     return True
 
 
@@ -248,7 +249,7 @@ def _group_max():
 
 
 def _wgrad_queue(device):
-    key = device.index if device.index is not None else torch.cuda.current_device()
+    key = _dev_key(device)
     q = _WGQ.get(key)
     if q is None:
         q = _WGQ[key] = _WgradQueue()
@@ -277,7 +278,7 @@ _WS = {}
 
 
 def workspace(nbytes: int, device):
-    key = device.index if device.index is not None else torch.cuda.current_device()
+    key = _dev_key(device)
     ws = _WS.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = torch.empty(int(nbytes * 1.25) + (1 << 20), dtype=torch.uint8, device=device)
@@ -337,10 +338,22 @@ def _split_ws_bytes(kmap, kind, cin, cout, planes):
     return b
 
 
+# the three forward entry points (csrc/units.hip: forward_unit behind each): workspace bytes, name
+_FORWARD = {
+    "bf16": (lambda kmap, kind, cin, cout, planes: lib.usc_unit_bf16_ws_bytes(kmap.ref, kind, cin, cout),
+             "usc_conv_bn_act_forward_bf16"),
+    "split": (_split_ws_bytes, "usc_conv_bn_act_forward_split"),
+    "f32": (lambda kmap, kind, cin, cout, planes: lib.usc_unit_ws_bytes(kmap.ref, kind, cin, cout), "usc_conv_bn_act_forward"),
+}
+
+
 def unit_forward(x, W3, bn, kmap: KMapRef, kind, residual, relu, wp=None, planes=0):
     """-> (y conv output, stats f32[4,c], out).  W3 f32[K,cin,cout].  wp: the packed bf16 weights
     (precision.unit_weights) -> the conv runs in bf16 (inference only); planes 2 / 3 (precision.train_planes) -> in split
     bf16 (usc_conv_bn_act_forward_split, the function a step program's marked step calls); else f32."""
+    form = "bf16" if wp is not None else ("split" if planes else "f32")
+    ws_bytes, name = _FORWARD[form]
+    weights, extra = (wp if form == "bf16" else W3), ((planes,) if form == "split" else ())
     dev = x.device
     K, cin, cout = W3.shape
     n_out = kmap.n_in if kind == UP else kmap.n_out
@@ -348,26 +361,10 @@ def unit_forward(x, W3, bn, kmap: KMapRef, kind, residual, relu, wp=None, planes
     out = torch.empty((n_out, cout), dtype=torch.float32, device=dev)
     stats = torch.empty((4, cout), dtype=torch.float32, device=dev)
     _, bref = _bn_desc(bn, _training(bn))
-    if wp is not None:
-        ws = workspace(lib.usc_unit_bf16_ws_bytes(kmap.ref, kind, cin, cout), dev)
-        check(lib.usc_conv_bn_act_forward_bf16(kmap.ref, kind, x.data_ptr(), cin, wp.data_ptr(), cout, bref,
-                                               None if residual is None else residual.data_ptr(), int(relu),
-                                               y.data_ptr(), stats.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                                               ws.numel(), ops._stream()), "usc_conv_bn_act_forward_bf16")
-        return y, stats, out
-    if planes:
-        ws = workspace(_split_ws_bytes(kmap, kind, cin, cout, planes), dev)
-        check(lib.usc_conv_bn_act_forward_split(kmap.ref, kind, x.data_ptr(), cin, W3.data_ptr(), cout, planes, bref,
-                                                None if residual is None else residual.data_ptr(), int(relu),
-                                                y.data_ptr(), stats.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                                                ws.numel(), ops._stream()), "usc_conv_bn_act_forward_split")
-        return y, stats, out
-    wsb = lib.usc_unit_ws_bytes(kmap.ref, kind, cin, cout)
-    ws = workspace(wsb, dev)
-    check(lib.usc_conv_bn_act_forward(kmap.ref, kind, x.data_ptr(), cin, W3.data_ptr(), cout, bref,
-                                      None if residual is None else residual.data_ptr(), int(relu), y.data_ptr(),
-                                      stats.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()),
-          "usc_conv_bn_act_forward")
+    ws = workspace(ws_bytes(kmap, kind, cin, cout, planes), dev)
+    check(getattr(lib, name)(kmap.ref, kind, x.data_ptr(), cin, weights.data_ptr(), cout, *extra, bref,
+                             None if residual is None else residual.data_ptr(), int(relu), y.data_ptr(), stats.data_ptr(),
+                             out.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()), name)
     return y, stats, out
 
 
