@@ -686,8 +686,8 @@ def _mask_logits(feats, mask_embed, chain=False):
     return (out, nxt) if chain else out
 
 
-def multihead_attention(mha: nn.MultiheadAttention, query, key, value, attn_mask=None, mask_bsl=None, pos_q=None,
-                        pos_k=None, residual=False):
+def multihead_attention(mha: nn.MultiheadAttention, query, key, value, attn_mask=None, pos_q=None, pos_k=None,
+                        residual=False):
     """nn.MultiheadAttention.forward(query + pos_q, key + pos_k, value, attn_mask=…, need_weights=False)[0] for the
     sequence-first layout, dropout 0 and a boolean mask (True = masked), with the input / output projections
     through ops.in_proj / ops.linear (same parameters, same state_dict); the positional adds of the reference
@@ -705,16 +705,10 @@ def multihead_attention(mha: nn.MultiheadAttention, query, key, value, attn_mask
     else:
         q, k, v = ops.in_proj(query, key, value, mha.in_proj_weight, mha.in_proj_bias, pos_q=pos_q, pos_k=pos_k)
     done = (lambda o: (o, res)) if residual else (lambda o: o)
-    if mask_bsl is not None and hd == 16 and L <= fused_attn_max_queries():
-        # `mask_bsl` = the decoder's bool[B, S, L] mask (same for every head): fused HIP kernels, no score tensor
-        out = ops.masked_cross_attention(q, k, v, mask_bsl, H)
-        return done(ops.linear(out, mha.out_proj.weight, mha.out_proj.bias))
-    if mask_bsl is None and attn_mask is None and hd == 16 and L == S and L <= fused_attn_max_queries():
+    if attn_mask is None and hd == 16 and L == S and L <= fused_attn_max_queries():
         # the decoder's self attention (100 queries; up to 256): one HIP launch each way instead of the library's fused kernels
         out = ops.self_attention(q, k, v, H)
         return done(ops.linear(out, mha.out_proj.weight, mha.out_proj.bias))
-    if mask_bsl is not None:
-        attn_mask = mask_bsl.repeat_interleave(H, dim=0).permute(0, 2, 1)
     q = q.reshape(L, B * H, hd).transpose(0, 1).reshape(B, H, L, hd)
     k = k.reshape(S, B * H, hd).transpose(0, 1).reshape(B, H, S, hd)
     v = v.reshape(S, B * H, hd).transpose(0, 1).reshape(B, H, S, hd)
@@ -930,17 +924,21 @@ class CrossAttentionLayer(nn.Module):
     def forward(self, tgt, memory, memory_mask=None, memory_key_padding_mask=None, pos=None, query_pos=None,
                 memory_mask_bsl=None):
         """`memory_mask_bsl`: the same mask as `memory_mask` in the decoder's own bool[B, S, L] layout (not repeated
-        per head); when given on a HIP device the fused attention kernels are used."""
+        per head); when given on a HIP device this is forward_kv on the layer's own keys and values."""
+        mha = self.multihead_attn
+        on_device = memory_key_padding_mask is None and mha.dropout == 0.0 and tgt.is_cuda
+        if on_device and memory_mask_bsl is not None:
+            k, v = ops.in_proj_kv(memory, mha.in_proj_weight, mha.in_proj_bias, pos=pos)
+            return self.forward_kv(tgt, k, v, memory_mask_bsl, query_pos)
         src = self.norm(tgt) if self.normalize_before else tgt
-        if memory_mask is None and memory_mask_bsl is not None and not src.is_cuda:
-            memory_mask = memory_mask_bsl.repeat_interleave(self.multihead_attn.num_heads, dim=0).permute(0, 2, 1)
-        if memory_key_padding_mask is None and self.multihead_attn.dropout == 0.0 and src.is_cuda:
+        if memory_mask is None and memory_mask_bsl is not None:
+            memory_mask = memory_mask_bsl.repeat_interleave(mha.num_heads, dim=0).permute(0, 2, 1)
+        if on_device:
             if not self.normalize_before:
-                upd, tgt = multihead_attention(self.multihead_attn, src, memory, memory, attn_mask=memory_mask,
-                                               mask_bsl=memory_mask_bsl, pos_q=query_pos, pos_k=pos, residual=True)
+                upd, tgt = multihead_attention(mha, src, memory, memory, attn_mask=memory_mask, pos_q=query_pos,
+                                               pos_k=pos, residual=True)
             else:
-                upd = multihead_attention(self.multihead_attn, src, memory, memory, attn_mask=memory_mask,
-                                          mask_bsl=memory_mask_bsl, pos_q=query_pos, pos_k=pos)
+                upd = multihead_attention(mha, src, memory, memory, attn_mask=memory_mask, pos_q=query_pos, pos_k=pos)
         else:
             upd = self.multihead_attn(query=_with_pos(src, query_pos), key=_with_pos(memory, pos), value=memory,
                                       attn_mask=memory_mask, key_padding_mask=memory_key_padding_mask,

@@ -485,6 +485,29 @@ def _grad_written(*params):
                 GRAD_WRITTEN_HOOK(p)
 
 
+def _param_grads(params, zeros=False):
+    """The parameter-gradient rule of one backward node, for its parameters in order (None: the node has no such
+    parameter) -> (buffers, accumulate, finish).  In place only if EVERY parameter has a target (_grad_target): the
+    buffers are then the p.grad tensors and the kernels add into them (accumulate); otherwise fresh buffers that the
+    kernels write and autograd gets whole — zeros=True for a node that writes only some rows of a packed parameter.
+    finish(), after the node's last launch: -> what the node returns for the parameters (None where written in place,
+    which is also reported: _grad_written)."""
+    live = [p for p in params if p is not None]
+    bufs = [_grad_target(p) for p in live]
+    in_place = all(t is not None for t in bufs)
+    if not in_place:
+        bufs = [torch.zeros_like(p) if zeros else torch.empty_like(p) for p in live]
+    it = iter(bufs)
+    bufs = [None if p is None else next(it) for p in params]
+
+    def finish():
+        if not in_place:
+            return tuple(bufs)
+        _grad_written(*params)
+        return (None,) * len(params)
+    return bufs, in_place, finish
+
+
 def wgrad(a, b, K, a_idx=None, b_idx=None, koff=None, into=None, out=None, nbr=None):
     """dW[k] = sum_{p in list k} a[a_idx[p]]^T b[b_idx[p]] -> f32[K,cin,cout]; ADDED into `into`, or WRITTEN to `out`
     (a contiguous buffer of K*cin*cout floats), when given.
@@ -1225,19 +1248,13 @@ class _LayerNorm(torch.autograd.Function):
         from .graphs import grad_buffer_for
         buf = grad_buffer_for(x2)
         dx = buf.view(rows, d) if buf is not None else torch.empty_like(x2)
-        tg, tb = _grad_target(ctx.w_param), _grad_target(ctx.b_param)
-        in_place = tg is not None and tb is not None
-        dgamma = tg if in_place else torch.empty_like(weight)
-        dbeta = tb if in_place else torch.empty_like(weight)
+        (dgamma, dbeta), in_place, finish = _param_grads((ctx.w_param, ctx.b_param))
         wsb = lib.usc_layernorm_bwd_ws_bytes(rows, d)
         ws = _ws(wsb, x2.device) if wsb > 0 else None
         check(lib.usc_layernorm_bwd_ex(_ptr(dy2), _ptr(x2), _ptr(mean), _ptr(rstd), _ptr(weight), rows, d, _ptr(dadd),
                                        _ptr(dx), _ptr(dgamma), _ptr(dbeta), int(in_place), _ptr(ws), wsb, _stream()),
               "usc_layernorm_bwd")
-        if in_place:
-            dgamma = dbeta = None
-            _grad_written(ctx.w_param, ctx.b_param)
-        return dx.view(ctx.shape), dgamma, dbeta, None, None
+        return (dx.view(ctx.shape),) + finish() + (None, None)
 
 
 class _AddLayerNorm(torch.autograd.Function):
@@ -1350,7 +1367,8 @@ def _lin_bwd(dy2, x2, W, dW_out, db_out, need_dx=True, accumulate=False, add=Non
     M, N = dy2.shape
     K = x2.shape[1]
     if want_dx_b or dx_add2 is not None:
-        if not need_dx:
+        if not need_dx:                          # the parameter gradients only
+            _lin_bwd(dy2, x2, W, dW_out, db_out, False, accumulate, add, y_relu)
             return (None, None) if want_dx_b else None
         if _small_linear_ok(M, K, N):
             dx = torch.empty((M, K), dtype=torch.float32, device=dy2.device)
@@ -1405,12 +1423,12 @@ class _LinearRows(torch.autograd.Function):
                 raise RuntimeError("linear: pad_rows_to is for one [.., M, K] table, M <= pad_rows_to, without relu")
             y = _lin_fwd(x2, W, b, pad_rows_to=pad_rows_to)
             ctx.save_for_backward(x2, W, None)
-            ctx.has_bias, ctx.shape = b is not None, x.shape
+            ctx.shape = x.shape
             ctx.w_param, ctx.b_param = W, b
             return y.view(*x.shape[:-2], int(pad_rows_to), W.shape[0])
         y = _lin_fwd(x2, W, b, relu=relu)
         ctx.save_for_backward(x2, W, y if relu else None)
-        ctx.has_bias, ctx.shape = b is not None, x.shape
+        ctx.shape = x.shape
         ctx.w_param, ctx.b_param = W, b
         y = y.view(*x.shape[:-1], W.shape[0])
         # passthrough: x is handed back as a second output; whatever gradient arrives there (the residual path around
@@ -1421,21 +1439,11 @@ class _LinearRows(torch.autograd.Function):
     def backward(ctx, dy, dres=None):
         x2, W, y_relu = ctx.saved_tensors
         dy2 = dy.contiguous().view(-1, W.shape[0])[:ctx.rows]       # [:rows]: drops the zero-extension rows, if any
-        tw = _grad_target(ctx.w_param)
-        tb = _grad_target(ctx.b_param) if ctx.has_bias else None
-        in_place = tw is not None and (tb is not None or not ctx.has_bias)
-        if in_place:
-            dW, db = tw, tb
-        else:
-            dW = torch.empty_like(W)
-            db = torch.empty(W.shape[0], dtype=torch.float32, device=W.device) if ctx.has_bias else None
+        (dW, db), in_place, finish = _param_grads((ctx.w_param, ctx.b_param))
         dres2 = None if dres is None else dres.contiguous().view(-1, x2.shape[1])
         dx = _lin_bwd(dy2, x2, W, dW, db, need_dx=ctx.needs_input_grad[0], accumulate=in_place, y_relu=y_relu,
                       dx_add=dres2)
-        if in_place:
-            dW = db = None
-            _grad_written(ctx.w_param, ctx.b_param if ctx.has_bias else None)
-        return (None if dx is None else dx.view(ctx.shape)), dW, db, None, None, None
+        return (None if dx is None else dx.view(ctx.shape),) + finish() + (None, None, None)
 
 
 def linear(x, W, b=None, relu=False, passthrough=False, pad_rows_to=None):
@@ -1449,156 +1457,90 @@ def linear(x, W, b=None, relu=False, passthrough=False, pad_rows_to=None):
     return _LinearRows.apply(x, W, b, relu, passthrough, pad_rows_to)
 
 
-class _InProj(torch.autograd.Function):
-    """q, k, v = the three input projections of nn.MultiheadAttention from its packed in_proj_weight [3E,E] /
-    in_proj_bias [3E] (reference: nn.MultiheadAttention inside models/mask3d.py:491-605).  One Function so that the
-    three weight gradients are written into ONE [3E,E] tensor instead of three sliced ones summed by autograd.
-    pos_q / pos_k (optional): q = (xq + pos_q) Wq, k = (xk + pos_k) Wk — the `with_pos_embed` adds of the reference
-    (:485, :517) folded into the projection launches.  Inputs that are the SAME tensor (self attention: xq, xk, xv;
-    cross attention: xk, xv) get one summed gradient, chained through the input-gradient launches (dx_add) instead of
-    separate tensors added by autograd."""
-
-    @staticmethod
-    def forward(ctx, xq, xk, xv, W, b, pos_q, pos_k, residual=False):
-        E = W.shape[1]
-        xs = [t.contiguous().view(-1, E) for t in (xq, xk, xv)]
-        ps = [None if t is None else t.contiguous().view(-1, E) for t in (pos_q, pos_k, None)]
-        for j in range(2):     # many-row inputs (the sampled voxels): no fused add on those kernels, keep the sum
-            if ps[j] is not None and not _small_linear_ok(xs[j].shape[0], E, E):
-                xs[j], ps[j] = xs[j] + ps[j], None
-        def same_t(a, c):
-            return a.data_ptr() == c.data_ptr() and a.shape == c.shape
-        if (same_t(xs[0], xs[1]) and same_t(xs[1], xs[2]) and _small_linear_ok(xs[0].shape[0], E, 3 * E)
-                and W.is_contiguous() and (ps[0] is None) == (ps[1] is None)
-                and (ps[0] is None or same_t(ps[0], ps[1]))):
-            # self attention: one launch for the three projections of the one input ([3, M, E], each its own matrix)
-            M = xs[0].shape[0]
-            y3 = torch.empty((3, M, E), dtype=torch.float32, device=W.device)
-            check(lib.usc_linear_fwd_split(_ptr(xs[0]), _ptr(ps[0]), _ptr(W), _ptr(b), M, 3 * E, E, 2 * E, E, _ptr(y3),
-                                           _stream()), "usc_linear_fwd_split")
-            outs = [y3[0], y3[1], y3[2]]
-        else:
-            outs = [_lin_fwd(xs[j], W[j * E:(j + 1) * E], b[j * E:(j + 1) * E], add=ps[j]) for j in range(3)]
-        ctx.save_for_backward(xs[0], xs[1], xs[2], W, ps[0], ps[1])
-        ctx.shapes = (xq.shape, xk.shape, xv.shape)
-        ctx.pos_shapes = (None if pos_q is None else pos_q.shape, None if pos_k is None else pos_k.shape)
-        ctx.w_param, ctx.b_param = W, b
-
-        def same(a, c):
-            return a is not None and c is not None and a.data_ptr() == c.data_ptr() and a.shape == c.shape \
-                and a.stride() == c.stride()
-        # q and k may share one summed input gradient only if their positional terms are the same too (both absent,
-        # or one tensor) — also when a term was folded into the many-row input above
-        ctx.same_qk, ctx.same_kv = same(xq, xk), same(xk, xv)
-        ctx.same_pos = (pos_q is None and pos_k is None) or same(pos_q, pos_k)
-        out = tuple(o.view(*shp[:-1], E) for o, shp in zip(outs, ctx.shapes))
-        # residual: xq is handed back as a fourth output (the `tgt + attention(tgt ...)` residual of the decoder
-        # blocks); its gradient joins the query input's inside the input-gradient launches
-        return out + (xq,) if residual else out
-
-    @staticmethod
-    def backward(ctx, dq, dk, dv, dres=None):
-        x0, x1, x2, W, p0, p1 = ctx.saved_tensors
-        E = W.shape[1]
-        dres2 = None if dres is None else dres.contiguous().view(-1, E)
-        tw, tb = _grad_target(ctx.w_param), _grad_target(ctx.b_param)
-        in_place = tw is not None and tb is not None
-        if in_place:
-            dW, db = tw, tb
-        else:
-            dW = torch.empty_like(W)
-            db = torch.empty(3 * E, dtype=torch.float32, device=W.device)
-        need = list(ctx.needs_input_grad[:3])
-        need_pq, need_pk = ctx.needs_input_grad[5], ctx.needs_input_grad[6]
-
-        def bwd(j, dyj, xj, pj, need_dx, dx_add=None):
-            return _lin_bwd(dyj.contiguous().view(-1, E), xj, W[j * E:(j + 1) * E], dW[j * E:(j + 1) * E],
-                            db[j * E:(j + 1) * E], need_dx=need_dx, accumulate=in_place, add=pj, dx_add=dx_add)
-
-        M = x0.shape[0]
-        adjacent = (dq.is_contiguous() and dk.is_contiguous() and dv.is_contiguous()
-                    and dk.data_ptr() == dq.data_ptr() + 4 * M * E and dv.data_ptr() == dk.data_ptr() + 4 * M * E)
-        if (ctx.same_qk and ctx.same_kv and ctx.same_pos and need[0] and adjacent and W.is_contiguous()
-                and _small_linear_ok(M, 3 * E, E) and dW.is_contiguous() and db.is_contiguous()):
-            # self attention: the three projections backwards in one launch (usc_qkv_proj_bwd)
-            gx = torch.empty((M, E), dtype=torch.float32, device=W.device)
-            gpos = torch.empty_like(gx) if (need_pq and p0 is not None) else None
-            check(lib.usc_qkv_proj_bwd(_ptr(dq), _ptr(x0), _ptr(p0), _ptr(W), M, E, _ptr(gx), _ptr(gpos), _ptr(dres2),
-                                       _ptr(dW), _ptr(db), int(in_place), _stream()), "usc_qkv_proj_bwd")
-            out_x = (gx, None, None)
-            out_p = (gpos, None)
-        elif dres2 is not None and ctx.same_qk and ctx.same_kv and ctx.same_pos and need[0]:
-            # self attention with the residual: v (+ residual) first, then k, then q on top of both; the q launch also
-            # writes the sum WITHOUT the v/residual part — the positional term's gradient
-            gv = bwd(2, dv, x2, None, True, dx_add=dres2)
-            gk = bwd(1, dk, x1, p1, True)
-            gx, gpos = _lin_bwd(dq.contiguous().view(-1, E), x0, W[:E], dW[:E], db[:E], need_dx=True,
-                                accumulate=in_place, add=p0, dx_add=gk, dx_add2=gv, want_dx_b=True)
-            out_x = (gx, None, None)
-            out_p = (gpos if need_pq else None, None)
-        elif dres2 is not None and not ctx.same_qk and need[0]:
-            # cross attention with the residual: the query product feeds d(tgt) (+ residual) and d(query_pos)
-            gk = bwd(1, dk, x1, p1, need[1] or need_pk)
-            gq, gq_pos = _lin_bwd(dq.contiguous().view(-1, E), x0, W[:E], dW[:E], db[:E], need_dx=True,
-                                  accumulate=in_place, add=p0, dx_add2=dres2, want_dx_b=True)
-            chain_v = ctx.same_kv and gk is not None
-            gv = bwd(2, dv, x2, None, need[2], dx_add=gk if chain_v else None)
-            out_x = (gq, gv, None) if chain_v else (gq, gk, gv)
-            out_p = (gq_pos if need_pq else None, gk if need_pk else None)
-        else:
-            out_x, out_p = _InProj._backward_plain(ctx, bwd, dq, dk, dv, x0, x1, x2, p0, p1, need, need_pq, need_pk)
-            if dres2 is not None and need[0]:          # shapes the fused forms above do not cover
-                out_x = (dres2 if out_x[0] is None else out_x[0] + dres2,) + tuple(out_x[1:])
-        if in_place:
-            dW = db = None
-            _grad_written(ctx.w_param, ctx.b_param)
-        gx = tuple(None if (g is None or not n) else g.view(shp) for g, n, shp in zip(out_x, need, ctx.shapes))
-        gp = tuple(None if g is None else g.view(shp) for g, shp in zip(out_p, ctx.pos_shapes))
-        return gx + (dW, db) + gp + (None,)
-
-    @staticmethod
-    def _backward_plain(ctx, bwd, dq, dk, dv, x0, x1, x2, p0, p1, need, need_pq, need_pk):
-        # k first, then q on top of it when they share the input (and the positional term); v last on top of both
-        # when it shares the input too: one summed tensor per distinct input
-        gk = bwd(1, dk, x1, p1, need[1] or need_pk)
-        chain_q = ctx.same_qk and gk is not None and ctx.same_pos
-        gq = bwd(0, dq, x0, p0, need[0] or need_pq, dx_add=gk if chain_q else None)
-        if chain_q:                       # gq = d(xq + pos) summed over the q and k paths
-            gx, gpos = gq, gq
-            gv = bwd(2, dv, x2, None, need[2], dx_add=gx if ctx.same_kv else None)
-            if ctx.same_kv:
-                out_x = (gv, None, None)
-            else:
-                out_x = (gx, None, gv)
-            out_p = (gpos if need_pq else None, None)
-        else:
-            chain_v = ctx.same_kv and gk is not None
-            gv = bwd(2, dv, x2, None, need[2], dx_add=gk if chain_v else None)
-            out_x = (gq, gv, None) if chain_v else (gq, gk, gv)
-            out_p = (gq if need_pq else None, gk if need_pk else None)
-        return out_x, out_p
+# The input projections of nn.MultiheadAttention from its packed in_proj_weight [3E,E] / in_proj_bias [3E] (reference:
+# nn.MultiheadAttention inside models/mask3d.py:491-605) in the two forms the decoder uses: _InProjSelf (one input for
+# q, k and v) and _InProjQ + _InProjKV (queries apart from the memory).  Every node writes its row blocks of ONE [3E,E]
+# weight gradient / [3E] bias gradient; the `with_pos_embed` adds of the reference (:485, :517) are folded into the
+# projection launches, and an input used twice gets one summed gradient chained through the input-gradient launches
+# (dx_add) instead of separate tensors added by autograd.
 
 
-def _packed_grad_targets(W, b):
-    """(dW [3E,E], db [3E], in_place) for one part of a packed in-projection: the parameters' gradient buffers when they
-    exist (the part's rows are added into), else fresh zero tensors (returned to autograd whole)."""
-    tw, tb = _grad_target(W), _grad_target(b)
-    if tw is not None and tb is not None:
-        return tw, tb, True
-    return torch.zeros_like(W), torch.zeros_like(b), False
+def _rows(t, E):
+    return None if t is None else t.contiguous().view(-1, E)
 
 
-class _InProjQ(torch.autograd.Function):
-    """q = (x + pos) Wq^T + bq, Wq = in_proj_weight[:E] — the QUERY third of nn.MultiheadAttention's packed input
-    projection on its own (reference models/mask3d.py:547-605 CrossAttentionLayer, :517 with_pos_embed), so that the key /
-    value thirds can be computed elsewhere (ops.in_proj_kv: they do not depend on the queries).  residual: x comes back
-    as a second output and its gradient (the block's residual path) is summed inside the input-gradient launch."""
+def _same_tensor(a, c):
+    return a.data_ptr() == c.data_ptr() and a.shape == c.shape and a.stride() == c.stride()
+
+
+class _InProjSelf(torch.autograd.Function):
+    """Self attention: q = (x + pos) Wq^T + bq, k = (x + pos) Wk^T + bk, v = x Wv^T + bv.  residual: x comes back as a
+    fourth output (the `tgt + attention(tgt ...)` residual of the decoder blocks); its gradient joins x's inside the
+    input-gradient launches."""
 
     @staticmethod
     def forward(ctx, x, W, b, pos, residual=False):
         E = W.shape[1]
-        x2 = x.contiguous().view(-1, E)
-        p2 = None if pos is None else pos.contiguous().view(-1, E)
+        x2, p2 = _rows(x, E), _rows(pos, E)
+        M = x2.shape[0]
+        xp = x2
+        if p2 is not None and not _small_linear_ok(M, E, E):
+            xp, p2 = x2 + p2, None                  # (many rows: no fused add on those kernels)
+        if _small_linear_ok(M, E, 3 * E) and W.is_contiguous():
+            # one launch for the three projections ([3, M, E], each its own matrix)
+            y3 = torch.empty((3, M, E), dtype=torch.float32, device=W.device)
+            check(lib.usc_linear_fwd_split(_ptr(x2), _ptr(p2), _ptr(W), _ptr(b), M, 3 * E, E, 2 * E, E, _ptr(y3),
+                                           _stream()), "usc_linear_fwd_split")
+            outs = (y3[0], y3[1], y3[2])
+        else:
+            outs = (_lin_fwd(xp, W[:E], b[:E], add=p2), _lin_fwd(xp, W[E:2 * E], b[E:2 * E], add=p2),
+                    _lin_fwd(x2, W[2 * E:], b[2 * E:]))
+        ctx.save_for_backward(xp, x2, W, p2)
+        ctx.shape, ctx.pos_shape = x.shape, None if pos is None else pos.shape
+        ctx.w_param, ctx.b_param = W, b
+        out = tuple(o.view(*x.shape[:-1], E) for o in outs)
+        return out + (x,) if residual else out
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv, dres=None):
+        xp, x2, W, p2 = ctx.saved_tensors
+        E = W.shape[1]
+        M = x2.shape[0]
+        dres2 = _rows(dres, E)
+        (dW, db), in_place, finish = _param_grads((ctx.w_param, ctx.b_param))
+        need_x, need_pos = ctx.needs_input_grad[0], ctx.pos_shape is not None and ctx.needs_input_grad[3]
+        adjacent = (dq.is_contiguous() and dk.is_contiguous() and dv.is_contiguous()
+                    and dk.data_ptr() == dq.data_ptr() + 4 * M * E and dv.data_ptr() == dk.data_ptr() + 4 * M * E)
+        if (need_x and adjacent and W.is_contiguous() and _small_linear_ok(M, 3 * E, E) and dW.is_contiguous()
+                and db.is_contiguous()):
+            # the attention core hands dq | dk | dv over as one table: the three projections backwards in one launch
+            gx = torch.empty((M, E), dtype=torch.float32, device=W.device)
+            gpos = torch.empty_like(gx) if need_pos else None
+            check(lib.usc_qkv_proj_bwd(_ptr(dq), _ptr(x2), _ptr(p2), _ptr(W), M, E, _ptr(gx), _ptr(gpos), _ptr(dres2),
+                                       _ptr(dW), _ptr(db), int(in_place), _stream()), "usc_qkv_proj_bwd")
+        else:
+            # v (+ residual) first, then k, then q on top of both; the q launch also writes the sum WITHOUT the
+            # v / residual part — the positional term's gradient
+            def bwd(j, dyj, xj, pj, **kw):
+                return _lin_bwd(_rows(dyj, E), xj, W[j * E:(j + 1) * E], dW[j * E:(j + 1) * E], db[j * E:(j + 1) * E],
+                                accumulate=in_place, add=pj, **kw)
+            gv = bwd(2, dv, x2, None, need_dx=need_x, dx_add=dres2)
+            gk = bwd(1, dk, xp, p2, need_dx=need_x or need_pos)
+            gx, gpos = bwd(0, dq, xp, p2, need_dx=need_x or need_pos, dx_add=gk, dx_add2=gv, want_dx_b=True)
+        return ((gx.view(ctx.shape) if need_x else None,) + finish()
+                + (gpos.view(ctx.pos_shape) if need_pos else None, None))
+
+
+class _InProjQ(torch.autograd.Function):
+    """q = (x + pos) Wq^T + bq, Wq = in_proj_weight[:E] — the QUERY third on its own (reference models/mask3d.py:547-605
+    CrossAttentionLayer, :517 with_pos_embed), so that the key / value thirds can be computed elsewhere (_InProjKV: they
+    do not depend on the queries).  residual: x comes back as a second output and its gradient (the block's residual
+    path) is summed inside the input-gradient launch."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, pos, residual=False):
+        E = W.shape[1]
+        x2, p2 = _rows(x, E), _rows(pos, E)
         if p2 is not None and not _small_linear_ok(x2.shape[0], E, E):
             x2, p2 = x2 + p2, None
         y = _lin_fwd(x2, W[:E], b[:E], add=p2)
@@ -1612,86 +1554,90 @@ class _InProjQ(torch.autograd.Function):
     def backward(ctx, dq, dres=None):
         x2, W, p2 = ctx.saved_tensors
         E = W.shape[1]
-        dW, db, in_place = _packed_grad_targets(ctx.w_param, ctx.b_param)
-        dq2 = dq.contiguous().view(-1, E)
-        dres2 = None if dres is None else dres.contiguous().view(-1, E)
+        (dW, db), in_place, finish = _param_grads((ctx.w_param, ctx.b_param), zeros=True)
+        dres2 = _rows(dres, E)
         need_pos = ctx.pos_shape is not None and ctx.needs_input_grad[3]
         if dres2 is not None and need_pos:
-            gx, gpos = _lin_bwd(dq2, x2, W[:E], dW[:E], db[:E], need_dx=True, accumulate=in_place, add=p2, dx_add2=dres2,
-                                want_dx_b=True)
+            gx, gpos = _lin_bwd(_rows(dq, E), x2, W[:E], dW[:E], db[:E], need_dx=True, accumulate=in_place, add=p2,
+                                dx_add2=dres2, want_dx_b=True)
         else:
-            gx = _lin_bwd(dq2, x2, W[:E], dW[:E], db[:E], need_dx=True, accumulate=in_place, add=p2, dx_add=dres2)
-            gpos = gx if need_pos else None
-        if in_place:
-            dW = db = None
-            _grad_written(ctx.w_param, ctx.b_param)
-        return (gx.view(ctx.shape), dW, db, None if gpos is None or ctx.pos_shape is None else gpos.view(ctx.pos_shape), None)
+            gx = gpos = _lin_bwd(_rows(dq, E), x2, W[:E], dW[:E], db[:E], need_dx=True, accumulate=in_place, add=p2,
+                                 dx_add=dres2)
+        return (gx.view(ctx.shape),) + finish() + (gpos.view(ctx.pos_shape) if need_pos else None, None)
 
 
 class _InProjKV(torch.autograd.Function):
-    """k = (x + pos) Wk^T + bk, v = x Wv^T + bv with Wk, Wv = in_proj_weight[E:2E], [2E:3E]: the key / value thirds of the
-    packed input projection over the sampled voxels of a decoder pass.  `outs` (optional): (k, v) buffers to write into
-    (the static inputs of a captured pass).  One summed gradient for x (k's part chained into v's launch)."""
+    """k = (xk + pos) Wk^T + bk, v = xv Wv^T + bv with Wk, Wv = in_proj_weight[E:2E], [2E:3E]: the key / value thirds (in
+    the decoder: over the sampled voxels of a pass, xk and xv one tensor).  `outs` (optional): (k, v) buffers to write
+    into (the static inputs of a captured pass).  One tensor for both gets one summed gradient (k's part chained into
+    v's launch)."""
 
     @staticmethod
-    def forward(ctx, x, W, b, pos, outs=None):
+    def forward(ctx, xk, xv, W, b, pos, outs=None):
         E = W.shape[1]
-        x2 = x.contiguous().view(-1, E)
-        p2 = None if pos is None else pos.contiguous().view(-1, E)
-        xk, pk = x2, p2
-        if pk is not None and not _small_linear_ok(x2.shape[0], E, E):
-            xk, pk = x2 + pk, None                  # (many rows: no fused add on those kernels)
+        ctx.shared = _same_tensor(xk, xv)
+        k2, pk = _rows(xk, E), _rows(pos, E)
+        v2 = k2 if ctx.shared else _rows(xv, E)
+        if pk is not None and not _small_linear_ok(k2.shape[0], E, E):
+            k2, pk = k2 + pk, None                  # (many rows: no fused add on those kernels)
         ok, ov = (None, None) if outs is None else (outs[0].detach().view(-1, E), outs[1].detach().view(-1, E))
-        k = _lin_fwd(xk, W[E:2 * E], b[E:2 * E], add=pk, out=ok)
-        v = _lin_fwd(x2, W[2 * E:], b[2 * E:], out=ov)
-        ctx.save_for_backward(xk, x2, W, pk)
-        ctx.shape = x.shape
+        k = _lin_fwd(k2, W[E:2 * E], b[E:2 * E], add=pk, out=ok)
+        v = _lin_fwd(v2, W[2 * E:], b[2 * E:], out=ov)
+        ctx.save_for_backward(k2, v2, W, pk)
+        ctx.shapes, ctx.pos_shape = (xk.shape, xv.shape), None if pos is None else pos.shape
         ctx.w_param, ctx.b_param = W, b
-        shp = (*x.shape[:-1], E)
-        return k.view(shp), v.view(shp)
+        return k.view(*xk.shape[:-1], E), v.view(*xv.shape[:-1], E)
 
     @staticmethod
     def backward(ctx, dk, dv):
-        xk, x2, W, pk = ctx.saved_tensors
+        k2, v2, W, pk = ctx.saved_tensors
         E = W.shape[1]
-        dW, db, in_place = _packed_grad_targets(ctx.w_param, ctx.b_param)
-        need = ctx.needs_input_grad[0]
-        gk = _lin_bwd(dk.contiguous().view(-1, E), xk, W[E:2 * E], dW[E:2 * E], db[E:2 * E], need_dx=need,
+        (dW, db), in_place, finish = _param_grads((ctx.w_param, ctx.b_param), zeros=True)
+        need_k, need_v = ctx.needs_input_grad[:2]
+        need_pos = ctx.pos_shape is not None and ctx.needs_input_grad[4]
+        gk = _lin_bwd(_rows(dk, E), k2, W[E:2 * E], dW[E:2 * E], db[E:2 * E], need_dx=need_k or need_pos,
                       accumulate=in_place, add=pk)
-        gx = _lin_bwd(dv.contiguous().view(-1, E), x2, W[2 * E:], dW[2 * E:], db[2 * E:], need_dx=need,
-                      accumulate=in_place, dx_add=gk)
-        if in_place:
-            dW = db = None
-            _grad_written(ctx.w_param, ctx.b_param)
-        return (None if gx is None else gx.view(ctx.shape)), dW, db, None, None
+        gv = _lin_bwd(_rows(dv, E), v2, W[2 * E:], dW[2 * E:], db[2 * E:], need_dx=need_v, accumulate=in_place,
+                      dx_add=gk if ctx.shared else None)
+        gpos = gk.view(ctx.pos_shape) if need_pos else None
+        if ctx.shared:                              # gv is the sum: handed to the first of the two
+            gk, gv = gv, None
+        elif not need_k:
+            gk = None
+        return (None if gk is None else gk.view(ctx.shapes[0]), None if gv is None else gv.view(ctx.shapes[1])) \
+            + finish() + (gpos, None)
 
 
-def in_proj_q(x, W, b, pos=None, residual=False):
-    _chk(W, torch.float32, "in_proj_weight")
-    _chk(b, torch.float32, "in_proj_bias")
-    if pos is not None and pos.shape != x.shape:
-        raise RuntimeError(f"in_proj_q: pos {tuple(pos.shape)} must have the shape of the input {tuple(x.shape)}")
-    return _InProjQ.apply(x, W, b, pos, residual)
-
-
-def in_proj_kv(x, W, b, pos=None, outs=None):
-    _chk(W, torch.float32, "in_proj_weight")
-    _chk(b, torch.float32, "in_proj_bias")
-    if pos is not None and pos.shape != x.shape:
-        raise RuntimeError(f"in_proj_kv: pos {tuple(pos.shape)} must have the shape of the input {tuple(x.shape)}")
-    return _InProjKV.apply(x, W, b, pos, outs)
-
-
-def in_proj(xq, xk, xv, W, b, pos_q=None, pos_k=None, residual=False):
+def _in_proj_checks(name, W, b, x, pos):
     _chk(W, torch.float32, "in_proj_weight")
     _chk(b, torch.float32, "in_proj_bias")
     # the kernels read the positional term row for row: no broadcasting (a [Q,1,E] term with B > 1 would be read
     # out of bounds)
-    if pos_q is not None and pos_q.shape != xq.shape:
-        raise RuntimeError(f"in_proj: pos_q {tuple(pos_q.shape)} must have the shape of the query input {tuple(xq.shape)}")
-    if pos_k is not None and pos_k.shape != xk.shape:
-        raise RuntimeError(f"in_proj: pos_k {tuple(pos_k.shape)} must have the shape of the key input {tuple(xk.shape)}")
-    return _InProj.apply(xq, xk, xv, W, b, pos_q, pos_k, residual)
+    if pos is not None and pos.shape != x.shape:
+        raise RuntimeError(f"{name}: pos {tuple(pos.shape)} must have the shape of the input {tuple(x.shape)}")
+
+
+def in_proj_q(x, W, b, pos=None, residual=False):
+    _in_proj_checks("in_proj_q", W, b, x, pos)
+    return _InProjQ.apply(x, W, b, pos, residual)
+
+
+def in_proj_kv(x, W, b, pos=None, outs=None):
+    _in_proj_checks("in_proj_kv", W, b, x, pos)
+    return _InProjKV.apply(x, x, W, b, pos, outs)
+
+
+def in_proj(xq, xk, xv, W, b, pos_q=None, pos_k=None, residual=False):
+    """-> q, k, v (residual: and xq routed through the query's node).  One input for all three and one positional term
+    (or none) for q and k: the self form; everything else: the query node and the key / value node."""
+    _in_proj_checks("in_proj (query)", W, b, xq, pos_q)
+    _in_proj_checks("in_proj (key)", W, b, xk, pos_k)
+    if _same_tensor(xq, xk) and _same_tensor(xk, xv) and (pos_q is None) == (pos_k is None) \
+            and (pos_q is None or _same_tensor(pos_q, pos_k)):
+        return _InProjSelf.apply(xq, W, b, pos_q, residual)
+    q = _InProjQ.apply(xq, W, b, pos_q, residual)
+    k, v = _InProjKV.apply(xk, xv, W, b, pos_k, None)
+    return (q[0], k, v, q[1]) if residual else (q, k, v)
 
 
 ATTN_MAX_QUERIES = int(lib.usc_attn_max_queries())    # queries the fused attention and key-sampling kernels take (256)
