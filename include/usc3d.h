@@ -601,6 +601,17 @@ int32_t usc_step_size(void);
 /* Scratch bytes that cover every step of the program (the steps run one after the other on one stream). */
 int64_t usc_program_ws_bytes(const usc_step* steps, int32_t n_steps);
 int usc_program_run(const usc_step* steps, int32_t begin, int32_t end, void* ws, int64_t ws_bytes, usc_stream_t s);
+/* Steps [begin, end) of a backward program issued ON the weight-gradient lane (usc_set_wgrad_lane; an error without one):
+ * the lane waits behind one event of `s`, then runs the units' input-gradient chain, then — behind an event of its own,
+ * "the chain is done" — every weight gradient of the range (those the lane takes are noted while the chain is issued,
+ * as under usc_wgrad_lane_hold, and released behind it).  `s` does not wait for anything: a later
+ * usc_wgrad_lane_wait_chain(s) puts `s` behind the chain only (whoever continues the program from the range's input
+ * gradients), usc_wgrad_lane_join(s) behind everything.  For a range whose gradients do not depend on what `s` is about
+ * to run: the finest U-Net stage beside the mask decoder's backward.  ws: scratch of the range's own
+ * (usc_program_ws_bytes), neither the lane's nor one that other streams use meanwhile.  A hold in force is released
+ * first.  Same kernels and the same results as usc_program_run on `s`. */
+int usc_program_run_lane(const usc_step* steps, int32_t begin, int32_t end, void* ws, int64_t ws_bytes, usc_stream_t s);
+int usc_wgrad_lane_wait_chain(usc_stream_t s);
 
 /* ------------------------------------------------------------------------
  * B  row-wise batch norm / ReLU / residual — replaces [ME] MinkowskiBatchNorm
@@ -953,6 +964,13 @@ int usc_linear_bwd_ex(const float* dy, const float* y_relu, const float* x,
 int usc_linear_bwd_ex2(const float* dy, const float* y_relu, const float* x, const float* x2, const float* W, int32_t M,
                        int32_t N, int32_t K, float* dx, const float* dx_add, const float* dx_add2, float* dx_b, float* dW,
                        float* db, int32_t accumulate, usc_stream_t s);
+/* The input gradient of L <= usc_linear_heads_max() linear heads over ONE input in one launch:
+ *   dx[M,K] = P_0 + (P_1 + ( ... + P_{L-1})),  P_l = dy[l] [M,N] W[l] [N,K]   (dy, W: host arrays of L device pointers)
+ * — the 13 mask-logit products of a training step over the segment table (models/mask3d.py:425,430).  The bits of the
+ * chain usc_linear_bwd_ex(dy[l], ..., dx_add = the sum so far), last head first. */
+int32_t usc_linear_heads_max(void);
+int usc_linear_heads_dx(const float* const* dy, const float* const* W, int32_t L, int32_t M, int32_t N, int32_t K, float* dx,
+                        usc_stream_t s);
 /* Backward of usc_linear_fwd_split for the self-attention projections (split_cols = E, N = 3E, x2_cols = 2E), one launch:
  * dy3 [3][M][E] = dq | dk | dv;  dx = dq Wq + dk Wk + dv Wv (+ dres: the block's residual path);  dx_b (optional) =
  * dq Wq + dk Wk, the positional term's gradient;  dW [3E][E] and db [3E] written or (accumulate) added to, with the

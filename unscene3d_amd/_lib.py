@@ -107,6 +107,8 @@ SIGNATURES = {
     "usc_step_size": (_i32, []),
     "usc_program_ws_bytes": (_i64, [_sp, _i32]),
     "usc_program_run": (C.c_int, [_sp, _i32, _i32, _p, _i64, _p]),
+    "usc_program_run_lane": (C.c_int, [_sp, _i32, _i32, _p, _i64, _p]),
+    "usc_wgrad_lane_wait_chain": (C.c_int, [_p]),
     "usc_spconv_wgrad_group_max": (_i32, []),
     "usc_spconv_wgrad_grid_limit": (None, [_i32]),
     "usc_spconv_wgrad_group_ok": (C.c_int, [_i32, _i32, _i32, _i32, _i64]),
@@ -212,6 +214,8 @@ SIGNATURES = {
     "usc_linear_bwd_ex": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _p]),
     "usc_qkv_proj_bwd": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p]),
     "usc_linear_bwd_ex2": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _p]),
+    "usc_linear_heads_max": (_i32, []),
+    "usc_linear_heads_dx": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "usc_layernorm_bwd_ws_bytes": (_i64, [_i64, _i32]),
     "usc_layernorm_bwd": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _i32, _p, _i64, _p]),
     "usc_layernorm_bwd_ex": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _p, _i64, _p]),

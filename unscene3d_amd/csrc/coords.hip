@@ -223,7 +223,7 @@ using namespace usc;
 extern "C" {
 
 const char* usc_last_error(void) { return g_err; }
-int usc_abi_version(void) { return 4; }   // 4: usc_attn_max_queries / usc_attn_lse_stride; attention and key sampling take <= 256 queries
+int usc_abi_version(void) { return 5; }   // 5: usc_program_run_lane / usc_wgrad_lane_wait_chain, usc_linear_heads_dx
 
 int usc_device_count(void) {
   int n = 0;

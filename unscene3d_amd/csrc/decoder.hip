@@ -326,11 +326,11 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict
 // dx_add (optional, [M,K]): added to the result (the other gradient path into the same input);
 // dx_b (optional, [M,K]): also receives dy W + dx_add, while dx receives dy W + dx_add + dx_add2 — the product feeds
 // two gradients (the layer input's, which also has a residual path, and the positional term's, which has not).
+// linear_dx_acc: this wave's share of the tile's reduction (its chunks of N, in order); linear_dx_tile sums the four
+// shares and stores.
 template <bool EX>
-__device__ inline void linear_dx_tile(const float* __restrict__ dy, const float* __restrict__ ymask,
-                                      const float* __restrict__ W, int M, int N, int K, float* __restrict__ dx,
-                                      const float* __restrict__ dx_add, const float* __restrict__ dx_add2,
-                                      float* __restrict__ dx_b, int c0, int m0, float (*red)[16][64]) {
+__device__ inline f32x16 linear_dx_acc(const float* __restrict__ dy, const float* __restrict__ ymask,
+                                       const float* __restrict__ W, int M, int N, int K, int c0, int m0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
   const int m = m0 + i;
   const float* ya = dy + (int64_t)(m < M ? m : 0) * N + 4 * h;
@@ -375,6 +375,15 @@ __device__ inline void linear_dx_tile(const float* __restrict__ dy, const float*
       for (int j = 0; j < 4; ++j) acc = MFMA32(av[j], bv[4 * t + j], acc);
     }
   }
+  return acc;
+}
+template <bool EX>
+__device__ inline void linear_dx_tile(const float* __restrict__ dy, const float* __restrict__ ymask,
+                                      const float* __restrict__ W, int M, int N, int K, float* __restrict__ dx,
+                                      const float* __restrict__ dx_add, const float* __restrict__ dx_add2,
+                                      float* __restrict__ dx_b, int c0, int m0, float (*red)[16][64]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const f32x16 acc = linear_dx_acc<EX>(dy, ymask, W, M, N, K, c0, m0);
   tile_reduce_store(acc, red, wave, lane, dx, K, m0, c0, M, nullptr, 0, 0, EX ? dx_add : nullptr,
                     EX ? dx_add2 : nullptr, EX ? dx_b : nullptr);
 }
@@ -550,6 +559,40 @@ __global__ __launch_bounds__(256) void qkv_bwd_kernel(const float* __restrict__ 
   }
 }
 
+// ---- the input gradient of L linear heads over ONE input, in ONE launch ------------------------------------------------
+//   dx[M,K] = P_0 + (P_1 + ( ... + P_{L-1})),   P_l = dy_l[M,N] W_l[N,K]
+// The 13 mask-logit products of a training step read the same segment table (models/mask3d.py:425,430); as a chain of
+// linear_bwd launches the sum came out of L dependent launches, each adding its predecessor's result as dx_add.  Here a
+// workgroup keeps its tile's running sum in registers: the same per-wave chunk order (linear_dx_acc), the same wave-order
+// reduction and the same association, last head first — the bits of the chain.
+constexpr int kMaxHeads = 16;
+struct HeadPtrs { const float* dy[kMaxHeads]; const float* W[kMaxHeads]; };
+
+__global__ __launch_bounds__(256) void linear_heads_dx_kernel(HeadPtrs hp, int L, int M, int N, int K,
+                                                             float* __restrict__ dx) {
+  __shared__ float red[4][16][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
+  const int kt = K / 32;
+  const int c0 = ((int)blockIdx.x % kt) * 32, m0 = ((int)blockIdx.x / kt) * 32;
+  float run[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int l = L - 1; l >= 0; --l) {
+    const f32x16 acc = linear_dx_acc<false>(hp.dy[l], nullptr, hp.W[l], M, N, K, c0, m0);
+    float v[4];
+    tile_reduce4(acc, red, wave, lane, v);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float o = v[q] + 0.f + 0.f;           // (tile_reduce_store's absent bias and accumulate terms)
+      if (l < L - 1) o += run[q];
+      run[q] = o;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int row = m0 + acc_row16(4 * wave + q, h);
+    if (row < M) dx[(int64_t)row * K + c0 + i] = run[q];
+  }
+}
+
 // Column sums of a many-row table (the bias gradient of a linear layer over 3 200 / 12 800 sampled voxels), in a fixed
 // order: 64-row partial sums, then per column 16 lanes add the partials ascending and their sums are added ascending.  No atomics, no
 // last-block semaphores: the same bits on every launch and inside captured graphs.
@@ -676,6 +719,25 @@ int usc_qkv_proj_bwd(const float* dy3, const float* x, const float* pos, const f
   hipLaunchKernelGGL(usc::qkv_bwd_kernel, dim3(dx_tiles + dw_tiles), dim3(256), 0, usc::as_stream(s), dy3, x, pos, W, (int)M,
                      (int)E, dx_tiles, (int)accumulate, dx, dx_b, dres, dW, db);
   USC_CHECK_LAUNCH("usc_qkv_proj_bwd");
+  return USC_OK;
+}
+
+int32_t usc_linear_heads_max(void) { return usc::kMaxHeads; }
+
+int usc_linear_heads_dx(const float* const* dy, const float* const* W, int32_t L, int32_t M, int32_t N, int32_t K, float* dx,
+                        usc_stream_t s) {
+  USC_REQUIRE(L >= 1 && L <= usc::kMaxHeads, "usc_linear_heads_dx: 1 <= L <= %d heads", usc::kMaxHeads);
+  USC_REQUIRE(M >= 1 && N >= 32 && N % 32 == 0 && K >= 32 && K % 32 == 0, "usc_linear_heads_dx: N, K must be multiples of 32");
+  USC_REQUIRE(dy && W && dx, "usc_linear_heads_dx: null pointer");
+  usc::HeadPtrs hp{};
+  for (int l = 0; l < L; ++l) {
+    USC_REQUIRE(dy[l] && W[l], "usc_linear_heads_dx: null pointer (head %d)", l);
+    hp.dy[l] = dy[l];
+    hp.W[l] = W[l];
+  }
+  hipLaunchKernelGGL(usc::linear_heads_dx_kernel, dim3((K / 32) * ((M + 31) / 32)), dim3(256), 0, usc::as_stream(s), hp,
+                     (int)L, (int)M, (int)N, (int)K, dx);
+  USC_CHECK_LAUNCH("usc_linear_heads_dx");
   return USC_OK;
 }
 

@@ -154,11 +154,14 @@ int issue_wgrad(const WgradJob& j, int accumulate, void* ws, int64_t ws_bytes, u
 // returns; the input-gradient chain — the critical path of the backward pass — carries on, and the latency-bound
 // weight-gradient launches of the coarse levels fill the CUs it leaves idle.  The caller joins once, when the
 // gradients are needed (usc_wgrad_lane_join), keeps x / dy / dW alive until then, and gives the lane its own scratch.
-struct Lane { hipStream_t st = nullptr; hipEvent_t fork = nullptr, join = nullptr; void* ws = nullptr; int64_t ws_bytes = 0;
+struct Lane { hipStream_t st = nullptr; hipEvent_t fork = nullptr, join = nullptr, chain = nullptr; void* ws = nullptr; int64_t ws_bytes = 0;
               int64_t max_rows = 0; bool dirty = false;
               // hold: weight gradients of maps with >= hold_min_rows rows are only NOTED until the caller's chain reaches a map
               // with <= release_max_rows rows (or the hold is lifted); from then on everything goes to the lane at once
-              bool hold = false; int64_t hold_min_rows = 0, release_max_rows = 0; std::vector<WgradJob> held; };
+              bool hold = false; int64_t hold_min_rows = 0, release_max_rows = 0; std::vector<WgradJob> held;
+              // chain: recorded on the lane behind the input-gradient chain of a range issued ON the lane
+              // (usc_program_run_lane), in front of that range's weight gradients
+              bool chain_set = false; };
 Lane g_lane[16];
 Lane* lane_for_current_device() {
   int dev = 0;
@@ -585,12 +588,14 @@ int usc_set_wgrad_lane(usc_stream_t lane, void* lane_ws, int64_t lane_ws_bytes, 
     e.st = nullptr;
     e.held.clear();
     e.hold = false;
+    e.chain_set = false;
     return USC_OK;
   }
   USC_REQUIRE(lane_ws && lane_ws_bytes > 0 && max_rows > 0, "usc_set_wgrad_lane: the lane needs its own scratch and a row bound");
   if (!e.fork) {
     if (hipEventCreateWithFlags(&e.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&e.join, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&e.join, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&e.chain, hipEventDisableTiming) != hipSuccess) {
       set_error("usc_set_wgrad_lane: hipEventCreate failed");
       return USC_ERR_LAUNCH;
     }
@@ -600,6 +605,7 @@ int usc_set_wgrad_lane(usc_stream_t lane, void* lane_ws, int64_t lane_ws_bytes, 
   e.ws_bytes = lane_ws_bytes;
   e.max_rows = max_rows;
   e.dirty = false;
+  e.chain_set = false;
   return USC_OK;
 }
 
@@ -734,7 +740,11 @@ int32_t usc_step_size(void) { return (int32_t)sizeof(usc_step); }
 // two halves: step i works in half i & 1, so the input-gradient slices a backward step leaves for the next one survive it
 int64_t usc_program_ws_bytes(const usc_step* steps, int32_t n_steps) { return 2 * program_half_bytes(steps, n_steps) + 256; }
 
-int usc_program_run(const usc_step* steps, int32_t begin, int32_t end, void* ws_all, int64_t ws_all_bytes, usc_stream_t s) {
+namespace {
+// chain_done (optional): recorded on `s` behind the last kernel of the units' chain, in front of the weight gradients the
+// call itself deferred
+int program_run_impl(const usc_step* steps, int32_t begin, int32_t end, void* ws_all, int64_t ws_all_bytes, usc_stream_t s,
+                     hipEvent_t chain_done) {
   USC_REQUIRE(steps && begin >= 0 && end >= begin, "usc_program_run: bad step range");
   hipStream_t st = as_stream(s);
   DeferredWgrads q;
@@ -816,13 +826,60 @@ int usc_program_run(const usc_step* steps, int32_t begin, int32_t end, void* ws_
         rc = USC_ERR_ARG;
     }
   }
-  const int rc3 = flush_pending(pend, s);
+  int rc3 = flush_pending(pend, s);
+  if (chain_done && !rc && !rc3 && hipEventRecord(chain_done, st) != hipSuccess) {
+    set_error("usc_program_run_lane: recording the chain's event failed");
+    rc3 = USC_ERR_LAUNCH;
+  }
   // the queued weight gradients last: with two halves, the one the pending slices (just reduced, in stream order) were not in
   const int rc2 = flush_deferred(q, ws, ws_bytes, s);
   if (rc) return rc;
   if (rc3) return rc3;
   if (rc2) return rc2;
   USC_CHECK_LAUNCH("usc_program_run");
+  return USC_OK;
+}
+}  // namespace
+
+int usc_program_run(const usc_step* steps, int32_t begin, int32_t end, void* ws_all, int64_t ws_all_bytes, usc_stream_t s) {
+  return program_run_impl(steps, begin, end, ws_all, ws_all_bytes, s, nullptr);
+}
+
+int usc_program_run_lane(const usc_step* steps, int32_t begin, int32_t end, void* ws, int64_t ws_bytes, usc_stream_t s) {
+  Lane* lane = lane_for_current_device();
+  USC_REQUIRE(lane, "usc_program_run_lane: no weight-gradient lane on this device (usc_set_wgrad_lane)");
+  USC_REQUIRE(ws != lane->ws, "usc_program_run_lane: the range needs scratch of its own, not the lane's");
+  const usc_stream_t ls = (usc_stream_t)lane->st;
+  // what an earlier hold noted goes first, behind the caller's stream as usual
+  if (!lane->held.empty() || lane->hold) { const int rc = lane_release(lane, s); if (rc) return rc; }
+  if (as_stream(s) != lane->st &&
+      (hipEventRecord(lane->fork, as_stream(s)) != hipSuccess || hipStreamWaitEvent(lane->st, lane->fork, 0) != hipSuccess)) {
+    set_error("usc_program_run_lane: putting the lane behind the caller's stream failed (event)");
+    return USC_ERR_LAUNCH;
+  }
+  // the chain first: every weight gradient the lane would take is noted and goes behind the chain's event
+  lane->hold = true;
+  lane->hold_min_rows = 0;
+  lane->release_max_rows = -1;
+  lane->dirty = true;
+  lane->chain_set = false;
+  int rc = program_run_impl(steps, begin, end, ws, ws_bytes, ls, lane->chain);
+  if (rc) {                                   // nothing stays noted after a failed range
+    lane->held.clear();
+    lane->hold = false;
+    return rc;
+  }
+  lane->chain_set = true;
+  return lane_release(lane, ls);
+}
+
+int usc_wgrad_lane_wait_chain(usc_stream_t s) {
+  Lane* lane = lane_for_current_device();
+  USC_REQUIRE(lane && lane->chain_set, "usc_wgrad_lane_wait_chain: no range has been issued on the lane (usc_program_run_lane)");
+  if (as_stream(s) != lane->st && hipStreamWaitEvent(as_stream(s), lane->chain, 0) != hipSuccess) {
+    set_error("usc_wgrad_lane_wait_chain: waiting for the chain's event failed");
+    return USC_ERR_LAUNCH;
+  }
   return USC_OK;
 }
 

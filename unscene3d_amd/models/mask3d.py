@@ -320,11 +320,18 @@ class Mask3D(nn.Module):
                                            is_eval=is_eval)
         coordinates, coords, pos_encodings_pcd = geo["coordinates"], geo["coords"], geo["pos_encodings_pcd"]
 
-        mask_features = self.mask_features_head(pcd_features)
+        # the last U-Net stage's backward ahead of the decoder's (_EarlyStageGate): the mask head and the segment means then
+        # take no part in autograd — the gate issues their backward itself, on the lane
+        early = self._early_stage(pcd_features, aux, point2segment)
+        with (torch.no_grad() if early is not None else contextlib.nullcontext()):
+            mask_features = self.mask_features_head(pcd_features)
         mask_segments, seg_csr = None, None
         if self.train_on_segments:
             seg_csr = geo["seg_csr"]
-            if self.scatter_type == "mean":
+            if early is not None:
+                with torch.no_grad():
+                    mask_segments = [ops.segment_mean(f, csr) for f, csr in zip(mask_features.decomposed_features, seg_csr)]
+            elif self.scatter_type == "mean":
                 mask_segments = [ops.segment_mean(f, csr) for f, csr in zip(mask_features.decomposed_features, seg_csr)]
             else:
                 # scatter_type 'max' (reference :66-67, :223: torch_scatter.scatter_max(...)[0]; not used by the shipped
@@ -473,6 +480,8 @@ class Mask3D(nn.Module):
                                                       point2segment=p2s_arg, coords=coords, defer_class=True)
         predictions_class.append(output_class)
         predictions_mask.append(outputs_mask)
+        if early is not None:
+            predictions_mask = _early_stage_gate(self, early, pcd_features, mask_features, seg_csr, predictions_mask)
         # the class head over every call's normalised queries at once (reference :428 per call)
         predictions_class = list(self.class_embed_head(torch.stack(predictions_class)).unbind(0))
 
@@ -483,6 +492,31 @@ class Mask3D(nn.Module):
             "sampled_coords": _host_array(sampled_coords) if sampled_coords is not None else None,
             "backbone_features": pcd_features,
         }
+
+    def _early_stage(self, pcd_features, aux, point2segment):
+        """-> the trunk's handle (program.TrunkHandle) when this step may run the finest U-Net stage's backward beside the
+        decoder's, else None.  The gradient of the s1 output must not depend on the decoder layers' backward: the s1 map is
+        no key level, the queries take nothing from it (use_np_features off), the attention masks are detached — what is left
+        is mask head -> segment mean -> the mask-logit products, whose gradients the criterion hands back at once."""
+        from .. import program
+        feats = pcd_features.F
+        handle = program.handle_of(feats)
+        if not (self.training and torch.is_grad_enabled() and self.train_on_segments and self.scatter_type == "mean"
+                and not self.use_np_features and point2segment is not None and feats.is_cuda
+                and feats.dtype == torch.float32 and self.mask_dim % 32 == 0 and (len(aux) - 1) not in self.hlevels
+                and program.early_possible(handle)):
+            return None
+        head = self.mask_features_head
+        bias = head.bias
+        if head.kernel_volume != 1 or head.stride != 1 or ops._grad_target(head.kernel) is None:
+            return None
+        if bias is not None and (not bias.requires_grad or bias.grad is None or bias._backward_hooks
+                                 or getattr(bias, "_post_accumulate_grad_hooks", None)):
+            return None
+        cm = pcd_features.coordinate_manager
+        if not all(isinstance(sl, slice) for sl in cm.batch_slices(pcd_features._ts())):
+            return None
+        return handle
 
     def _norm_queries(self, queries):
         """decoder_norm(queries) for mask_module AND the queries for the next decoder layer as outputs of ONE autograd
@@ -675,15 +709,99 @@ def _mask_logits(feats, mask_embed, chain=False):
         pad = (-Q) % 32
         W = F.pad(mask_embed, (0, 0, 0, pad)) if pad else mask_embed
     nxt = feats
+    Wc = W.contiguous()
     if chain and feats.requires_grad and torch.is_grad_enabled():
-        out, nxt = ops.linear(feats, W.contiguous(), passthrough=True)
+        out, nxt = ops.linear(feats, Wc, passthrough=True)
     else:
-        out = ops.linear(feats, W.contiguous())
+        out = ops.linear(feats, Wc)
     if pad:
         view = out[:, :Q]
         view._usc_padded = out        # the device criterion reads (and differentiates) the padded table directly
         out = view
+    out._usc_embed = Wc               # the head's weights as the launch read them (_early_stage_gate)
     return (out, nxt) if chain else out
+
+
+EARLY_STAGE_STEPS = 0       # training steps whose finest U-Net stage ran its backward ahead (tests, tools)
+
+
+class _EarlyStageGate(torch.autograd.Function):
+    """The mask-logit tables of all mask_module calls pass through unchanged.  Created behind the last call, its backward
+    runs before any decoder layer's and holds every table's gradient: `run` issues what depends on nothing else (the heads'
+    input gradient, the segment means', the mask head's, the finest U-Net stage's) on the lane."""
+
+    @staticmethod
+    def forward(ctx, run, *tables):
+        ctx.run = run
+        return tables
+
+    @staticmethod
+    def backward(ctx, *grads):
+        run, ctx.run = ctx.run, None
+        run(grads)
+        return (None,) + grads
+
+
+def _early_stage_gate(model, handle, pcd_features, mask_features, seg_csr, predictions_mask):
+    """predictions_mask (per mask_module call, per scene: the [S, Q] logits) behind an _EarlyStageGate -> the same lists."""
+    from .. import program, units
+    tables, embeds, where = [], [], []
+    for c, per_scene in enumerate(predictions_mask):
+        for i, o in enumerate(per_scene):
+            if getattr(o, "_usc_embed", None) is None:
+                raise RuntimeError("early stage: a mask-logit table did not come from the device product")
+            tables.append(getattr(o, "_usc_padded", o))
+            embeds.append(o._usc_embed.detach())
+            where.append((c, i, o.shape[1]))
+    n_scenes = len(seg_csr)
+    head = model.mask_features_head
+    x = pcd_features.F
+    slices = pcd_features.coordinate_manager.batch_slices(pcd_features._ts())
+    d = mask_features.F.shape[1]
+    dev = x.device
+
+    def run(grads):
+        global EARLY_STAGE_STEPS
+        lane = units._lane(dev)[0]
+        ready = torch.cuda.Event()
+        ready.record()                       # every table's gradient exists on the backward pass's stream
+        lane.wait_event(ready)
+        grads = [g.contiguous() for g in grads]
+        # (the segment tables come from the prefetch stream's pool, which knows nothing of the lane's reads)
+        for t in grads + embeds + [t for csr in seg_csr for t in (csr.seg, csr.seg_off)]:
+            t.record_stream(lane)
+        with torch.cuda.stream(lane), torch.no_grad():
+            dmask = torch.empty((x.shape[0], d), dtype=torch.float32, device=dev)
+            kept = [grads, embeds, dmask]
+            for i in range(n_scenes):
+                mine = [k for k, w in enumerate(where) if w[1] == i]
+                dseg = ops.linear_heads_dx([grads[k] for k in mine], [embeds[k] for k in mine])
+                csr = seg_csr[i]
+                rows = dmask[slices[i]]
+                ops.check(ops.lib.usc_segment_mean_bwd(dseg.data_ptr(), d, csr.seg.data_ptr(), csr.seg_off.data_ptr(),
+                                                       rows.shape[0], rows.data_ptr(), ops._stream()), "usc_segment_mean_bwd")
+                kept.extend((dseg, csr))
+            # the 1x1 mask head, as ops._ConvSame.backward issues it
+            W = head.kernel
+            W3 = (W if W.dim() == 3 else W[None]).contiguous()
+            dfeats = ops.gather_gemm(dmask, ops.weight_transpose(W3, mirror=False), None, x.shape[0])
+            ops.wgrad(x, dmask, 1, into=ops._grad_target(W))
+            ops._grad_written(W)
+            if head.bias is not None:
+                head.bias.grad.add_(ops.colsum(dmask).view_as(head.bias.grad))
+            kept.extend((x, W3, dfeats))
+            program.early_backward(handle, dfeats, keep=kept)
+        EARLY_STAGE_STEPS += 1
+
+    outs = _EarlyStageGate.apply(run, *tables)
+    result = [list(per_scene) for per_scene in predictions_mask]
+    for t, (c, i, q) in zip(outs, where):
+        if t.shape[1] != q:
+            view = t[:, :q]
+            view._usc_padded = t
+            t = view
+        result[c][i] = t
+    return result
 
 
 def multihead_attention(mha: nn.MultiheadAttention, query, key, value, attn_mask=None, pos_q=None, pos_k=None,

@@ -1413,6 +1413,36 @@ def _lin_bwd(dy2, x2, W, dW_out, db_out, need_dx=True, accumulate=False, add=Non
     return dy2 @ W
 
 
+def linear_heads_dx(dys, Ws):
+    """dx [M,K] = P_0 + (P_1 + ( ... + P_{L-1})), P_l = dys[l] [M,N] @ Ws[l] [N,K]: the input gradient of L linear heads
+    over one input (the mask-logit products over the segment table) without the L-long chain of
+    `linear(..., passthrough=True)` nodes — and with its bits: one launch on the few-row kernels
+    (usc_linear_heads_dx), head by head on the kernels the chain takes above SMALL_ROWS."""
+    L = len(dys)
+    M, N = dys[0].shape
+    K = Ws[0].shape[1]
+    for dy, W in zip(dys, Ws):
+        _chk(dy, torch.float32, "dy")
+        _chk(W, torch.float32, "W")
+        if tuple(dy.shape) != (M, N) or tuple(W.shape) != (N, K):
+            raise RuntimeError("linear_heads_dx: every head needs dy [M, N] and W [N, K] of the same shape")
+    if _small_linear_ok(M, K, N):
+        if L > lib.usc_linear_heads_max():
+            raise RuntimeError(f"linear_heads_dx: at most {lib.usc_linear_heads_max()} heads in one launch, got {L}")
+        pd = (ctypes.c_void_p * L)(*[dy.data_ptr() for dy in dys])
+        pw = (ctypes.c_void_p * L)(*[W.data_ptr() for W in Ws])
+        dx = torch.empty((M, K), dtype=torch.float32, device=dys[0].device)
+        check(lib.usc_linear_heads_dx(pd, pw, L, M, N, K, _ptr(dx), _stream()), "usc_linear_heads_dx")
+        return dx
+    dx = None
+    rows_ok = _rows_gemm_ok(M, K, N)
+    for l in range(L - 1, -1, -1):                      # what _lin_bwd does for one head of the chain, minus dW
+        W = Ws[l]
+        p = gather_gemm(dys[l], W.view(1, N, K), None, M) if rows_ok and W.is_contiguous() else dys[l] @ W
+        dx = p if dx is None else p.add_(dx)
+    return dx
+
+
 class _LinearRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, b, relu=False, passthrough=False, pad_rows_to=None):

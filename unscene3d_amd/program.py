@@ -139,6 +139,16 @@ def _plan(model):
                     seen.add(id(p))
                     params.append(p)
     pl.params = params
+    # the last U-Net stage (transposed conv onto the finest map, concatenation, blocks): ops[early_from:], see early_backward
+    pl.early_from = None
+    if model._UP:
+        last = (model._UP[-1][0], model._UP[-1][2])
+        k = len(pl.ops)
+        while k > 0 and pl.ops[k - 1]["stage"] in last:
+            k -= 1
+        first = pl.ops[k] if k < len(pl.ops) else None
+        if first is not None and first["t"] == "unit" and first["kind"] == UP and first["x"] == pl.levels[-2]:
+            pl.early_from = k
     return pl
 
 
@@ -228,10 +238,14 @@ def usable(model, x):
     return pl
 
 
+_N_PLAIN_ARGS = 8        # _Trunk.forward's arguments in front of the parameters
+
+
 class _Trunk(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, pl, cm, ts, bf16, split, feats, *params):
+    def forward(ctx, model, pl, cm, ts, bf16, split, holder, feats, *params):
         dev = feats.device
+        settle_abandoned(dev)
         rows = [cm.coord_map(ts << l).n for l in range(pl.n_levels)]
         floats = sum(r * f for r, f in zip(rows, pl.act_floats)) + pl.stat_floats + (pl.n_act + 8) * _ALIGN
         car = _Carver(floats, dev)
@@ -291,10 +305,14 @@ class _Trunk(torch.autograd.Function):
         check(lib.usc_program_run(steps, 0, len(pl.ops), ws.data_ptr(), ws.numel(), ops._stream()), "usc_program_run")
         outs = tuple(car.view(offs[b], rows[pl.bufs[b][0]], pl.bufs[b][1]) for b in pl.levels)
         ctx.state = (model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows, split)
+        ctx.holder = holder
+        if holder is not None:
+            holder.state = ctx.state
         return outs
 
     @staticmethod
     def backward(ctx, *gouts):
+        holder = ctx.holder
         model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows, split = ctx.state
         dev = feats.device
         gar = _Pool(dev, max(rows[0] * 256, 1 << 20))
@@ -303,122 +321,36 @@ class _Trunk(torch.autograd.Function):
             gar.release = lambda p_, n_: None
             car.arena.record_stream(lane[0])
         keep = [g.contiguous() if g is not None else None for g in gouts]
-        G = {}                                   # buffer id -> [pointer, read-only (an incoming gradient tensor), floats]
-        held_dy = []                             # dy buffers the current stage's queued weight gradients still read
-        for b, g in zip(pl.levels, keep):
-            if g is not None:
-                G[b] = [g.data_ptr(), True, g.numel()]
-        steps = (Step * (3 * len(pl.ops) + 8))()
-        ns = 0
-        segments, cur_params, stage = [], [], None       # one C call per U-Net stage: (end step, parameters it finished)
-
-        def add_step(dst, src, n):
-            nonlocal ns
-            st = steps[ns]
-            ns += 1
-            st.op, st.dst, st.a, st.n = STEP_ADD, dst, src, n
-
-        def contribute(bid, numel, can_accumulate):
-            """Where the next contribution to the gradient of buffer `bid` goes -> (pointer, accumulate flag, finish):
-            finish() is called after the producing step has been emitted (fan-in add when the target could not be
-            accumulated into: an incoming gradient tensor is never written, and the pair-list forms only write)."""
-            cur = G.get(bid)
-            if cur is None:
-                p = gar.take(numel)
-                G[bid] = [p, False, numel]
-                return p, 0, None
-            if can_accumulate and not cur[1]:
-                return cur[0], 1, None
-            p = gar.take(numel)
-            if cur[1]:                           # new buffer = this contribution + the incoming gradient; ours from now on
-                def fin(p=p, old=cur[0]):
-                    add_step(p, old, numel)
-                    G[bid] = [p, False, numel]
-            else:
-                def fin(p=p, old=cur[0]):
-                    add_step(old, p, numel)
-                    gar.release(p, numel)
-            return p, 0, fin
-
-        def consumed(bid):
-            """The gradient of buffer `bid` has been read by its producer's backward step: give the range back."""
-            cur = G.pop(bid, None)
-            if cur is not None and not cur[1]:
-                gar.release(cur[0], cur[2])
-
-        for i in range(len(pl.ops) - 1, -1, -1):
-            op = pl.ops[i]
-            if op["stage"] != stage:
-                if stage is not None:
-                    segments.append((ns, cur_params))
-                    cur_params = []
-                    for p_, n_ in held_dy:       # the stage's C call flushes its queued weight gradients before it returns
-                        gar.release(p_, n_)
-                    held_dy = []
-                stage = op["stage"]
-            if op["t"] == "cat":
-                g = G.get(op["out"])
+        early = _take_early(holder)
+        stream = ops._stream()
+        if early is None:
+            walk = _BackwardWalk(ctx.state, gar, {})
+            for b, g in zip(pl.levels, keep):
+                if g is not None:
+                    walk.G[b] = [g.data_ptr(), True, g.numel()]
+            hi = len(pl.ops)
+        else:
+            # the last stage has been issued on the lane (early_backward): the walk continues from its gradient table behind
+            # the event the lane recorded after the stage's chain.  The s1 argument is not used: that stage took its own.
+            check(lib.usc_wgrad_lane_wait_chain(stream), "usc_wgrad_lane_wait_chain")
+            walk = _BackwardWalk(ctx.state, gar, early["G"])
+            for b, g in zip(pl.levels[:-1], keep[:-1]):
                 if g is None:
                     continue
-                n = rows[op["level"]]
-                pa, _, fa = contribute(op["a"], n * op["ca"], False)
-                cur_b = G.get(op["b"])
-                if cur_b is not None and not cur_b[1]:
-                    pb, acc_b, fb = cur_b[0], 1, None
-                else:
-                    pb, acc_b, fb = contribute(op["b"], n * op["cb"], False)
-                st = steps[ns]
-                ns += 1
-                st.op, st.a, st.dst, st.dst2, st.n, st.ca, st.cb, st.accumulate = STEP_SPLIT, g[0], pa, pb, n, op["ca"], \
-                    op["cb"], acc_b
-                for f in (fa, fb):
-                    if f is not None:
-                        f()
-                consumed(op["out"])
-                continue
-            g = G.get(op["out"])
-            if g is None:
-                continue                          # nothing downstream asked for this unit's gradient
-            n_out, n_in, cin, cout = rows[op["lout"]], rows[op["lin"]], op["cin"], op["cout"]
-            pdy = gar.take(n_out * cout)
-            pres, fres = None, None
-            if op["res"] is not None:
-                pres, _, fres = contribute(op["res"], n_out * cout, False)
-            need_dx = op["x"] != pl.input
-            pdx, acc, fdx = (None, 0, None)
-            if need_dx:
-                pdx, acc, fdx = contribute(op["x"], n_in * cin, op["kind"] != DOWN)
-            conv, bn = op["conv"], op["bn"]
-            tW, tg, tb = ops._grad_target(conv.kernel), ops._grad_target(bn.weight), ops._grad_target(bn.bias)
-            if tW is None or tg is None or tb is None:
-                raise RuntimeError("step program: a parameter lost its in-place gradient target between forward and "
-                                   "backward (keep p.grad allocated: optimizer.zero_grad(set_to_none=False))")
-            st = steps[ns]
-            ns += 1
-            st.op, st.kind, st.cin, st.cout = STEP_UNIT_BWD, op["kind"], cin, cout
-            st.map, st.bn = C.addressof(kmaps[i].struct), bnrefs[i][0]
-            st.x, st.W = ptr[op["x"]], conv.kernel.data_ptr()
-            st.y, st.stats = ptr[op["y"]], stats_ptr[i]
-            st.out = ptr[op["out"]] if op["relu"] else None
-            st.dout, st.dy, st.dres, st.dx, st.dx_accumulate = g[0], pdy, pres, pdx, acc
-            st.dW, st.dW_accumulate, st.dgamma, st.dbeta, st.dbn_accumulate = tW.data_ptr(), 1, tg.data_ptr(), \
-                tb.data_ptr(), 1
-            st.defer_wgrad = int(units.GROUP_WGRAD)
-            if split:                            # the planes this unit's forward ran in
-                st.split_planes = split.get(i, 0)
-            cur_params.extend((conv.kernel, bn.weight, bn.bias))
-            for f in (fres, fdx):
-                if f is not None:
-                    f()
-            consumed(op["out"])
-            if st.defer_wgrad and op["kind"] == SAME and op["kvol"] > 1:
-                held_dy.append((pdy, n_out * cout))
-            else:
-                gar.release(pdy, n_out * cout)
-        segments.append((ns, cur_params))
+                cur = walk.G.get(b)
+                if cur is None:
+                    walk.G[b] = [g.data_ptr(), True, g.numel()]
+                else:                            # the boundary buffer: the early stage's contribution + the decoder's
+                    walk.add_step(cur[0], g.data_ptr(), g.numel())
+            hi = pl.early_from
+            # the stage's parameters are final, and reported only now: the optimizer's early step waits for an event of
+            # the lane on ITS stream — the key-preparation stream in the shipped loop, which the decoder's backward needs
+            ops._grad_written(*early["params"])
+            ops._params_final(early["params"])
+        walk.emit(hi, 0)
+        steps, ns, segments = walk.steps, walk.ns, walk.segments
         wsb = lib.usc_program_ws_bytes(steps, ns)
         ws = units.workspace(wsb, dev)
-        stream = ops._stream()
         begin = 0
         # the lane's schedule (usc_wgrad_lane_hold): the fine decoder stages' weight gradients are noted, not launched,
         # until the walk reaches a stage whose maps cannot fill the chip; their parameters are reported then
@@ -451,8 +383,259 @@ class _Trunk(torch.autograd.Function):
             for t in gar.chunks:
                 t.record_stream(lane[0])
             units.queue_lane_join(units._dev_key(dev))
+        if early is not None:
+            _close_early(early, dev)
+        if holder is not None:
+            holder.state = None
         ctx.state = None
-        return (None, None, None, None, None, None, None) + (None,) * len(pl.params)
+        return (None,) * _N_PLAIN_ARGS + (None,) * len(pl.params)
+
+
+class _BackwardWalk:
+    """The reverse walk over the plan as backward steps: the units' backward steps, column splits for the concatenations and
+    fan-in adds where a tensor has several consumers.  `G`: buffer id -> [pointer, read-only (an incoming gradient tensor),
+    floats] — the gradient table, which a walk over the first part of the plan hands to the walk over the rest
+    (early_backward).  `segments`: one (end step, parameters it finished) per U-Net stage."""
+
+    def __init__(self, state, gar, G):
+        self.state, self.gar, self.G = state, gar, G
+        pl = state[1]
+        self.steps = (Step * (3 * len(pl.ops) + 8))()
+        self.ns = 0
+        self.segments = []
+
+    def add_step(self, dst, src, n):
+        st = self.steps[self.ns]
+        self.ns += 1
+        st.op, st.dst, st.a, st.n = STEP_ADD, dst, src, n
+
+    def emit(self, hi, lo):
+        """Steps of pl.ops[lo:hi], last first."""
+        model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows, split = self.state
+        G, gar, steps, add_step = self.G, self.gar, self.steps, self.add_step
+        held_dy = []                             # dy buffers the current stage's queued weight gradients still read
+        cur_params, stage = [], None
+
+        def contribute(bid, numel, can_accumulate):
+            """Where the next contribution to the gradient of buffer `bid` goes -> (pointer, accumulate flag, finish):
+            finish() is called after the producing step has been emitted (fan-in add when the target could not be
+            accumulated into: an incoming gradient tensor is never written, and the pair-list forms only write)."""
+            cur = G.get(bid)
+            if cur is None:
+                p = gar.take(numel)
+                G[bid] = [p, False, numel]
+                return p, 0, None
+            if can_accumulate and not cur[1]:
+                return cur[0], 1, None
+            p = gar.take(numel)
+            if cur[1]:                           # new buffer = this contribution + the incoming gradient; ours from now on
+                def fin(p=p, old=cur[0]):
+                    add_step(p, old, numel)
+                    G[bid] = [p, False, numel]
+            else:
+                def fin(p=p, old=cur[0]):
+                    add_step(old, p, numel)
+                    gar.release(p, numel)
+            return p, 0, fin
+
+        def consumed(bid):
+            """The gradient of buffer `bid` has been read by its producer's backward step: give the range back."""
+            cur = G.pop(bid, None)
+            if cur is not None and not cur[1]:
+                gar.release(cur[0], cur[2])
+
+        for i in range(hi - 1, lo - 1, -1):
+            op = pl.ops[i]
+            if op["stage"] != stage:
+                if stage is not None:
+                    self.segments.append((self.ns, cur_params))
+                    cur_params = []
+                    for p_, n_ in held_dy:       # the stage's C call flushes its queued weight gradients before it returns
+                        gar.release(p_, n_)
+                    held_dy = []
+                stage = op["stage"]
+            if op["t"] == "cat":
+                g = G.get(op["out"])
+                if g is None:
+                    continue
+                n = rows[op["level"]]
+                pa, _, fa = contribute(op["a"], n * op["ca"], False)
+                cur_b = G.get(op["b"])
+                if cur_b is not None and not cur_b[1]:
+                    pb, acc_b, fb = cur_b[0], 1, None
+                else:
+                    pb, acc_b, fb = contribute(op["b"], n * op["cb"], False)
+                st = steps[self.ns]
+                self.ns += 1
+                st.op, st.a, st.dst, st.dst2, st.n, st.ca, st.cb, st.accumulate = STEP_SPLIT, g[0], pa, pb, n, op["ca"], \
+                    op["cb"], acc_b
+                for f in (fa, fb):
+                    if f is not None:
+                        f()
+                consumed(op["out"])
+                continue
+            g = G.get(op["out"])
+            if g is None:
+                continue                          # nothing downstream asked for this unit's gradient
+            n_out, n_in, cin, cout = rows[op["lout"]], rows[op["lin"]], op["cin"], op["cout"]
+            pdy = gar.take(n_out * cout)
+            pres, fres = None, None
+            if op["res"] is not None:
+                pres, _, fres = contribute(op["res"], n_out * cout, False)
+            need_dx = op["x"] != pl.input
+            pdx, acc, fdx = (None, 0, None)
+            if need_dx:
+                pdx, acc, fdx = contribute(op["x"], n_in * cin, op["kind"] != DOWN)
+            conv, bn = op["conv"], op["bn"]
+            tW, tg, tb = ops._grad_target(conv.kernel), ops._grad_target(bn.weight), ops._grad_target(bn.bias)
+            if tW is None or tg is None or tb is None:
+                raise RuntimeError("step program: a parameter lost its in-place gradient target between forward and "
+                                   "backward (keep p.grad allocated: optimizer.zero_grad(set_to_none=False))")
+            st = steps[self.ns]
+            self.ns += 1
+            st.op, st.kind, st.cin, st.cout = STEP_UNIT_BWD, op["kind"], cin, cout
+            st.map, st.bn = C.addressof(kmaps[i].struct), bnrefs[i][0]
+            st.x, st.W = ptr[op["x"]], conv.kernel.data_ptr()
+            st.y, st.stats = ptr[op["y"]], stats_ptr[i]
+            st.out = ptr[op["out"]] if op["relu"] else None
+            st.dout, st.dy, st.dres, st.dx, st.dx_accumulate = g[0], pdy, pres, pdx, acc
+            st.dW, st.dW_accumulate, st.dgamma, st.dbeta, st.dbn_accumulate = tW.data_ptr(), 1, tg.data_ptr(), \
+                tb.data_ptr(), 1
+            st.defer_wgrad = int(units.GROUP_WGRAD)
+            if split:                            # the planes this unit's forward ran in
+                st.split_planes = split.get(i, 0)
+            cur_params.extend((conv.kernel, bn.weight, bn.bias))
+            for f in (fres, fdx):
+                if f is not None:
+                    f()
+            consumed(op["out"])
+            if st.defer_wgrad and op["kind"] == SAME and op["kvol"] > 1:
+                held_dy.append((pdy, n_out * cout))
+            else:
+                gar.release(pdy, n_out * cout)
+        self.segments.append((self.ns, cur_params))
+
+
+# ---- the last U-Net stage ahead of the rest ----------------------------------------------------------------------------
+# The backward of the last stage (the transposed convolution onto the stride-1 map, the skip concatenation, the blocks at
+# that width) needs the gradient of the s1 output and nothing else.  A caller that has that gradient before autograd
+# reaches the trunk's node — models/mask3d.py: it is the sum of the mask heads' input gradients, which the criterion hands
+# back all at once — issues that stage on the weight-gradient lane (usc_program_run_lane) while the compute stream goes
+# through the decoder's backward; _Trunk.backward then continues from the stage's gradient table (DESIGN.md §3.24).
+# USC3D_EARLY_STAGE=0: the walk is issued whole by _Trunk.backward, as before.
+EARLY_STAGE = os.environ.get("USC3D_EARLY_STAGE", "1") == "1"
+EARLY_RUNS = 0                  # stages issued ahead so far (tests, tools)
+_EARLY_WS = {}                  # device index -> scratch of the early range (the shared one serves other streams meanwhile)
+_EARLY_OPEN = {}                # device index -> the early state whose continuation has not run yet
+
+
+class TrunkHandle:
+    """What a forward pass of the trunk leaves for early_backward: the node's state, and between early_backward and the
+    node's own backward the stage's gradient table."""
+
+    __slots__ = ("state", "early", "__weakref__")
+
+    def __init__(self):
+        self.state, self.early = None, None
+
+
+def handle_of(s1_features):
+    """The TrunkHandle of the forward pass that produced this stride-1 output (None: not a step program's)."""
+    return getattr(s1_features, "_usc_trunk", None)
+
+
+def early_possible(handle):
+    """May the last stage of this forward pass be issued ahead?  Needs the switch, a lane and no gradient reducer (its
+    bucket order follows the order in which gradients are reported written)."""
+    if not (EARLY_STAGE and handle is not None and handle.state is not None and handle.early is None):
+        return False
+    if ops.GRAD_WRITTEN_HOOK is not None:
+        return False
+    return units._lane(handle.state[4].device) is not None
+
+
+def _early_ws(nbytes, device):
+    key = units._dev_key(device)
+    ws = _EARLY_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _EARLY_WS[key] = torch.empty(int(nbytes * 1.25) + (1 << 20), dtype=torch.uint8, device=device)
+    return ws
+
+
+def early_backward(handle, g_s1, keep=()):
+    """Issue the last stage's backward for the s1 gradient `g_s1` on the lane, behind the current stream (which may be the
+    lane itself); the trunk node's own backward, later in the same backward pass, continues from there.  `keep`: whatever
+    else the lane reads on the caller's behalf, held with the stage's own buffers until the lane has been joined."""
+    global EARLY_RUNS
+    if not early_possible(handle):
+        raise RuntimeError("program.early_backward: not possible for this forward pass (program.early_possible)")
+    model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows, split = handle.state
+    dev = feats.device
+    lane_st = units._lane(dev)[0]
+    key = units._dev_key(dev)
+    settle_abandoned(dev)
+    g = g_s1.contiguous()
+    if tuple(g.shape) != (rows[0], pl.bufs[pl.levels[-1]][1]) or g.dtype != torch.float32:
+        raise RuntimeError("program.early_backward: the gradient does not have the s1 output's shape")
+    # buffers of the stage: a pool of their own, nothing handed out twice (the lane and, behind the chain's event, the
+    # compute stream read them), alive until the lane has been joined
+    gar = _Pool(dev, max(rows[0] * 256, 1 << 20))
+    gar.release = lambda p_, n_: None
+    walk = _BackwardWalk(handle.state, gar, {pl.levels[-1]: [g.data_ptr(), True, g.numel()]})
+    walk.emit(len(pl.ops), pl.early_from)
+    car.arena.record_stream(lane_st)
+    g.record_stream(lane_st)
+    for t in gar.chunks:
+        t.record_stream(lane_st)
+    ws = _early_ws(lib.usc_program_ws_bytes(walk.steps, walk.ns), dev)
+    ws.record_stream(lane_st)
+    state = {"task": ops._graph_task(), "G": walk.G, "keep": [gar, g, walk.steps, ws, handle.state, list(keep)], "key": key,
+             "params": [p for _, plist in walk.segments for p in plist]}
+    _EARLY_OPEN[key] = state
+    try:
+        check(lib.usc_program_run_lane(walk.steps, 0, walk.ns, ws.data_ptr(), ws.numel(), ops._stream()),
+              "usc_program_run_lane")
+    except BaseException:
+        lib.usc_wgrad_lane_hold(-1, 0, 0, None)
+        raise
+    handle.early = state
+    EARLY_RUNS += 1
+    units.queue_lane_join(key)
+
+
+def _take_early(holder):
+    early = None if holder is None else holder.early
+    if early is None:
+        return None
+    holder.early = None
+    if early["task"] >= 0 and early["task"] != ops._graph_task():      # (< 0: issued by a direct call, outside any pass)
+        raise RuntimeError("step program: the last stage was issued ahead in another backward pass than this one")
+    return early
+
+
+def _close_early(early, dev):
+    """The continuation has been issued: the stage's buffers go when the lane has been joined (the join was queued first)."""
+    _EARLY_OPEN.pop(early["key"], None)
+    kept = early["keep"]
+    if ops._graph_task() >= 0:
+        torch.autograd.Variable._execution_engine.queue_callback(kept.clear)
+
+
+def settle_abandoned(device=None):
+    """After a backward pass that raised between early_backward and the trunk's own backward: the lane still runs (or has
+    run) that stage, nobody continued from it and the engine dropped the queued join.  The current stream waits for the
+    lane, nothing stays noted, the stage's gradient table is dropped.  Called by the next forward pass and the next
+    early_backward; a training loop that reuses the gradient buffers after a failed pass calls it before it zeroes them."""
+    key = units._dev_key(device)
+    state = _EARLY_OPEN.pop(key, None)
+    if state is None:
+        return False
+    lib.usc_wgrad_lane_hold(-1, 0, 0, None)
+    with torch.cuda.device(key):
+        units.join_lane()
+    state["G"] = None
+    state["keep"].clear()
+    return True
 
 
 def trunk(model, x):
@@ -484,4 +667,8 @@ def trunk(model, x):
                 if planes:
                     split[i] = planes
         split = split or None
-    return list(_Trunk.apply(model, pl, cm, ts, bf16, split, feats, *pl.params))
+    holder = TrunkHandle() if (EARLY_STAGE and torch.is_grad_enabled() and pl.early_from is not None) else None
+    outs = list(_Trunk.apply(model, pl, cm, ts, bf16, split, holder, feats, *pl.params))
+    if holder is not None and holder.state is not None:
+        outs[-1]._usc_trunk = holder
+    return outs
