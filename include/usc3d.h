@@ -1123,6 +1123,49 @@ int usc_cc_eps_finish(const int32_t* label, int64_t n, int32_t* rank_ws,
                       int64_t* labels, usc_stream_t s);
 
 /* ------------------------------------------------------------------------
+ * E1b DBSCAN of all query masks of one scene in one pass — replaces the loop
+ * over queries around sklearn.cluster.DBSCAN(eps, min_samples).fit(xyz[on])
+ * of trainer/trainer.py:517-533, for any min_samples >= 1 (csrc/dbscan.hip).
+ * Points are binned into cells of side eps / 2; the caller sorts them by cell
+ * key between the calls (ops.dbscan_masks):
+ *   usc_dbscan_cell_keys      replaces nothing in the reference (binning):
+ *       xyz f32[n,3] -> keys i64[n] = (cx*ny + cy)*nz + cz,
+ *       c = floor((x - min) / (eps/2)) in f64; nx, ny, nz <= 2^20.
+ *   usc_dbscan_neighbor_table cell_keys i64[n_cells] ascending and distinct ->
+ *       nbr i32[n_cells,125]: the occupied cell at offset (k/25-2, k/5%5-2,
+ *       k%5-2), or -1.
+ *   usc_dbscan_labels         replaces sklearn.cluster.DBSCAN(...).labels_ per
+ *       query (trainer.py:521-523): xyz_sorted f32[n,3] and order i64[n] (sorted
+ *       position -> original row, ascending inside a cell), cell_of i32[n],
+ *       cell_start i32[n_cells+1], masks f32[n,q] in ORIGINAL row order (on:
+ *       > 0) -> labels i32[n,q] in original row order (sklearn's label on an
+ *       on-point, -1 noise, -2 off) and n_clusters i32[q].  Distances as in
+ *       usc_cc_eps_step: f64 on the f32 coordinates against
+ *       (double)eps*(double)eps.  ws: usc_dbscan_ws_bytes bytes.
+ *   usc_dbscan_expand         replaces the per-cluster mask products of
+ *       trainer.py:525-533: out f32[n,n_cols] (zeroed by the caller),
+ *       out[i, col_start[q] + labels[i,q]] = masks[i,q] where the label >= 0.
+ * ---------------------------------------------------------------------- */
+#define USC_DBSCAN_MAX_CELLS_PER_AXIS (1 << 20)
+int usc_dbscan_cell_keys(const float* xyz, int64_t n, float eps, double min_x,
+                         double min_y, double min_z, int32_t nx, int32_t ny,
+                         int32_t nz, int64_t* keys, usc_stream_t s);
+int usc_dbscan_neighbor_table(const int64_t* cell_keys, int64_t n_cells,
+                              int32_t nx, int32_t ny, int32_t nz, int32_t* nbr,
+                              usc_stream_t s);
+int64_t usc_dbscan_ws_bytes(int64_t n, int32_t q, int64_t n_cells,
+                            int32_t min_samples);
+int usc_dbscan_labels(const float* xyz_sorted, const int64_t* order,
+                      const int32_t* cell_of, const int32_t* cell_start,
+                      const int32_t* nbr, const float* masks, int64_t n,
+                      int32_t q, int64_t n_cells, float eps,
+                      int32_t min_samples, void* ws, int64_t ws_bytes,
+                      int32_t* labels, int32_t* n_clusters, usc_stream_t s);
+int usc_dbscan_expand(const float* masks, const int32_t* labels,
+                      const int64_t* col_start, int64_t n, int32_t q,
+                      int64_t n_cols, float* out, usc_stream_t s);
+
+/* ------------------------------------------------------------------------
  * L3  tri-plane projection — replaces
  * custom_cuda_utils.project_sparse_voxels_to_planes{,_backward}
  * (utils/cuda_utils/cuda_utils.cpp:26-46, cuda_utils_kernel.cu:371-603; wrapper

@@ -170,6 +170,11 @@ SIGNATURES = {
     "usc_cc_eps_init": (C.c_int, [_p, _i64, _p]),
     "usc_cc_eps_step": (C.c_int, [_p, _i64, _f32, _p, _p, _p, _p]),
     "usc_cc_eps_finish": (C.c_int, [_p, _i64, _p, _p, _p]),
+    "usc_dbscan_cell_keys": (C.c_int, [_p, _i64, _f32, _f64, _f64, _f64, _i32, _i32, _i32, _p, _p]),
+    "usc_dbscan_neighbor_table": (C.c_int, [_p, _i64, _i32, _i32, _i32, _p, _p]),
+    "usc_dbscan_ws_bytes": (_i64, [_i64, _i32, _i64, _i32]),
+    "usc_dbscan_labels": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _f32, _i32, _p, _i64, _p, _p, _p]),
+    "usc_dbscan_expand": (C.c_int, [_p, _p, _p, _i64, _i32, _i64, _p, _p]),
     "usc_project_planes_fwd": (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _i32] + [_p] * 10),
     "usc_project_planes_bwd": (C.c_int, [_p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
     "usc_brick_mask_build": (C.c_int, [_p, _i64, _p, _i32, _i32, _i32, _i32, _p, _p]),

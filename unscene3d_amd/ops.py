@@ -1210,6 +1210,78 @@ def cc_eps(xyz: torch.Tensor, eps: float, max_rounds: int = 256) -> torch.Tensor
     return labels
 
 
+DBSCAN_OFF = -2                           # label of a point outside the query's mask (noise is sklearn's -1)
+DBSCAN_MAX_CELLS_PER_AXIS = 1 << 20       # USC_DBSCAN_MAX_CELLS_PER_AXIS
+
+
+def dbscan_masks(xyz: torch.Tensor, masks: torch.Tensor, eps: float, min_samples: int = 1):
+    """sklearn.cluster.DBSCAN(eps, min_samples) of every query mask of one scene in one pass (csrc/dbscan.hip).
+
+    xyz f32[N,3], masks f32[N,Q] (on: > 0) -> (labels i32[N,Q], n_clusters i32[Q]).  An on-point carries the label
+    sklearn gives it among the on-points of its query (-1: noise), an off-point DBSCAN_OFF.  Distances as in
+    `cc_eps`: f64 on the f32 coordinates against the f32 eps squared in f64.  The host reads the scene's bounding box
+    (to size the grid and to refuse non-finite coordinates) and the number of occupied cells, nothing else."""
+    require_device()
+    _chk(xyz, torch.float32, "xyz")
+    _chk(masks, torch.float32, "masks")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or masks.dim() != 2 or masks.shape[0] != xyz.shape[0]:
+        raise RuntimeError(f"dbscan_masks: xyz must be [N,3] and masks [N,Q], got {list(xyz.shape)}, {list(masks.shape)}")
+    eps32 = ctypes.c_float(float(eps)).value              # the value that crosses the ABI
+    if not (eps32 > 0.0) or eps32 == float("inf"):
+        raise RuntimeError(f"dbscan_masks: eps must be positive and finite, got {eps}")
+    if int(min_samples) != min_samples or int(min_samples) < 1:
+        raise RuntimeError(f"dbscan_masks: min_samples must be an integer >= 1, got {min_samples}")
+    min_samples = int(min_samples)
+    N, Q = masks.shape
+    dev = xyz.device
+    labels = torch.empty((N, Q), dtype=torch.int32, device=dev)
+    n_clusters = torch.zeros(Q, dtype=torch.int32, device=dev)
+    if N == 0 or Q == 0:
+        return labels, n_clusters
+    lo, hi = (t.double().cpu() for t in torch.aminmax(xyz, dim=0))
+    if not (bool(torch.isfinite(lo).all()) and bool(torch.isfinite(hi).all())):
+        raise RuntimeError("dbscan_masks: non-finite coordinates")
+    cells = torch.floor((hi - lo) / (eps32 * 0.5)) + 1
+    if float(cells.max()) > DBSCAN_MAX_CELLS_PER_AXIS:
+        raise RuntimeError(f"dbscan_masks: eps = {eps32} needs {[int(c) for c in cells]} cells over the scene's extent, "
+                           f"more than {DBSCAN_MAX_CELLS_PER_AXIS} along an axis")
+    nx, ny, nz = (int(c) for c in cells)
+    keys = torch.empty(N, dtype=torch.int64, device=dev)
+    check(lib.usc_dbscan_cell_keys(_ptr(xyz), N, eps32, float(lo[0]), float(lo[1]), float(lo[2]), nx, ny, nz, _ptr(keys),
+                                   _stream()), "usc_dbscan_cell_keys")
+    keys, order = torch.sort(keys, stable=True)           # stable: original indices ascend inside a cell
+    cell_keys, cell_of, counts = torch.unique_consecutive(keys, return_inverse=True, return_counts=True)
+    M = cell_keys.shape[0]                                # host read: the number of occupied cells
+    cell_of = cell_of.to(torch.int32)
+    cell_start = torch.zeros(M + 1, dtype=torch.int32, device=dev)
+    cell_start[1:] = counts.cumsum(0)
+    nbr = torch.empty((M, 125), dtype=torch.int32, device=dev)
+    check(lib.usc_dbscan_neighbor_table(_ptr(cell_keys), M, nx, ny, nz, _ptr(nbr), _stream()), "usc_dbscan_neighbor_table")
+    xs = xyz.index_select(0, order)
+    ws = _ws(lib.usc_dbscan_ws_bytes(N, Q, M, min_samples), dev)
+    check(lib.usc_dbscan_labels(_ptr(xs), _ptr(order), _ptr(cell_of), _ptr(cell_start), _ptr(nbr), _ptr(masks), N, Q, M,
+                                eps32, min_samples, _ptr(ws), ws.numel(), _ptr(labels), _ptr(n_clusters), _stream()),
+          "usc_dbscan_labels")
+    return labels, n_clusters
+
+
+def dbscan_expand(masks: torch.Tensor, labels: torch.Tensor, col_start: torch.Tensor, n_cols: int) -> torch.Tensor:
+    """One column per (query, cluster): out f32[N,n_cols], out[i, col_start[q] + labels[i,q]] = masks[i,q] where the
+    label is >= 0, else 0.  col_start i64[Q] (exclusive prefix of the clusters per query)."""
+    require_device()
+    _chk(masks, torch.float32, "masks")
+    _chk(labels, torch.int32, "labels")
+    _chk(col_start, torch.int64, "col_start")
+    if labels.shape != masks.shape or col_start.shape[0] != masks.shape[1]:
+        raise RuntimeError("dbscan_expand: labels must match masks [N,Q] and col_start must be [Q]")
+    N, Q = masks.shape
+    out = torch.zeros((N, int(n_cols)), dtype=torch.float32, device=masks.device)
+    if N and Q and n_cols:
+        check(lib.usc_dbscan_expand(_ptr(masks), _ptr(labels), _ptr(col_start), N, Q, int(n_cols), _ptr(out), _stream()),
+              "usc_dbscan_expand")
+    return out
+
+
 # ------------------------------------------------------------------ decoder-side small-row ops
 _LN_DIMS = {64, 128, 192, 256, 384, 512}
 

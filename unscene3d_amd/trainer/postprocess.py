@@ -1,7 +1,9 @@
 """Evaluation-time mask splitting (reference trainer/trainer.py:507-539, `general.use_dbscan`): every query
-mask is split into the connected components of its eps-ball graph.  The reference calls
-sklearn DBSCAN(eps=0.95, min_samples=1) once per query; here the components come from the device
-(`ops.cc_eps`, identical labels)."""
+mask is split into its DBSCAN clusters.  The reference calls sklearn DBSCAN(eps, min_samples=dbscan_min_points)
+once per query; here `dbscan_split_batched` labels all queries of a scene in one pass on the device
+(`ops.dbscan_masks`, sklearn's labels for any min_samples).  `dbscan_split` is the per-query route through the
+eps-ball components of `ops.cc_eps` (min_samples = 1 only): the A/B reference of the tests and of
+tools/export_bench.py, and the route of the CPU stand-ins of the host-logic tests."""
 from __future__ import annotations
 
 import os
@@ -29,6 +31,23 @@ def dbscan_split(masks: torch.Tensor, logits: torch.Tensor, coords: torch.Tensor
     if not new_masks:   # every query mask empty (the reference's torch.stack raises here): no instances
         return masks.new_zeros((masks.shape[0], 0)), logits.new_zeros((0, logits.shape[1]))
     return torch.stack(new_masks).T, torch.stack(new_logits)
+
+
+def dbscan_split_batched(masks: torch.Tensor, logits: torch.Tensor, coords: torch.Tensor, eps: float = 0.95,
+                         min_points: int = 1):
+    """`dbscan_split` for all queries at once and for any `min_points` (sklearn's min_samples): masks f32[N,Q],
+    logits [Q,C], coords f32[N,3] (device) -> (new_masks [N,Q'], new_logits [Q',C]), one column per (query, cluster),
+    queries ascending, clusters ascending; noise points (min_points > 1) belong to no column.  One host read: Q'."""
+    masks = masks.contiguous()
+    labels, n_clusters = ops.dbscan_masks(coords.float().contiguous(), masks, eps, min_points)
+    ends = n_clusters.to(torch.int64).cumsum(0)
+    total = int(ends[-1]) if ends.numel() else 0      # host read: the number of columns
+    if total == 0:
+        return masks.new_zeros((masks.shape[0], 0)), logits.new_zeros((0, logits.shape[1]))
+    new_masks = ops.dbscan_expand(masks, labels, (ends - n_clusters).contiguous(), total)
+    query = torch.repeat_interleave(torch.arange(masks.shape[1], device=masks.device), n_clusters.to(torch.int64),
+                                    output_size=total)
+    return new_masks, logits.index_select(0, query)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -92,8 +111,8 @@ def export_instances(output, target_low_res, target_full_res, inverse_maps, raw_
 
     output: model output dict (`pred_logits` [B,Q,C+1], `pred_masks` list of [S_b or N_b, Q], `aux_outputs`);
     target_*[b]['point2segment']; inverse_maps[b] i64[N_full_b]; raw_coords f32[sum N_b, 3] (DBSCAN only);
-    general: config node with use_dbscan, dbscan_eps, topk_per_image, filter_out_instances, scores_threshold,
-    iou_threshold.  -> list of dicts {pred_masks bool[N_full,K], pred_scores f32[K], pred_classes i64[K]
+    general: config node with use_dbscan, dbscan_eps, dbscan_min_points (optional, 1), topk_per_image,
+    filter_out_instances, scores_threshold, iou_threshold.  -> list of dicts {pred_masks bool[N_full,K], pred_scores f32[K], pred_classes i64[K]
     (+ label_offset), pred_boxes f64[K',8] = class, centre, extent, score of the non-empty masks}."""
     preds = list(output["aux_outputs"]) + [{"pred_logits": output["pred_logits"], "pred_masks": output["pred_masks"]}]
     pred = preds[decoder_id]
@@ -109,7 +128,14 @@ def export_instances(output, target_low_res, target_full_res, inverse_maps, raw_
             n = masks.shape[0]
             coords = torch.as_tensor(raw_coords[offset:offset + n], dtype=torch.float32, device=dev)
             offset += n
-            new_masks, new_logits = dbscan_split(masks, logits[bid], coords, eps=general.dbscan_eps)
+            min_points = int(getattr(general, "dbscan_min_points", 1))
+            if masks.is_cuda:
+                new_masks, new_logits = dbscan_split_batched(masks, logits[bid], coords, general.dbscan_eps, min_points)
+            elif min_points == 1:     # the host-logic tests' stand-ins (test scaffolding, not a product path)
+                new_masks, new_logits = dbscan_split(masks, logits[bid], coords, eps=general.dbscan_eps)
+            else:
+                raise RuntimeError(f"export_instances: dbscan_min_points = {min_points} needs the device "
+                                   "(ops.dbscan_masks); CPU tensors support dbscan_min_points = 1 only")
             scores, masks, classes, heatmap = get_mask_and_scores(new_logits, new_masks, new_logits.shape[0],
                                                                   num_classes - 1, general.topk_per_image)
         else:
