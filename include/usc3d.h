@@ -1521,6 +1521,36 @@ int usc_mask_bits_nms_weighted(const uint64_t* bits, const int32_t* count, const
                                const int32_t* order, int32_t n, float nms_thr, uint8_t* keep, void* ws,
                                int64_t ws_bytes, usc_stream_t s);
 
+/* ------------------------------------------------------------------------
+ * Dataset tables (datasets/freemask.py, datasets/preprocessing.py).  Explicit
+ * stream, no allocation, no synchronisation, no float atomics.
+ *
+ * usc_softmask_stats (datasets/freemask_semseg.py:300-310 without the [N,K,2]
+ *   temporaries): for every column j of soft f32[n,k], count i32[k] = the rows
+ *   with soft > thr, lo / hi f32[k,2] = min / max of x and y (xyz f32[n,3]) over
+ *   those rows; an empty column gives lo = +FLT_MAX, hi = -FLT_MAX.  Lanes run
+ *   over columns; partials per row block, then one finish pass in block order.
+ *   ws: usc_softmask_stats_ws_bytes(n, k).
+ * usc_softmask_table (:311-316 and the segment column of :437): out
+ *   i32[n, kk+2]; column 1 + j = soft[:, keep[j]] > thr as 0/1 (keep i32[kk],
+ *   every entry in [0, k): the CALLER checks that), column 0 = the OR of those,
+ *   column kk+1 = (int32_t)segments[r].
+ * usc_mesh_vertex_normals (open3d TriangleMesh::ComputeVertexNormals): the
+ *   unnormalised face normals (v1-v0) x (v2-v0), in f64 from the f32 vertices
+ *   and uncontracted, summed per vertex over corner_order i64[3F] (the stable
+ *   sort of the face corners by vertex: ascending face order) between
+ *   vertex_off[v] and vertex_off[v+1], normalised, stored as f32; a zero or
+ *   non-finite sum gives (0,0,1).  Face indices in [0, V): the CALLER checks.
+ * ---------------------------------------------------------------------- */
+int64_t usc_softmask_stats_ws_bytes(int64_t n, int32_t k);
+int usc_softmask_stats(const float* soft, const float* xyz, int64_t n, int32_t k, float thr, int32_t* count, float* lo,
+                       float* hi, void* ws, int64_t ws_bytes, usc_stream_t s);
+int usc_softmask_table(const float* soft, int64_t n, int32_t k, float thr, const int32_t* keep, int32_t kk,
+                       const float* segments, int32_t* out, usc_stream_t s);
+int usc_mesh_vertex_normals(const float* vertices, const int32_t* faces, const int64_t* corner_order,
+                            const int64_t* vertex_off, int64_t n_vertices, int64_t n_faces, float* normals,
+                            usc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

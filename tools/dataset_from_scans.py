@@ -1,0 +1,55 @@
+#!/usr/bin/env python
+"""Scan directories + pseudo-mask files -> the dataset tools/train.py --data-dir reads
+(unscene3d_amd/datasets/preprocessing.py; reference datasets/preprocessing/freemask_preprocessing.py).
+
+    python tools/dataset_from_scans.py --scans SCANS --pseudo MASKS --out DATA
+    python tools/dataset_from_scans.py --scans SCANS --pseudo MASKS --out DATA --train scannetv2_train.txt --val scannetv2_val.txt
+    python tools/train.py --data-dir DATA --steps 100 --out RUN
+
+SCANS holds one directory per scan (`scene0000_00/`: info file, mesh, and — for ground truth — labels PLY, segs.json,
+aggregation.json); MASKS is the output directory of tools/pseudo_masks_run.py.  --train / --val are text files with one
+scan name per line (ScanNet's split files); without them every directory of SCANS goes into the train split.  A scan
+without pseudo-mask files is skipped with a message.  --oracle writes one-hot ground-truth masks instead of pseudo masks.
+Prints one JSON line: scans written per mode."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--scans", required=True, help="directory with one sub-directory per scan")
+    ap.add_argument("--pseudo", default=None, help="directory with {scene}_cloud.npy / {scene}_masks.npy")
+    ap.add_argument("--out", required=True, help="dataset directory")
+    ap.add_argument("--train", default=None, metavar="FILE", help="scan names of the train split")
+    ap.add_argument("--val", default=None, metavar="FILE", help="scan names of the validation split")
+    ap.add_argument("--oracle", action="store_true", help="one-hot ground-truth masks instead of pseudo masks")
+    ap.add_argument("--segments-min-verts", type=int, default=20, help="over-segmentation when a scan has no segs.json")
+    args = ap.parse_args(argv)
+    if not args.oracle and args.pseudo is None:
+        ap.error("--pseudo is needed unless --oracle is given")
+
+    import torch
+
+    from unscene3d_amd.datasets.preprocessing import build_dataset
+
+    splits = {}
+    if args.train:
+        splits["train"] = args.train
+    if args.val:
+        splits["validation"] = args.val
+    if not splits:
+        splits["train"] = sorted(e for e in os.listdir(args.scans) if os.path.isdir(os.path.join(args.scans, e)))
+    device = torch.device("cuda", torch.cuda.current_device())
+    databases = build_dataset(args.scans, splits, args.pseudo, args.out, oracle=args.oracle, device=device,
+                              segments_min_verts=args.segments_min_verts)
+    print(json.dumps({"out": args.out, "scans": {mode: len(db) for mode, db in databases.items()}}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -254,6 +254,10 @@ SIGNATURES = {
     "usc_mask_bits_components": (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     "usc_mask_bits_split": (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "usc_mask_bits_nms_weighted": (C.c_int, [_p, _p, _p, _i64, _p, _i32, _f32, _p, _p, _i64, _p]),
+    "usc_softmask_stats_ws_bytes": (_i64, [_i64, _i32]),
+    "usc_softmask_stats": (C.c_int, [_p, _p, _i64, _i32, _f32, _p, _p, _p, _p, _i64, _p]),
+    "usc_softmask_table": (C.c_int, [_p, _i64, _i32, _f32, _p, _i32, _p, _p, _p]),
+    "usc_mesh_vertex_normals": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _p, _p]),
 }
 
 

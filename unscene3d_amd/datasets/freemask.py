@@ -10,7 +10,11 @@ python's global generators with the reference's own calls and in its order, so a
 their published definitions).  Random cuboid cuts / point resampling (point_per_cut, resample_points, noise_rate: 0 in
 every shipped config) are not built.
 
-The per-point work (1-NN transfer of the exported masks, the greedy merge, the extent filter) runs on the device."""
+The per-point work (1-NN transfer of the exported masks, the greedy merge, the extent filter) runs on the device.  With
+`device_tables=True` the reader also builds the [N, K+2] mask table there (`mask_tables_device`, csrc/dataset.hip)
+instead of with numpy on the host.
+
+`entries_from_database` / `load_color_mean_std` read what datasets/preprocessing.py writes."""
 from __future__ import annotations
 
 import os
@@ -74,17 +78,77 @@ def filter_by_extent(coordinates, freemasks, hard_threshold=0.5, extent_max_rati
     return keep.nonzero().flatten().tolist()
 
 
+def mask_tables_device(coordinates, freemasks, segments, hard_threshold=0.5, extent_max_ratio=0.8, device="cuda"):
+    """`filter_by_extent` and the table lines of `FreeMaskSceneReader.__getitem__` in two passes over the soft masks on
+    the device, without the [N,K,2] temporaries: -> (table i32[N, len(keep)+2] on the device, keep).
+    table[:, 0] = any kept mask set, table[:, 1:-1] = freemasks[:, keep] > threshold, table[:, -1] = (int32)segments;
+    `keep` is `filter_by_extent`'s list.  With an empty `keep` the table is None.
+
+    The threshold is rounded to f32 once, as numpy's `f32 array > python float` and torch's tensor-against-scalar
+    comparison both do.  The keep decision is `filter_by_extent`'s f32 arithmetic on K-sized device vectors.  The soft
+    masks must be f32, bool or integer (cast to f32 exactly); another float width would round differently from the
+    host path and is refused."""
+    dev = torch.device(device)
+    fm = np.asarray(freemasks)
+    if fm.dtype != np.float32:
+        if fm.dtype.kind not in "biu" and fm.dtype != np.float16:
+            raise TypeError(f"mask_tables_device: soft masks must be float32, bool or integer, got {fm.dtype}")
+        fm = fm.astype(np.float32)
+    N, K = fm.shape
+    if K == 0 or N == 0:
+        return None, []
+    soft = torch.as_tensor(np.ascontiguousarray(fm), device=dev)
+    xyz_h = np.asarray(coordinates)[:, :3]
+    if xyz_h.dtype != np.float32:
+        raise TypeError(f"mask_tables_device: coordinates must be float32, got {xyz_h.dtype}")
+    xyz = torch.as_tensor(np.ascontiguousarray(xyz_h), device=dev)
+    count, lo, hi = ops.softmask_stats(soft, xyz, hard_threshold)
+    c = xyz[:, :2]
+    scene = (c.amax(0) - c.amin(0)) * extent_max_ratio
+    keep = ((count > 0) & ~((hi - lo) > scene).any(1)).nonzero().flatten().tolist()
+    if not keep:
+        return None, keep
+    seg = torch.as_tensor(np.ascontiguousarray(np.asarray(segments), dtype=np.float32), device=dev)
+    return ops.softmask_table(soft, hard_threshold, keep, seg), keep
+
+
+def entries_from_database(path):
+    """`{mode}_database.yaml` (datasets/preprocessing.py; the reference's `_load_yaml`) -> the list of entry dicts the
+    reader takes (`filepath`, `raw_filepath`, `scene`, `sub_scene`, `file_len`, `color_mean`, `color_std`, ...)."""
+    import yaml
+
+    with open(path) as f:
+        entries = yaml.safe_load(f)
+    if not isinstance(entries, list) or any(not isinstance(e, dict) or "filepath" not in e or "raw_filepath" not in e
+                                            for e in entries):
+        raise ValueError(f"{path}: not a scene database (a list of entries with filepath and raw_filepath)")
+    return entries
+
+
+def load_color_mean_std(path):
+    """`color_mean_std.yaml` -> ((mean r, g, b), (std r, g, b)), the reader's `color_mean_std`."""
+    import yaml
+
+    with open(path) as f:
+        d = yaml.safe_load(f)
+    if not isinstance(d, dict) or len(d.get("mean", ())) != 3 or len(d.get("std", ())) != 3:
+        raise ValueError(f"{path}: needs mean and std with three numbers each")
+    return tuple(float(v) for v in d["mean"]), tuple(float(v) for v in d["std"])
+
+
 class FreeMaskSceneReader:
     """Validation-mode `SemanticSegmentationFreeDataset.__getitem__`: `{scene}.npy` ([N,12]: xyz, rgb, normal,
     segment id, 2 unused) + `{scene}_freemasks.npy` ([N,K] soft masks) -> the 9-tuple
-    (coordinates, features, freemasks+segments, scene_name, raw_color, raw_normals, raw_coordinates, idx, [])."""
+    (coordinates, features, freemasks+segments, scene_name, raw_color, raw_normals, raw_coordinates, idx, []).
+    `device_tables`: item 2 is built by `mask_tables_device` and returned as a device int32 tensor (the collate takes
+    it as it is); same values, same random draws (the table path draws none)."""
 
     def __init__(self, entries, color_mean_std=SCANNET_COLOR_MEAN_STD, add_colors=True, add_normals=True,
                  add_raw_coordinates=False, freemask_hard_threshold=0.5, freemask_extent_max_ratio=0.8,
                  max_num_gt_instances=-1, load_self_train_data=False, self_train_data_dir=None, num_self_train_data=5,
                  device="cuda", mode="validation", volume_augmentations=None, image_augmentations=None,
                  is_elastic_distortion=True, flip_in_center=False, color_drop=0.0, point_per_cut=0, resample_points=0,
-                 noise_rate=0):
+                 noise_rate=0, device_tables=False):
         self.data = list(entries)                      # dicts with "filepath" and "raw_filepath" (the database yaml)
         self.color_mean = np.asarray(color_mean_std[0], np.float32) * 255.0
         self.color_den = np.reciprocal(np.asarray(color_mean_std[1], np.float32) * 255.0)
@@ -95,7 +159,7 @@ class FreeMaskSceneReader:
         self.load_self_train_data = load_self_train_data
         self.self_train_data_dir = self_train_data_dir
         self.num_self_train_data = num_self_train_data
-        self.device = device
+        self.device, self.device_tables = device, bool(device_tables)
         self.mode, self.is_elastic_distortion, self.color_drop = mode, is_elastic_distortion, color_drop
         # objects with a `transforms` attribute, called like the reference's (volumentations / albumentations Compose);
         # datasets.augment.VolumeAugmentations() / ColorAugmentations() are the shipped YAML pipelines
@@ -129,6 +193,8 @@ class FreeMaskSceneReader:
         if self.max_num_gt_instances > 0:
             freemasks = freemasks[:, :self.max_num_gt_instances]
         coordinates, color, normals, segments = points[:, :3], points[:, 3:6], points[:, 6:9], points[:, 9]
+        if self.device_tables:
+            return self._item_device_tables(idx, path, coordinates, color, normals, segments, freemasks)
         keep = filter_by_extent(coordinates, freemasks, self.freemask_hard_threshold, self.freemask_extent_max_ratio,
                                 self.device)
         if not keep:
@@ -152,6 +218,25 @@ class FreeMaskSceneReader:
         raw = self.data[idx]["raw_filepath"]
         scene_name = f"scene{raw.split('/')[-1].split('_')[0]}" if "arkit" in raw.lower() else raw.split("/")[-2]
         return coordinates, features, freemasks, scene_name, raw_color, raw_normals, raw_coordinates, idx, []
+
+    def _item_device_tables(self, idx, path, coordinates, color, normals, segments, freemasks):
+        """`__getitem__` from the extent filter on, with the mask table built on the device, segment column included."""
+        table, keep = mask_tables_device(coordinates, freemasks, segments, self.freemask_hard_threshold,
+                                         self.freemask_extent_max_ratio, self.device)
+        if not keep:
+            raise LookupError(f"{path}: no usable pseudo mask")
+        raw_coordinates, raw_color, raw_normals = coordinates.copy(), color, normals
+        if not self.add_colors:
+            color = np.ones((len(color), 3))
+        if "train" in self.mode and hasattr(self.volume_augmentations, "transforms"):
+            return self._train_item(idx, coordinates, color, normals, None, table, raw_coordinates, raw_color,
+                                    raw_normals)
+        features = (color.astype(np.uint8).astype(np.float32) - self.color_mean) * self.color_den
+        if self.add_normals:
+            features = np.hstack((features, normals))
+        if self.add_raw_coordinates:
+            features = np.hstack((features, coordinates))
+        return coordinates, features, table, self._scene_name(idx), raw_color, raw_normals, raw_coordinates, idx, []
 
     def _scene_name(self, idx):
         raw = self.data[idx]["raw_filepath"]
@@ -186,5 +271,6 @@ class FreeMaskSceneReader:
             features = torch.cat([features, nrm.to(features.dtype)], 1)
         if self.add_raw_coordinates:
             features = torch.cat([features, c.to(features.dtype)], 1)
-        freemasks = np.hstack((freemasks, segments[..., None].astype(freemasks.dtype))).astype(np.int32)
+        if segments is not None:                       # device tables carry the segment column already
+            freemasks = np.hstack((freemasks, segments[..., None].astype(freemasks.dtype))).astype(np.int32)
         return c, features, freemasks, self._scene_name(idx), raw_color, raw_normals, raw_coordinates, idx, []

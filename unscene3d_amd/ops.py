@@ -1282,6 +1282,64 @@ def dbscan_expand(masks: torch.Tensor, labels: torch.Tensor, col_start: torch.Te
     return out
 
 
+# ------------------------------------------------------------------ dataset tables (csrc/dataset.hip)
+def softmask_stats(soft: torch.Tensor, xyz: torch.Tensor, thr: float):
+    """Per column of soft f32[N,K]: -> (count i32[K] of the rows with soft > f32(thr), lo f32[K,2], hi f32[K,2] = min /
+    max of x and y (xyz f32[N,3]) over those rows; an empty column gives +max / -max of f32)."""
+    require_device()
+    _chk(soft, torch.float32, "soft")
+    _chk(xyz, torch.float32, "xyz")
+    if soft.dim() != 2 or soft.shape[0] < 1 or soft.shape[1] < 1 or xyz.shape != (soft.shape[0], 3):
+        raise RuntimeError("softmask_stats: soft must be f32 [N>=1, K>=1] and xyz f32 [N,3]")
+    N, K = soft.shape
+    dev = soft.device
+    count = torch.empty(K, dtype=torch.int32, device=dev)
+    lo = torch.empty((K, 2), dtype=torch.float32, device=dev)
+    hi = torch.empty((K, 2), dtype=torch.float32, device=dev)
+    ws = _ws(lib.usc_softmask_stats_ws_bytes(N, K), dev)
+    check(lib.usc_softmask_stats(_ptr(soft), _ptr(xyz), N, K, float(thr), _ptr(count), _ptr(lo), _ptr(hi), _ptr(ws),
+                                 ws.numel(), _stream()), "usc_softmask_stats")
+    return count, lo, hi
+
+
+def softmask_table(soft: torch.Tensor, thr: float, keep, segments: torch.Tensor) -> torch.Tensor:
+    """-> i32[N, len(keep)+2]: column 0 = any kept column set, columns 1.. = soft[:, keep] > f32(thr) as 0/1, the last
+    column = (int32)segments.  `keep`: a host list of column indices."""
+    require_device()
+    _chk(soft, torch.float32, "soft")
+    _chk(segments, torch.float32, "segments")
+    N, K = soft.shape
+    keep = [int(j) for j in keep]
+    if not keep or min(keep) < 0 or max(keep) >= K or segments.shape != (N,):
+        raise RuntimeError(f"softmask_table: keep must hold indices in [0, {K}) and segments must be f32 [{N}]")
+    keep_d = torch.tensor(keep, dtype=torch.int32, device=soft.device)
+    out = torch.empty((N, len(keep) + 2), dtype=torch.int32, device=soft.device)
+    check(lib.usc_softmask_table(_ptr(soft), N, K, float(thr), _ptr(keep_d), len(keep), _ptr(segments), _ptr(out),
+                                 _stream()), "usc_softmask_table")
+    return out
+
+
+def mesh_vertex_normals(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """Area-weighted vertex normals of a triangle mesh (vertices f32[V,3], faces i32[F,3]) -> f32[V,3]: the sum of the
+    unnormalised face normals (v1-v0)x(v2-v0) over a vertex's faces in ascending face order, in f64, normalised; a
+    vertex with no face or a zero / non-finite sum gets (0,0,1).  open3d's `compute_vertex_normals` as published —
+    open3d is not available to pin it against: UNPINNED."""
+    require_device()
+    _chk(vertices, torch.float32, "vertices")
+    _chk(faces, torch.int32, "faces")
+    V, F = vertices.shape[0], faces.shape[0]
+    if F == 0 or V == 0:
+        return torch.tensor([0.0, 0.0, 1.0], device=vertices.device).repeat(V, 1)
+    lo, hi = torch.aminmax(faces)                     # the kernel dereferences the indices
+    if int(lo) < 0 or int(hi) >= V:
+        raise RuntimeError(f"mesh_vertex_normals: face index out of range [0, {V}) (min {int(lo)}, max {int(hi)})")
+    csr = segment_csr(faces.reshape(-1).to(torch.int64).contiguous(), V)     # stable: ascending face order
+    normals = torch.empty((V, 3), dtype=torch.float32, device=vertices.device)
+    check(lib.usc_mesh_vertex_normals(_ptr(vertices), _ptr(faces), _ptr(csr.order), _ptr(csr.seg_off), V, F,
+                                      _ptr(normals), _stream()), "usc_mesh_vertex_normals")
+    return normals
+
+
 # ------------------------------------------------------------------ decoder-side small-row ops
 _LN_DIMS = {64, 128, 192, 256, 384, 512}
 

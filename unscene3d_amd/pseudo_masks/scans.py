@@ -15,7 +15,8 @@ voxelisation (ME.utils.sparse_quantize), the mesh over-segmentation (felzenszwal
 and the ray-cast projection (pipeline.encode_scene_feats_2d).
 
 Not covered: the 3D modality (`pipeline.encode_scene_feats_3d` exists; add `feats_3d` to the file), depth
-images, label / instance columns, chunked scenes, the other datasets' layouts."""
+images, label / instance columns (the training dataset's builder, datasets/preprocessing.py, reads them through
+`read_ply_vertex_properties`), chunked scenes, the other datasets' layouts."""
 from __future__ import annotations
 
 import glob
@@ -194,6 +195,41 @@ def read_ply_mesh(path):
     if faces.size and (faces.min() < 0 or faces.max() >= vertices.shape[0]):
         raise ValueError(f"{path}: face index outside [0, {vertices.shape[0]})")
     return vertices, colors.astype(np.float32), np.ascontiguousarray(faces, dtype=np.int32)
+
+
+def read_ply_vertex_properties(path, names):
+    """Scalar properties of the vertex element as they are stored -> {name: array[V]} in the property's own type (what
+    the reference takes from plyfile's `elements[0].data[name]`): the integer colours 0..255 of a mesh, the `label` of
+    ScanNet's `*_vh_clean_2.labels.ply`.  Same formats as `read_ply_mesh`.  Elements in front of the vertex element
+    must hold scalars only (they are skipped).  A missing property or vertex element raises ValueError with the file
+    name."""
+    path = os.fspath(path)
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f, path)
+        for name, count, props in elements:
+            if any(p[0] == "list" for p in props):
+                raise ValueError(f"{path}: list property in element {name!r} (the vertex element or one in front of "
+                                 f"it) is not covered")
+            dt = np.dtype([(p[2], "<" + PLY_TYPES[p[1]]) for p in props])
+            if fmt == "binary_little_endian":
+                buf = f.read(dt.itemsize * count)
+                if len(buf) != dt.itemsize * count:
+                    raise ValueError(f"{path}: element {name!r} ends after {len(buf) // max(1, dt.itemsize)} of {count} records")
+                rec = np.frombuffer(buf, dtype=dt)
+            else:
+                rows = [f.readline().decode("ascii", "replace").split() for _ in range(count)]
+                if any(len(r) != len(dt.names) for r in rows):
+                    raise ValueError(f"{path}: element {name!r} has a line that does not hold {len(dt.names)} values")
+                table = np.array(rows, dtype=np.float64).reshape(count, len(dt.names))
+                rec = np.zeros(count, dtype=dt)
+                for col, n in enumerate(dt.names):
+                    rec[n] = table[:, col]
+            if name == "vertex":
+                missing = [n for n in names if n not in dt.names]
+                if missing:
+                    raise ValueError(f"{path}: vertex property {missing[0]!r} is missing")
+                return {n: np.ascontiguousarray(rec[n]) for n in names}
+    raise ValueError(f"{path}: needs a vertex element")
 
 
 # ------------------------------------------------------------------------------------------------------------ frames
