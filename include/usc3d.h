@@ -1551,6 +1551,50 @@ int usc_mesh_vertex_normals(const float* vertices, const int32_t* faces, const i
                             const int64_t* vertex_off, int64_t n_vertices, int64_t n_faces, float* normals,
                             usc_stream_t s);
 
+/* ------------------------------------------------------------------------
+ * Self-training files as bit rows (csrc/selftrain.hip; trainer/postprocess.py
+ * save_for_freemask(fmt="bits"), datasets/freemask.py load_self_train_bits).
+ * Layout of usc_freemask_bits: row j is u64[W], W = ceil(n / 64), point r is
+ * bit r % 64 of word r / 64; bits at positions >= n are written as zero and
+ * every word is written.  Explicit stream, no allocation, no synchronisation,
+ * no atomics: two runs give the same bytes.
+ *
+ * usc_mask_columns_to_bits: masks u8[n,k] row-major (non-zero = set) -> bits
+ *   u64[k,W], count i32[k] = the column popcounts (a second pass over the
+ *   rows).  A wave owns 64 consecutive points; its tile is staged through LDS
+ *   128 columns at a time and gives one ballot word per column.
+ * usc_mask_bits_gather: dst row j = src row j (u64[k, ceil(m / 64)]) read at
+ *   ind i64[n] (the 1-NN transfer masks[ind]); every entry in [0, m): the
+ *   CALLER checks that.  count i32[k] = the popcounts of dst.
+ * usc_mask_bits_count: count i32[k] = the popcounts of the rows of bits
+ *   u64[k,W] (the sizes of a file's masks: the file holds no counts).
+ * usc_selftrain_merge (datasets/freemask_semseg.py:246-265): one workgroup
+ *   walks the rows of st u64[kp,W] in ascending order; with f = popcount(st[j]
+ *   & ~fg), row j is taken when total[j] > 0 and 2 f > total[j] (integers; a
+ *   tie is refused): fresh[a] = st[j] & ~fg, fg |= fresh[a], picked[a] = j.
+ *   Stops at a == max_add or j == kp; rows a.. of fresh are zero, picked[a..]
+ *   = -1, *n_added = a; fg u64[W] is updated in place.  kp = 0 and max_add = 0
+ *   are valid.  fg is kept in LDS while W <= usc_selftrain_merge_lds_words
+ *   (default 7168 words = 458 752 points), else in global memory.
+ * usc_selftrain_merge_lds_words(words): sets that limit (clamped to the
+ *   default; a negative value changes nothing) and returns the previous one.
+ * usc_mask_bits_to_columns / _u8: out[r * ld + col0 + i] = bit r of row
+ *   rows[i] (i32[m], rows of bits u64[*, W]: the CALLER checks the range) as
+ *   0.0f / 1.0f (u8: 0 / 1), r < n; needs col0 + m <= ld.
+ * ---------------------------------------------------------------------- */
+int usc_mask_columns_to_bits(const uint8_t* masks, int64_t n, int32_t k, uint64_t* bits, int32_t* count,
+                             usc_stream_t s);
+int usc_mask_bits_gather(const uint64_t* src, int64_t m, const int64_t* ind, int64_t n, int32_t k, uint64_t* dst,
+                         int32_t* count, usc_stream_t s);
+int usc_mask_bits_count(const uint64_t* bits, int32_t k, int64_t n, int32_t* count, usc_stream_t s);
+int32_t usc_selftrain_merge_lds_words(int32_t words);
+int usc_selftrain_merge(const uint64_t* st, const int32_t* total, int32_t kp, int64_t n, uint64_t* fg,
+                        int32_t max_add, uint64_t* fresh, int32_t* picked, int32_t* n_added, usc_stream_t s);
+int usc_mask_bits_to_columns(const uint64_t* bits, const int32_t* rows, int32_t m, int64_t n, float* out, int64_t ld,
+                             int32_t col0, usc_stream_t s);
+int usc_mask_bits_to_columns_u8(const uint64_t* bits, const int32_t* rows, int32_t m, int64_t n, uint8_t* out,
+                                int64_t ld, int32_t col0, usc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,8 @@ one JSON line.
 colour statistics) over train_database.yaml, mask tables built on the device; --host-tables builds them with numpy on
 the host instead (same tables, same steps; for A/B).  validation_database.yaml + instance_gt/validation, when both
 exist, switch the validation pass on (every cfg.trainer.check_val_every_n_epoch epochs).  --self-train-dir DIR merges
-the previous round's export (DIR/freemasks/scene*_cloud.npy, _masks.npy) into every scene's masks.  The line then holds
+the previous round's export (tools/export_round.py: DIR/freemasks/scene*_cloud.npy and _masks.npy, or the bit rows
+_masks_bits.npy, which are preferred when both exist) into every scene's masks.  The line then holds
 `losses_per_step`, the weighted loss vector of every step taken.  --seed seeds numpy's, python's and torch's generators
 (the reader's augmentations draw from the first two).
 

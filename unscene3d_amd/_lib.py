@@ -258,6 +258,13 @@ SIGNATURES = {
     "usc_softmask_stats": (C.c_int, [_p, _p, _i64, _i32, _f32, _p, _p, _p, _p, _i64, _p]),
     "usc_softmask_table": (C.c_int, [_p, _i64, _i32, _f32, _p, _i32, _p, _p, _p]),
     "usc_mesh_vertex_normals": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _p, _p]),
+    "usc_mask_columns_to_bits": (C.c_int, [_p, _i64, _i32, _p, _p, _p]),
+    "usc_mask_bits_gather": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _p]),
+    "usc_mask_bits_count": (C.c_int, [_p, _i32, _i64, _p, _p]),
+    "usc_selftrain_merge_lds_words": (_i32, [_i32]),
+    "usc_selftrain_merge": (C.c_int, [_p, _p, _i32, _i64, _p, _i32, _p, _p, _p, _p]),
+    "usc_mask_bits_to_columns": (C.c_int, [_p, _p, _i32, _i64, _p, _i64, _i32, _p]),
+    "usc_mask_bits_to_columns_u8": (C.c_int, [_p, _p, _i32, _i64, _p, _i64, _i32, _p]),
 }
 
 

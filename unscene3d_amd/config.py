@@ -24,6 +24,9 @@ def default_config():
                     # export between self-training rounds (conf/config_base_instance_segmentation.yaml:12-44)
                     "filter_out_instances": False, "scores_threshold": 0.1, "iou_threshold": 0.66,
                     "topk_per_image": 100, "save_for_freemask": False, "save_dir": "saved",
+                    # mask files of save_for_freemask: "npy" (bool [N,K], the reference's), "bits" (u64 bit rows,
+                    # `{name}_masks_bits.npy`, packed on the device) or "both"
+                    "freemask_format": "npy",
                     # trunk convolutions of eval_step / validation_step / the pseudo-mask 3D encoder: "f32" or "bf16"
                     # (unscene3d_amd.inference_precision; never used with autograd)
                     "eval_precision": "f32",
@@ -72,6 +75,8 @@ def apply_overrides(cfg, overrides):
     if getattr(cfg.general, "train_precision", "f32") not in ("f32", "bf16x2", "bf16x3"):
         raise ValueError("general.train_precision must be 'f32', 'bf16x2' or 'bf16x3', not "
                          f"{cfg.general.train_precision!r}")
+    if getattr(cfg.general, "freemask_format", "npy") not in ("npy", "bits", "both"):
+        raise ValueError(f"general.freemask_format must be 'npy', 'bits' or 'both', not {cfg.general.freemask_format!r}")
     # interpolations of the reference YAML (${general.num_targets}, ${general.train_on_segments}, …)
     cfg.model.num_classes = cfg.general.num_targets
     cfg.loss.num_classes = cfg.general.num_targets

@@ -12,7 +12,9 @@ every shipped config) are not built.
 
 The per-point work (1-NN transfer of the exported masks, the greedy merge, the extent filter) runs on the device.  With
 `device_tables=True` the reader also builds the [N, K+2] mask table there (`mask_tables_device`, csrc/dataset.hip)
-instead of with numpy on the host.
+instead of with numpy on the host.  When the export wrote bit rows (`{scene}_masks_bits.npy`,
+save_for_freemask(fmt="bits")), `load_self_train_bits` merges them with the kernels of csrc/selftrain.hip: one launch for
+the greedy loop and one read-back (the number of added columns) instead of one per visited column.
 
 `entries_from_database` / `load_color_mean_std` read what datasets/preprocessing.py writes."""
 from __future__ import annotations
@@ -64,6 +66,58 @@ def load_self_train_masks(points, freemasks, self_train_cloud, self_train_masks,
     return np.concatenate([fm, new], axis=1)
 
 
+def load_self_train_bits(points, freemasks, self_train_cloud, bits, num_self_train_data=5, drop_original=False,
+                         device="cuda", as_device=False):
+    """`load_self_train_masks` for the bit-row file (`{scene}_masks_bits.npy`, u64[K', ceil(M/64)], written by
+    save_for_freemask(fmt="bits")): the same sameness test, then `ops.knn1` + `ops.mask_bits_gather` when the clouds
+    differ; the covered points are `any(freemasks != 0)` packed as one bit row; the greedy loop is one
+    `ops.selftrain_merge` launch, and the number of added columns is the only value read back.
+    -> the array `load_self_train_masks` returns for the unpacked file (values and dtype).  `as_device`: that array as
+    an f32 device tensor [N, K + added] which never visits the host (what `mask_tables_device` takes); the soft masks
+    must then be f32, f16, bool or integer, as for `mask_tables_device`."""
+    dev = torch.device(device)
+    xyz = torch.as_tensor(np.ascontiguousarray(np.asarray(points)[:, :3]), dtype=torch.float32, device=dev)
+    cloud = torch.as_tensor(np.ascontiguousarray(np.asarray(self_train_cloud)[:, :3]), dtype=torch.float32, device=dev)
+    N, M = xyz.shape[0], cloud.shape[0]
+    b = np.asarray(bits)
+    if b.dtype != np.uint64 or b.ndim != 2 or b.shape[1] != (M + 63) // 64:
+        raise ValueError(f"load_self_train_bits: bits must be uint64 [K', {(M + 63) // 64}] for a cloud of {M} points, "
+                         f"got {b.dtype} {b.shape}")
+    fm = np.asarray(freemasks)
+    if as_device and fm.dtype != np.float32 and fm.dtype.kind not in "biu" and fm.dtype != np.float16:
+        raise TypeError(f"load_self_train_bits: soft masks must be float32, bool or integer, got {fm.dtype}")
+    if drop_original:
+        fm = np.zeros((fm.shape[0], 0), dtype=fm.dtype)
+    K = fm.shape[1]
+    fm_d = torch.as_tensor(np.ascontiguousarray(fm), device=dev) if K and N else None
+    added = 0
+    if N and M and b.shape[0] and num_self_train_data > 0:
+        st = torch.as_tensor(np.ascontiguousarray(b).view(np.int64), device=dev)
+        same = N == M and bool(torch.isclose(xyz, cloud, rtol=1e-5, atol=1e-8).all())
+        if same:
+            total = ops.mask_bits_count(st, N)
+        else:                                          # np.allclose failed: 1-NN transfer, on bit rows
+            _, ind = ops.knn1(xyz.contiguous(), cloud.contiguous())
+            st, total = ops.mask_bits_gather(st, M, ind, check_range=False)       # knn1 returns indices in [0, M)
+        if fm_d is not None:
+            fg = ops.mask_columns_to_bits((fm_d != 0).any(1).reshape(N, 1))[0][0].contiguous()
+        else:
+            fg = torch.zeros((N + 63) // 64, dtype=torch.int64, device=dev)
+        fresh, picked, n_added = ops.selftrain_merge(st, total, N, fg, int(num_self_train_data))
+        added = int(n_added)                           # the one read-back
+    if not as_device:
+        if not added:
+            return fm
+        new = ops.mask_bits_to_columns(fresh, N, rows=range(added), dtype=torch.bool).cpu().numpy()
+        return np.concatenate([fm, new], axis=1)
+    out = torch.empty((N, K + added), dtype=torch.float32, device=dev)
+    if fm_d is not None:
+        out[:, :K] = fm_d                              # exact: f32 as it is, bool / integer / f16 widened
+    if added:
+        ops.mask_bits_to_columns(fresh, N, rows=range(added), out=out, col0=K)
+    return out
+
+
 def filter_by_extent(coordinates, freemasks, hard_threshold=0.5, extent_max_ratio=0.8, device="cuda"):
     """Column indices of the masks that are non-empty and whose XY extent does not exceed `extent_max_ratio` of the
     scene's in either direction (freemask_semseg.py:300-310)."""
@@ -87,17 +141,26 @@ def mask_tables_device(coordinates, freemasks, segments, hard_threshold=0.5, ext
     The threshold is rounded to f32 once, as numpy's `f32 array > python float` and torch's tensor-against-scalar
     comparison both do.  The keep decision is `filter_by_extent`'s f32 arithmetic on K-sized device vectors.  The soft
     masks must be f32, bool or integer (cast to f32 exactly); another float width would round differently from the
-    host path and is refused."""
+    host path and is refused.  `freemasks` may also be an f32 device tensor [N,K], which is used where it lies."""
     dev = torch.device(device)
-    fm = np.asarray(freemasks)
-    if fm.dtype != np.float32:
-        if fm.dtype.kind not in "biu" and fm.dtype != np.float16:
-            raise TypeError(f"mask_tables_device: soft masks must be float32, bool or integer, got {fm.dtype}")
-        fm = fm.astype(np.float32)
-    N, K = fm.shape
-    if K == 0 or N == 0:
-        return None, []
-    soft = torch.as_tensor(np.ascontiguousarray(fm), device=dev)
+    if torch.is_tensor(freemasks):                     # already on the device (load_self_train_bits(as_device=True))
+        if freemasks.dtype != torch.float32 or not freemasks.is_cuda or freemasks.dim() != 2:
+            raise TypeError("mask_tables_device: a tensor of soft masks must be float32 [N,K] on the device, got "
+                            f"{freemasks.dtype} {tuple(freemasks.shape)} on {freemasks.device}")
+        N, K = freemasks.shape
+        if K == 0 or N == 0:
+            return None, []
+        soft = freemasks.contiguous()
+    else:
+        fm = np.asarray(freemasks)
+        if fm.dtype != np.float32:
+            if fm.dtype.kind not in "biu" and fm.dtype != np.float16:
+                raise TypeError(f"mask_tables_device: soft masks must be float32, bool or integer, got {fm.dtype}")
+            fm = fm.astype(np.float32)
+        N, K = fm.shape
+        if K == 0 or N == 0:
+            return None, []
+        soft = torch.as_tensor(np.ascontiguousarray(fm), device=dev)
     xyz_h = np.asarray(coordinates)[:, :3]
     if xyz_h.dtype != np.float32:
         raise TypeError(f"mask_tables_device: coordinates must be float32, got {xyz_h.dtype}")
@@ -175,6 +238,15 @@ class FreeMaskSceneReader:
         scene_id = Path(self.data[idx]["filepath"]).stem
         name = "masks" if self.load_self_train_data != "refined" else "masks_refined"
         base = os.path.join(self.self_train_data_dir, "freemasks")
+        bits_path = os.path.join(base, f"scene{scene_id}_masks_bits.npy")
+        if name == "masks" and os.path.exists(bits_path):       # save_for_freemask(fmt="bits" | "both")
+            try:
+                cloud = np.load(os.path.join(base, f"scene{scene_id}_cloud.npy"))
+            except FileNotFoundError:
+                print(f"Could not load self training data for scene{scene_id}")
+                return freemasks
+            return load_self_train_bits(points, freemasks, cloud, np.load(bits_path), self.num_self_train_data,
+                                        device=self.device, as_device=self.device_tables)
         try:
             cloud = np.load(os.path.join(base, f"scene{scene_id}_cloud.npy"))
             masks = np.load(os.path.join(base, f"scene{scene_id}_{name}.npy"))

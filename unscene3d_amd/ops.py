@@ -1319,6 +1319,127 @@ def softmask_table(soft: torch.Tensor, thr: float, keep, segments: torch.Tensor)
     return out
 
 
+# ------------------------------------------------------------------ self-training bit rows (csrc/selftrain.hip)
+def _bit_words(n: int) -> int:
+    return (int(n) + 63) // 64
+
+
+def _chk_bits(bits: torch.Tensor, n: int, name: str):
+    """Bit rows travel as int64 tensors (the u64 bit pattern), [rows, ceil(n / 64)]."""
+    _chk(bits, torch.int64, name)
+    if bits.dim() != 2 or bits.shape[1] != _bit_words(n):
+        raise RuntimeError(f"{name} must be int64 [rows, {_bit_words(n)}] (bit rows of {n} points), got "
+                           f"{tuple(bits.shape)}")
+    return bits
+
+
+def mask_columns_to_bits(masks: torch.Tensor):
+    """masks bool / uint8 [N>=1, K] (non-zero = set) -> (bits i64[K, ceil(N/64)]: column j as a bit row, point r = bit
+    r % 64 of word r / 64, zero beyond N; count i32[K] = the column popcounts)."""
+    require_device()
+    if isinstance(masks, torch.Tensor) and masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    _chk(masks, torch.uint8, "masks")
+    if masks.dim() != 2 or masks.shape[0] < 1:
+        raise RuntimeError("mask_columns_to_bits: masks must be bool or uint8 [N>=1, K]")
+    N, K = masks.shape
+    bits = torch.empty((K, _bit_words(N)), dtype=torch.int64, device=masks.device)
+    count = torch.empty(K, dtype=torch.int32, device=masks.device)
+    if K:
+        check(lib.usc_mask_columns_to_bits(_ptr(masks), N, K, _ptr(bits), _ptr(count), _stream()),
+              "usc_mask_columns_to_bits")
+    return bits, count
+
+
+def mask_bits_count(bits: torch.Tensor, n: int) -> torch.Tensor:
+    """Set bits of every row of bits i64[K, ceil(n/64)] -> i32[K]."""
+    require_device()
+    _chk_bits(bits, n, "bits")
+    count = torch.empty(bits.shape[0], dtype=torch.int32, device=bits.device)
+    if bits.shape[0]:
+        check(lib.usc_mask_bits_count(_ptr(bits), bits.shape[0], int(n), _ptr(count), _stream()), "usc_mask_bits_count")
+    return count
+
+
+def mask_bits_gather(src: torch.Tensor, m: int, ind: torch.Tensor, check_range: bool = True):
+    """Bit rows of `masks[ind]`: src i64[K, ceil(m/64)] (bit rows over m points), ind i64[N>=1] with every entry in
+    [0, m) (checked here with one host read; `check_range=False`: the caller vouches for it, e.g. `knn1`'s output)
+    -> (dst i64[K, ceil(N/64)], count i32[K])."""
+    require_device()
+    _chk_bits(src, m, "src")
+    _chk(ind, torch.int64, "ind")
+    if ind.dim() != 1 or ind.shape[0] < 1 or m < 1:
+        raise RuntimeError("mask_bits_gather: ind must be int64 [N>=1] and m >= 1")
+    if check_range:
+        lo, hi = torch.aminmax(ind)                   # the kernel dereferences the indices
+        if int(lo) < 0 or int(hi) >= m:
+            raise RuntimeError(f"mask_bits_gather: index out of range [0, {m}) (min {int(lo)}, max {int(hi)})")
+    N, K = ind.shape[0], src.shape[0]
+    dst = torch.empty((K, _bit_words(N)), dtype=torch.int64, device=src.device)
+    count = torch.empty(K, dtype=torch.int32, device=src.device)
+    if K:
+        check(lib.usc_mask_bits_gather(_ptr(src), int(m), _ptr(ind), N, K, _ptr(dst), _ptr(count), _stream()),
+              "usc_mask_bits_gather")
+    return dst, count
+
+
+def selftrain_merge(st: torch.Tensor, total: torch.Tensor, n: int, fg: torch.Tensor, max_add: int):
+    """The greedy merge of the self-training reader on bit rows: st i64[K', W] the exported instances (most confident
+    first), total i32[K'] their sizes, fg i64[W] the covered points (UPDATED IN PLACE), W = ceil(n/64).  Row j is
+    taken when total[j] > 0 and 2 * popcount(st[j] & ~fg) > total[j]; only its uncovered part is added.
+    -> (fresh i64[max_add, W], picked i32[max_add] (-1 past the end), n_added i32[1]), all on the device."""
+    require_device()
+    _chk_bits(st, n, "st")
+    _chk(total, torch.int32, "total")
+    _chk(fg, torch.int64, "fg")
+    W, kp, max_add = _bit_words(n), st.shape[0], int(max_add)
+    if n < 1 or total.shape != (kp,) or fg.shape != (W,) or max_add < 0:
+        raise RuntimeError(f"selftrain_merge: needs n >= 1, total i32[{kp}], fg i64[{W}] and max_add >= 0")
+    dev = st.device
+    fresh = torch.empty((max_add, W), dtype=torch.int64, device=dev)
+    picked = torch.empty(max_add, dtype=torch.int32, device=dev)
+    n_added = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib.usc_selftrain_merge(_ptr(st) if kp else None, _ptr(total) if kp else None, kp, int(n), _ptr(fg), max_add,
+                                  _ptr(fresh) if max_add else None, _ptr(picked) if max_add else None, _ptr(n_added),
+                                  _stream()), "usc_selftrain_merge")
+    return fresh, picked, n_added
+
+
+def mask_bits_to_columns(bits: torch.Tensor, n: int, rows=None, out: torch.Tensor = None, col0: int = 0,
+                         dtype=torch.float32):
+    """Columns from bit rows: out[r, col0 + i] = bit r of bits[rows[i]] as 0 / 1, r < n.  rows: a host list or an
+    i32 device tensor of row indices (None: every row in order).  out: f32 or uint8 [n, >= col0 + len(rows)]
+    (row-major; allocated as [n, len(rows)] of `dtype` when None; torch.bool is written as uint8).  -> out."""
+    require_device()
+    _chk_bits(bits, n, "bits")
+    if rows is None:
+        rows = torch.arange(bits.shape[0], dtype=torch.int32, device=bits.device)
+    elif not isinstance(rows, torch.Tensor):
+        rows = [int(j) for j in rows]
+        if rows and (min(rows) < 0 or max(rows) >= bits.shape[0]):
+            raise RuntimeError(f"mask_bits_to_columns: rows must hold indices in [0, {bits.shape[0]})")
+        rows = torch.tensor(rows, dtype=torch.int32, device=bits.device)
+    _chk(rows, torch.int32, "rows")
+    m = rows.shape[0]
+    if out is None:
+        if dtype not in (torch.float32, torch.uint8, torch.bool):
+            raise RuntimeError("mask_bits_to_columns: dtype must be float32, uint8 or bool")
+        out = torch.empty((int(n), m), dtype=torch.uint8 if dtype == torch.bool else dtype, device=bits.device)
+        ret = out.view(torch.bool) if dtype == torch.bool else out
+    else:
+        ret = out
+    if out.dtype not in (torch.float32, torch.uint8):
+        raise RuntimeError(f"mask_bits_to_columns: out must be float32 or uint8, got {out.dtype}")
+    _chk(out, out.dtype, "out")
+    if out.dim() != 2 or out.shape[0] != n or col0 < 0 or out.shape[1] < col0 + m:
+        raise RuntimeError(f"mask_bits_to_columns: out must be [{n}, >= {col0 + m}], got {tuple(out.shape)}")
+    fn = lib.usc_mask_bits_to_columns if out.dtype == torch.float32 else lib.usc_mask_bits_to_columns_u8
+    if n and m:
+        check(fn(_ptr(bits), _ptr(rows), m, int(n), _ptr(out), out.shape[1], int(col0), _stream()),
+              "usc_mask_bits_to_columns")
+    return ret
+
+
 def mesh_vertex_normals(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     """Area-weighted vertex normals of a triangle mesh (vertices f32[V,3], faces i32[F,3]) -> f32[V,3]: the sum of the
     unnormalised face normals (v1-v0)x(v2-v0) over a vertex's faces in ascending face order, in f64, normalised; a

@@ -178,11 +178,37 @@ def mask_boxes(masks, coords, classes, scores):
     return out[ok]
 
 
-def save_for_freemask(save_dir, file_name, full_res_coords, pred_masks):
+def save_for_freemask(save_dir, file_name, full_res_coords, pred_masks, fmt="npy"):
     """`{save_dir}/freemasks/{name}_cloud.npy` (coordinates) and `{name}_masks.npy` (bool [N_full,K]) — the files
-    the next self-training round's preprocessing reads (trainer.py:743-760)."""
+    the next self-training round's preprocessing reads (trainer.py:743-760).
+
+    fmt (`general.freemask_format`): "npy" writes those two files; "bits" writes the cloud and, instead of the bool
+    table, `{name}_masks_bits.npy`: u64[K, ceil(N_full/64)], mask j as a bit row (point r = bit r % 64 of word r / 64,
+    zero beyond N_full), packed on the device (`ops.mask_columns_to_bits`) so that only the bit rows cross to the
+    host — 1/8 of the bytes of the bool table in flight, 1/8 on disk; "both" writes all three.  The reader
+    (datasets/freemask.py) prefers the bit rows when they exist."""
+    if fmt not in ("npy", "bits", "both"):
+        raise ValueError(f"save_for_freemask: fmt must be 'npy', 'bits' or 'both', not {fmt!r}")
     d = os.path.join(save_dir, "freemasks")
     os.makedirs(d, exist_ok=True)
     np.save(os.path.join(d, f"{file_name}_cloud.npy"), np.asarray(full_res_coords))
+    if fmt != "npy":
+        np.save(os.path.join(d, f"{file_name}_masks_bits.npy"), pack_mask_bits(pred_masks))
+        if fmt == "bits":
+            return
     masks = pred_masks.cpu().numpy() if torch.is_tensor(pred_masks) else np.asarray(pred_masks)
     np.save(os.path.join(d, f"{file_name}_masks.npy"), masks.astype(bool))
+
+
+def pack_mask_bits(pred_masks):
+    """[N,K] masks (device tensor, or a host array that is uploaded; non-zero = set) -> host u64[K, ceil(N/64)]."""
+    m = pred_masks if torch.is_tensor(pred_masks) else torch.as_tensor(np.asarray(pred_masks))
+    if m.dim() != 2:
+        raise ValueError(f"pack_mask_bits: masks must be [N,K], got {tuple(m.shape)}")
+    if m.dtype != torch.bool:
+        m = m != 0
+    N, K = m.shape
+    if N == 0 or K == 0:
+        return np.zeros((K, (N + 63) // 64), np.uint64)
+    bits, _ = ops.mask_columns_to_bits((m if m.is_cuda else m.to("cuda")).contiguous())
+    return bits.cpu().numpy().view(np.uint64)

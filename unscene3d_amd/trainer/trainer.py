@@ -241,7 +241,7 @@ class InstanceSegmentation(nn.Module):
                                      full_res_coords=data.full_res_coords)
         if getattr(g, "save_for_freemask", False):
             for name, coords, inst in zip(file_names, data.full_res_coords, instances):
-                save_for_freemask(g.save_dir, name, coords, inst["pred_masks"])
+                save_for_freemask(g.save_dir, name, coords, inst["pred_masks"], getattr(g, "freemask_format", "npy"))
         sc = output.get("sampled_coords")
         if sc is not None and not isinstance(sc, np.ndarray):       # the reference hands back a numpy array (mask3d.py:467)
             output["sampled_coords"] = np.asarray(sc)
