@@ -166,6 +166,24 @@ def test_joins_are_queued_again_after_a_failed_backward(device, monkeypatch):
     """A backward node that raises makes the engine drop its end-of-backward callbacks.  The queued-once marks of the
     lane join / grouped weight gradients are keyed on the graph task, so the next pass queues its own join and its
     gradients are complete (a sticky flag left every later pass un-joined)."""
+    _failed_backward_then_a_clean_one(device, monkeypatch, lane=True)
+
+
+@pytest.mark.parametrize("path", ["lane-off-blocks"])
+def test_joins_are_queued_again_after_a_failed_backward_without_the_lane(device, monkeypatch, path):
+    """The same with the lane off on the per-block path: the poisoned pass leaves its last grouped weight gradients in
+    units._WgradQueue (their flush was an end-of-backward callback); the next pass drops them and empties its own queue."""
+    from unscene3d_amd import program, units
+    saved = units.LANE_MAX_ROWS
+    monkeypatch.setattr(program, "ENABLED", False)
+    try:
+        units.set_lane_max_rows(0)
+        _failed_backward_then_a_clean_one(device, monkeypatch, lane=False)
+    finally:
+        units.set_lane_max_rows(saved)
+
+
+def _failed_backward_then_a_clean_one(device, monkeypatch, lane):
     from unscene3d_amd import program, units
 
     class Poison(torch.autograd.Function):
@@ -179,13 +197,14 @@ def test_joins_are_queued_again_after_a_failed_backward(device, monkeypatch):
 
     coords4, feats = _scene(12_000, 2323)
     model = _fresh_model(device, seed=8)
-    monkeypatch.setattr(program, "ENABLED", True)
+    if lane:
+        monkeypatch.setattr(program, "ENABLED", True)
     joins = []
     real_join = units.join_lane
     monkeypatch.setattr(units, "join_lane", lambda *a, **k: (joins.append(1), real_join(*a, **k))[1])
     _run(model, coords4, feats, device, (1, 1, 1, 1, 1))[2].backward()
     torch.cuda.synchronize()
-    assert joins, "the lane join runs at the end of a backward pass"
+    assert bool(joins) == lane, "the lane join runs at the end of a backward pass"
     want = {n: p.grad.clone() for n, p in model.named_parameters() if not n.startswith("final.")}
     for p in model.parameters():
         p.grad.zero_()
@@ -196,13 +215,16 @@ def test_joins_are_queued_again_after_a_failed_backward(device, monkeypatch):
     with pytest.raises(RuntimeError, match="poisoned"):
         loss.backward()
     torch.cuda.synchronize()
+    if not lane:
+        assert any(q.items for q in units._WGQ.values()), "the poisoned pass left no queued weight gradient behind"
     for p in model.parameters():
         p.grad.zero_()
     model.load_state_dict({k: v for k, v in model.state_dict().items()})
     n0 = len(joins)
     # the batch-norm running statistics moved twice; the gradients depend on the batch statistics only
     _run(model, coords4, feats, device, (1, 1, 1, 1, 1))[2].backward()
-    assert len(joins) > n0, "the pass after a failed one queued no lane join"
+    assert (len(joins) > n0) == lane, "the pass after a failed one queued no lane join"
+    assert not any(q.items for q in units._WGQ.values())
     torch.cuda.synchronize()
     for n, g in want.items():
         assert torch.equal(g, dict(model.named_parameters())[n].grad), n

@@ -510,8 +510,7 @@ class Mask3D(nn.Module):
         bias = head.bias
         if head.kernel_volume != 1 or head.stride != 1 or ops._grad_target(head.kernel) is None:
             return None
-        if bias is not None and (not bias.requires_grad or bias.grad is None or bias._backward_hooks
-                                 or getattr(bias, "_post_accumulate_grad_hooks", None)):
+        if bias is not None and not (bias.requires_grad and ops._grad_target(bias) is not None):
             return None
         cm = pcd_features.coordinate_manager
         if not all(isinstance(sl, slice) for sl in cm.batch_slices(pcd_features._ts())):
@@ -781,14 +780,14 @@ def _early_stage_gate(model, handle, pcd_features, mask_features, seg_csr, predi
                 ops.check(ops.lib.usc_segment_mean_bwd(dseg.data_ptr(), d, csr.seg.data_ptr(), csr.seg_off.data_ptr(),
                                                        rows.shape[0], rows.data_ptr(), ops._stream()), "usc_segment_mean_bwd")
                 kept.extend((dseg, csr))
-            # the 1x1 mask head, as ops._ConvSame.backward issues it
+            # the 1x1 mask head: the backward of its ops._ConvSame node (the weight gradient goes into W.grad, _early_stage)
             W = head.kernel
             W3 = (W if W.dim() == 3 else W[None]).contiguous()
-            dfeats = ops.gather_gemm(dmask, ops.weight_transpose(W3, mirror=False), None, x.shape[0])
-            ops.wgrad(x, dmask, 1, into=ops._grad_target(W))
-            ops._grad_written(W)
-            if head.bias is not None:
-                head.bias.grad.add_(ops.colsum(dmask).view_as(head.bias.grad))
+            dfeats, dW, dbias = ops.conv_same_backward(x, W3, W, dmask, None, None, need_dbias=head.bias is not None)
+            if dW is not None:
+                raise RuntimeError("early stage: the mask head's kernel lost its in-place gradient target during the step")
+            if dbias is not None:
+                head.bias.grad.add_(dbias.view_as(head.bias.grad))
             kept.extend((x, W3, dfeats))
             program.early_backward(handle, dfeats, keep=kept)
         EARLY_STAGE_STEPS += 1

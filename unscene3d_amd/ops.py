@@ -12,6 +12,7 @@ from dataclasses import dataclass
 
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -436,14 +437,42 @@ def _grad_target(param):
     return None
 
 
-_JOIN_QUEUED_TASK = None        # id of the autograd graph task whose end-of-backward join has been queued
-
-
 def _graph_task():
-    """Id of the running backward pass (-1 outside one).  The queued-once marks of the end-of-backward joins are keyed
-    on it: the engine drops its callbacks when a backward node raises, and a sticky flag would then keep every later
-    pass from queueing its join (tests/test_gpu_program.py::test_joins_are_queued_again_after_a_failed_backward)."""
+    """Id of the running backward pass (-1 outside one)."""
     return torch._C._current_graph_task_id()
+
+
+_END_MARKS = weakref.WeakKeyDictionary()    # key object -> graph task in which at_end_of_backward queued the key's callback
+
+
+def at_end_of_backward(key, fn, outside):
+    """Run `fn` when the running backward pass ends: queued with the engine once per (key, pass), `key` being the object
+    the work belongs to.  Outside a pass (a direct call of a backward function) "run" calls `fn` now, "skip" does nothing.
+    The engine drops its callbacks when a backward node raises, so the marks are keyed on the graph task: a mark of
+    another pass is stale and is replaced (a sticky one kept every later pass from queueing,
+    test_joins_are_queued_again_after_a_failed_backward); held weakly, it goes with a short-lived key (a GradSink)."""
+    if outside not in ("run", "skip"):
+        raise ValueError("at_end_of_backward: outside is 'run' or 'skip'")
+    task = _graph_task()
+    if task < 0:
+        if outside == "run":
+            fn()
+        return
+    if _END_MARKS.get(key) == task:
+        return
+    _END_MARKS[key] = task
+
+    def done():
+        if _END_MARKS.get(key) == task:
+            del _END_MARKS[key]
+        fn()
+    torch.autograd.Variable._execution_engine.queue_callback(done)
+
+
+def queued_at_end_of_backward(key):
+    """Is the callback of `key` queued in the RUNNING pass?  If not, state that a caller keeps for the callback
+    (units._WgradQueue) was left by a pass that never finished."""
+    return 0 <= _graph_task() == _END_MARKS.get(key)
 
 
 def _join_after_backward():
@@ -451,19 +480,8 @@ def _join_after_backward():
     for the streams of the AccumulateGrad nodes it ran, not for a stream on which a backward wrote p.grad in place: one
     end-of-backward callback lets the caller's stream wait for the side streams, so that `loss.backward();
     optimizer.step()` stays correct without the caller knowing about them."""
-    global _JOIN_QUEUED_TASK
-    if not SIDE_STREAMS or not on_side_stream():
-        return
-    task = _graph_task()
-    if task < 0 or task == _JOIN_QUEUED_TASK:
-        return
-    _JOIN_QUEUED_TASK = task
-
-    def done():
-        global _JOIN_QUEUED_TASK
-        _JOIN_QUEUED_TASK = None
-        join_side_streams()
-    torch.autograd.Variable._execution_engine.queue_callback(done)
+    if SIDE_STREAMS and on_side_stream():
+        at_end_of_backward(join_side_streams, join_side_streams, outside="skip")
 
 
 PARAMS_FINAL_HOOK = None  # callable(list of params), set by optim.FlatAdamW.enable_early: "every kernel that adds into the
@@ -496,7 +514,8 @@ def _param_grads(params, zeros=False):
     bufs = [_grad_target(p) for p in live]
     in_place = all(t is not None for t in bufs)
     if not in_place:
-        bufs = [torch.zeros_like(p) if zeros else torch.empty_like(p) for p in live]
+        new = torch.zeros_like if zeros else torch.empty_like
+        bufs = [new(p, memory_format=torch.contiguous_format) for p in live]
     it = iter(bufs)
     bufs = [None if p is None else next(it) for p in params]
 
@@ -571,36 +590,42 @@ class _ConvSame(torch.autograd.Function):
         out = gather_gemm(feats, W3.contiguous(), nbr, feats.shape[0], bias=None if bias is None else bias.reshape(-1))
         ctx.save_for_backward(feats, W3)
         ctx.nbr, ctx.get_rulebook = nbr, get_rulebook
-        ctx.w_dim, ctx.has_bias = W.dim(), bias is not None
+        ctx.has_bias = bias is not None
         ctx.w_param = W
         return out
 
     @staticmethod
     def backward(ctx, dout):
         feats, W3 = ctx.saved_tensors
-        dout = dout.contiguous()
-        K = W3.shape[0]
-        dfeats = dW = dbias = None
-        if ctx.needs_input_grad[0]:
-            if K > 1:
-                dfeats = gather_gemm(dout, W3.contiguous(), ctx.nbr, feats.shape[0], w_transposed=True)
-            else:
-                dfeats = gather_gemm(dout, weight_transpose(W3.contiguous(), mirror=False), ctx.nbr, feats.shape[0])
-        if ctx.needs_input_grad[1]:
-            tgt = _grad_target(ctx.w_param)
-            if ctx.nbr is None:
-                dW = wgrad(feats, dout, 1, into=tgt)
-            else:
-                rb = ctx.get_rulebook()
-                dW = wgrad(feats, dout, K, rb.in_idx, rb.out_idx, rb.koff, into=tgt, nbr=ctx.nbr)
-            if tgt is not None:
-                dW = None
-                _grad_written(ctx.w_param)
-            elif ctx.w_dim == 2:
-                dW = dW[0]
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            dbias = colsum(dout).reshape(1, -1)
-        return dfeats, dW, dbias, None, None
+        dfeats, dW, dbias = conv_same_backward(feats, W3, ctx.w_param, dout.contiguous(), ctx.nbr, ctx.get_rulebook,
+                                               *ctx.needs_input_grad[:2], ctx.has_bias and ctx.needs_input_grad[2])
+        return dfeats, dW, None if dbias is None else dbias.reshape(1, -1), None, None
+
+
+def _wgrad_param(W_param, a, b, K, a_idx=None, b_idx=None, koff=None, nbr=None):
+    """wgrad under the parameter-gradient rule (_param_grads) -> what the node returns for the weight."""
+    (dW,), in_place, finish = _param_grads((W_param,))
+    wgrad(a, b, K, a_idx, b_idx, koff, into=dW if in_place else None, out=None if in_place else dW, nbr=nbr)
+    return finish()[0]
+
+
+def conv_same_backward(feats, W3, W_param, dout, nbr, get_rulebook, need_dfeats=True, need_dW=True, need_dbias=False):
+    """The body of _ConvSame.backward (models/mask3d.py's early-stage gate issues the mask head's on the lane): input
+    gradient, weight gradient (None when added into W_param.grad), bias column sum f32[cout]; None where not needed."""
+    K = W3.shape[0]
+    dfeats = dW = None
+    if need_dfeats:
+        if K > 1:
+            dfeats = gather_gemm(dout, W3.contiguous(), nbr, feats.shape[0], w_transposed=True)
+        else:
+            dfeats = gather_gemm(dout, weight_transpose(W3.contiguous(), mirror=False), nbr, feats.shape[0])
+    if need_dW:
+        if nbr is None:
+            dW = _wgrad_param(W_param, feats, dout, 1)
+        else:
+            rb = get_rulebook()
+            dW = _wgrad_param(W_param, feats, dout, K, rb.in_idx, rb.out_idx, rb.koff, nbr=nbr)
+    return dfeats, dW, colsum(dout) if need_dbias else None
 
 
 class _ConvDown2(torch.autograd.Function):
@@ -625,11 +650,7 @@ class _ConvDown2(torch.autograd.Function):
             Wt = weight_transpose(W.contiguous(), mirror=False)
             dfeats = pairs_gemm(dout, Wt, rb.out_idx, rb.in_idx, rb.koff, feats.shape[0], feats.shape[0])
         if ctx.needs_input_grad[1]:
-            tgt = _grad_target(ctx.w_param)
-            dW = wgrad(feats, dout, W.shape[0], rb.in_idx, rb.out_idx, rb.koff, into=tgt)
-            if tgt is not None:
-                dW = None
-                _grad_written(ctx.w_param)
+            dW = _wgrad_param(ctx.w_param, feats, dout, W.shape[0], rb.in_idx, rb.out_idx, rb.koff)
         return dfeats, dW, None, None
 
 
@@ -656,11 +677,7 @@ class _ConvTrUp2(torch.autograd.Function):
             Wt = weight_transpose(W.contiguous(), mirror=False)
             dfeats = gather_gemm(dout, Wt, ctx.nbr2, feats.shape[0])
         if ctx.needs_input_grad[1]:
-            tgt = _grad_target(ctx.w_param)
-            dW = wgrad(feats, dout, W.shape[0], rb.out_idx, rb.in_idx, rb.koff, into=tgt)
-            if tgt is not None:
-                dW = None
-                _grad_written(ctx.w_param)
+            dW = _wgrad_param(ctx.w_param, feats, dout, W.shape[0], rb.out_idx, rb.in_idx, rb.koff)
         return dfeats, dW, None, None, None
 
 
@@ -739,22 +756,17 @@ class _BatchNormAct(torch.autograd.Function):
         dy = dy.contiguous()
         n, c = x.shape
         dev = x.device
-        red = torch.empty((4, c), dtype=torch.float32, device=dev)   # dgamma | dbeta | mean_g | mean_gx
+        red = torch.empty((2, c), dtype=torch.float32, device=dev)   # mean_g | mean_gx
         ws = _ws(lib.usc_colstats_ws_bytes(n, c), dev)
-        tg, tb = _grad_target(ctx.gamma_param), _grad_target(ctx.beta_param)
-        in_place = tg is not None and tb is not None
-        dg, db = (tg, tb) if in_place else (red[0], red[1])
+        (dg, db), in_place, finish = _param_grads((ctx.gamma_param, ctx.beta_param))
         check(lib.usc_bn_backward_reduce(_ptr(x), _ptr(dy), _ptr(y), _ptr(mean), _ptr(invstd), n, c,
-                                         int(ctx.training), int(in_place), _ptr(dg), _ptr(db), _ptr(red[2]), _ptr(red[3]),
+                                         int(ctx.training), int(in_place), _ptr(dg), _ptr(db), _ptr(red[0]), _ptr(red[1]),
                                          _ptr(ws), ws.numel(), _stream()), "usc_bn_backward_reduce")
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if ctx.has_res else None
-        check(lib.usc_bn_backward_dx(_ptr(x), _ptr(dy), _ptr(y), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(red[2]),
-                                     _ptr(red[3]), _ptr(dx), _ptr(dres), n, c, _stream()), "usc_bn_backward_dx")
-        if in_place:
-            _grad_written(ctx.gamma_param, ctx.beta_param)
-        return (dx, (None if in_place else red[0]), (None if in_place else red[1]), dres, None, None, None, None, None,
-                None, None)
+        check(lib.usc_bn_backward_dx(_ptr(x), _ptr(dy), _ptr(y), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(red[0]),
+                                     _ptr(red[1]), _ptr(dx), _ptr(dres), n, c, _stream()), "usc_bn_backward_dx")
+        return (dx, *finish(), dres, None, None, None, None, None, None, None)
 
 
 def batch_norm_act(x, gamma, beta, residual=None, relu=False, eps=1e-5, running_mean=None, running_var=None,
@@ -874,10 +886,9 @@ class GradSink:
     leave the others' gradients stranded: checked when the backward pass ends."""
 
     def __init__(self):
-        self.buf, self.pending, self.check_queued = None, 0, False
+        self.buf, self.pending = None, 0
 
     def _check(self):
-        self.check_queued = False
         if self.pending != 0 and self.buf is not None:
             self.buf = None
             raise RuntimeError("GradSink: a consumer's backward did not run; the gradients accumulated for its table were "
@@ -965,9 +976,7 @@ class _SampleKeys(torch.autograd.Function):
             first = sink.buf is None
             if first:
                 sink.buf = torch.zeros((ctx.n_src, c), dtype=torch.float32, device=dfeats.device)
-                if not sink.check_queued:
-                    sink.check_queued = True
-                    torch.autograd.Variable._execution_engine.queue_callback(sink._check)
+                at_end_of_backward(sink, sink._check, outside="skip")
             scatter(sink.buf, add=not first)
             sink.pending -= 1
             if sink.pending > 0:

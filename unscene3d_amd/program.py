@@ -21,11 +21,14 @@ Same kernels and the same arithmetic per unit as units.py (`usc_conv_bn_act_forw
 to that path, gradients equal to rounding (different fan-in order).  Falls back to the per-block path whenever a piece
 is not the plain form: a bias, a Bottleneck block, a parameter without an in-place gradient target, an open profiler
 capture, `USC3D_BACKBONE_PROGRAM=0`.
+A forward pass leaves a `_PassState`; a backward walk's gradient table holds `_Grad` entries; a last stage issued ahead
+(`early_backward`) is an `_EarlyState` until the node's own backward has continued from it.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 
 import torch
 
@@ -241,6 +244,22 @@ def usable(model, x):
 _N_PLAIN_ARGS = 8        # _Trunk.forward's arguments in front of the parameters
 
 
+# What one forward pass of the trunk leaves for its backward walk(s).  cm: coordinate manager; ts: the input's tensor stride;
+# arena: _Carver; ptr: buffer id -> pointer; per op of the plan: stats_ptr (BN statistics), kmaps, bnrefs ((address, usc_bn
+# descriptor)); rows: per level; split: op index -> split-bf16 planes, or None
+_PassState = namedtuple("_PassState", "model plan cm ts feats arena ptr stats_ptr kmaps bnrefs rows split")
+# an entry of a backward walk's gradient table: where the gradient of a buffer stands (read_only: an incoming gradient tensor)
+_Grad = namedtuple("_Grad", "ptr read_only floats")
+
+
+class _EarlyState:
+    """The last stage issued ahead (early_backward), until the trunk node's own backward has continued from it: the graph
+    task it was issued in, its gradient table, what the lane reads, the device index, the stage's parameters as written."""
+
+    def __init__(self, task, G, keep, key, params):
+        self.task, self.G, self.keep, self.key, self.params = task, G, keep, key, params
+
+
 class _Trunk(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, pl, cm, ts, bf16, split, holder, feats, *params):
@@ -304,7 +323,7 @@ class _Trunk(torch.autograd.Function):
         ws = units.workspace(wsb, dev)
         check(lib.usc_program_run(steps, 0, len(pl.ops), ws.data_ptr(), ws.numel(), ops._stream()), "usc_program_run")
         outs = tuple(car.view(offs[b], rows[pl.bufs[b][0]], pl.bufs[b][1]) for b in pl.levels)
-        ctx.state = (model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows, split)
+        ctx.state = _PassState(model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows, split)
         ctx.holder = holder
         if holder is not None:
             holder.state = ctx.state
@@ -312,41 +331,40 @@ class _Trunk(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gouts):
-        holder = ctx.holder
-        model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows, split = ctx.state
-        dev = feats.device
+        holder, state = ctx.holder, ctx.state
+        pl, rows, dev = state.plan, state.rows, state.feats.device
         gar = _Pool(dev, max(rows[0] * 256, 1 << 20))
         lane = units._lane(dev)                  # weight-gradient lane (on by default): its launches read x and dy after
         if lane is not None:                     # this function has moved on -> nothing they read is re-used
             gar.release = lambda p_, n_: None
-            car.arena.record_stream(lane[0])
+            state.arena.arena.record_stream(lane[0])
         keep = [g.contiguous() if g is not None else None for g in gouts]
         early = _take_early(holder)
         stream = ops._stream()
         if early is None:
-            walk = _BackwardWalk(ctx.state, gar, {})
+            walk = _BackwardWalk(state, gar, {})
             for b, g in zip(pl.levels, keep):
                 if g is not None:
-                    walk.G[b] = [g.data_ptr(), True, g.numel()]
+                    walk.G[b] = _Grad(g.data_ptr(), True, g.numel())
             hi = len(pl.ops)
         else:
             # the last stage has been issued on the lane (early_backward): the walk continues from its gradient table behind
             # the event the lane recorded after the stage's chain.  The s1 argument is not used: that stage took its own.
             check(lib.usc_wgrad_lane_wait_chain(stream), "usc_wgrad_lane_wait_chain")
-            walk = _BackwardWalk(ctx.state, gar, early["G"])
+            walk = _BackwardWalk(state, gar, early.G)
             for b, g in zip(pl.levels[:-1], keep[:-1]):
                 if g is None:
                     continue
                 cur = walk.G.get(b)
                 if cur is None:
-                    walk.G[b] = [g.data_ptr(), True, g.numel()]
+                    walk.G[b] = _Grad(g.data_ptr(), True, g.numel())
                 else:                            # the boundary buffer: the early stage's contribution + the decoder's
-                    walk.add_step(cur[0], g.data_ptr(), g.numel())
+                    walk.add_step(cur.ptr, g.data_ptr(), g.numel())
             hi = pl.early_from
             # the stage's parameters are final, and reported only now: the optimizer's early step waits for an event of
             # the lane on ITS stream — the key-preparation stream in the shipped loop, which the decoder's backward needs
-            ops._grad_written(*early["params"])
-            ops._params_final(early["params"])
+            ops._grad_written(*early.params)
+            ops._params_final(early.params)
         walk.emit(hi, 0)
         steps, ns, segments = walk.steps, walk.ns, walk.segments
         wsb = lib.usc_program_ws_bytes(steps, ns)
@@ -383,8 +401,9 @@ class _Trunk(torch.autograd.Function):
             for t in gar.chunks:
                 t.record_stream(lane[0])
             units.queue_lane_join(units._dev_key(dev))
-        if early is not None:
-            _close_early(early, dev)
+        if early is not None:         # the stage's buffers go when the lane has been joined (the join was queued first)
+            _EARLY_OPEN.pop(early.key, None)
+            ops.at_end_of_backward(early, early.keep.clear, outside="skip")
         if holder is not None:
             holder.state = None
         ctx.state = None
@@ -393,14 +412,12 @@ class _Trunk(torch.autograd.Function):
 
 class _BackwardWalk:
     """The reverse walk over the plan as backward steps: the units' backward steps, column splits for the concatenations and
-    fan-in adds where a tensor has several consumers.  `G`: buffer id -> [pointer, read-only (an incoming gradient tensor),
-    floats] — the gradient table, which a walk over the first part of the plan hands to the walk over the rest
+    fan-in adds where a tensor has several consumers.  `G`: buffer id -> _Grad — the gradient table, which a walk over the first part of the plan hands to the walk over the rest
     (early_backward).  `segments`: one (end step, parameters it finished) per U-Net stage."""
 
     def __init__(self, state, gar, G):
         self.state, self.gar, self.G = state, gar, G
-        pl = state[1]
-        self.steps = (Step * (3 * len(pl.ops) + 8))()
+        self.steps = (Step * (3 * len(state.plan.ops) + 8))()
         self.ns = 0
         self.segments = []
 
@@ -411,7 +428,8 @@ class _BackwardWalk:
 
     def emit(self, hi, lo):
         """Steps of pl.ops[lo:hi], last first."""
-        model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows, split = self.state
+        state = self.state
+        pl, ptr, rows, split = state.plan, state.ptr, state.rows, state.split
         G, gar, steps, add_step = self.G, self.gar, self.steps, self.add_step
         held_dy = []                             # dy buffers the current stage's queued weight gradients still read
         cur_params, stage = [], None
@@ -423,17 +441,17 @@ class _BackwardWalk:
             cur = G.get(bid)
             if cur is None:
                 p = gar.take(numel)
-                G[bid] = [p, False, numel]
+                G[bid] = _Grad(p, False, numel)
                 return p, 0, None
-            if can_accumulate and not cur[1]:
-                return cur[0], 1, None
+            if can_accumulate and not cur.read_only:
+                return cur.ptr, 1, None
             p = gar.take(numel)
-            if cur[1]:                           # new buffer = this contribution + the incoming gradient; ours from now on
-                def fin(p=p, old=cur[0]):
+            if cur.read_only:                    # new buffer = this contribution + the incoming gradient; ours from now on
+                def fin(p=p, old=cur.ptr):
                     add_step(p, old, numel)
-                    G[bid] = [p, False, numel]
+                    G[bid] = _Grad(p, False, numel)
             else:
-                def fin(p=p, old=cur[0]):
+                def fin(p=p, old=cur.ptr):
                     add_step(old, p, numel)
                     gar.release(p, numel)
             return p, 0, fin
@@ -441,8 +459,8 @@ class _BackwardWalk:
         def consumed(bid):
             """The gradient of buffer `bid` has been read by its producer's backward step: give the range back."""
             cur = G.pop(bid, None)
-            if cur is not None and not cur[1]:
-                gar.release(cur[0], cur[2])
+            if cur is not None and not cur.read_only:
+                gar.release(cur.ptr, cur.floats)
 
         for i in range(hi - 1, lo - 1, -1):
             op = pl.ops[i]
@@ -461,13 +479,13 @@ class _BackwardWalk:
                 n = rows[op["level"]]
                 pa, _, fa = contribute(op["a"], n * op["ca"], False)
                 cur_b = G.get(op["b"])
-                if cur_b is not None and not cur_b[1]:
-                    pb, acc_b, fb = cur_b[0], 1, None
+                if cur_b is not None and not cur_b.read_only:
+                    pb, acc_b, fb = cur_b.ptr, 1, None
                 else:
                     pb, acc_b, fb = contribute(op["b"], n * op["cb"], False)
                 st = steps[self.ns]
                 self.ns += 1
-                st.op, st.a, st.dst, st.dst2, st.n, st.ca, st.cb, st.accumulate = STEP_SPLIT, g[0], pa, pb, n, op["ca"], \
+                st.op, st.a, st.dst, st.dst2, st.n, st.ca, st.cb, st.accumulate = STEP_SPLIT, g.ptr, pa, pb, n, op["ca"], \
                     op["cb"], acc_b
                 for f in (fa, fb):
                     if f is not None:
@@ -494,11 +512,11 @@ class _BackwardWalk:
             st = steps[self.ns]
             self.ns += 1
             st.op, st.kind, st.cin, st.cout = STEP_UNIT_BWD, op["kind"], cin, cout
-            st.map, st.bn = C.addressof(kmaps[i].struct), bnrefs[i][0]
+            st.map, st.bn = C.addressof(state.kmaps[i].struct), state.bnrefs[i][0]
             st.x, st.W = ptr[op["x"]], conv.kernel.data_ptr()
-            st.y, st.stats = ptr[op["y"]], stats_ptr[i]
+            st.y, st.stats = ptr[op["y"]], state.stats_ptr[i]
             st.out = ptr[op["out"]] if op["relu"] else None
-            st.dout, st.dy, st.dres, st.dx, st.dx_accumulate = g[0], pdy, pres, pdx, acc
+            st.dout, st.dy, st.dres, st.dx, st.dx_accumulate = g.ptr, pdy, pres, pdx, acc
             st.dW, st.dW_accumulate, st.dgamma, st.dbeta, st.dbn_accumulate = tW.data_ptr(), 1, tg.data_ptr(), \
                 tb.data_ptr(), 1
             st.defer_wgrad = int(units.GROUP_WGRAD)
@@ -551,7 +569,7 @@ def early_possible(handle):
         return False
     if ops.GRAD_WRITTEN_HOOK is not None:
         return False
-    return units._lane(handle.state[4].device) is not None
+    return units._lane(handle.state.feats.device) is not None
 
 
 def _early_ws(nbytes, device):
@@ -569,8 +587,8 @@ def early_backward(handle, g_s1, keep=()):
     global EARLY_RUNS
     if not early_possible(handle):
         raise RuntimeError("program.early_backward: not possible for this forward pass (program.early_possible)")
-    model, pl, cm, ts, feats, car, ptr, stats_ptr, kmaps, bnrefs, rows, split = handle.state
-    dev = feats.device
+    state = handle.state
+    pl, rows, dev = state.plan, state.rows, state.feats.device
     lane_st = units._lane(dev)[0]
     key = units._dev_key(dev)
     settle_abandoned(dev)
@@ -581,24 +599,24 @@ def early_backward(handle, g_s1, keep=()):
     # compute stream read them), alive until the lane has been joined
     gar = _Pool(dev, max(rows[0] * 256, 1 << 20))
     gar.release = lambda p_, n_: None
-    walk = _BackwardWalk(handle.state, gar, {pl.levels[-1]: [g.data_ptr(), True, g.numel()]})
+    walk = _BackwardWalk(state, gar, {pl.levels[-1]: _Grad(g.data_ptr(), True, g.numel())})
     walk.emit(len(pl.ops), pl.early_from)
-    car.arena.record_stream(lane_st)
+    state.arena.arena.record_stream(lane_st)
     g.record_stream(lane_st)
     for t in gar.chunks:
         t.record_stream(lane_st)
     ws = _early_ws(lib.usc_program_ws_bytes(walk.steps, walk.ns), dev)
     ws.record_stream(lane_st)
-    state = {"task": ops._graph_task(), "G": walk.G, "keep": [gar, g, walk.steps, ws, handle.state, list(keep)], "key": key,
-             "params": [p for _, plist in walk.segments for p in plist]}
-    _EARLY_OPEN[key] = state
+    early = _EarlyState(ops._graph_task(), walk.G, [gar, g, walk.steps, ws, state, list(keep)], key,
+                        [p for _, plist in walk.segments for p in plist])
+    _EARLY_OPEN[key] = early
     try:
         check(lib.usc_program_run_lane(walk.steps, 0, walk.ns, ws.data_ptr(), ws.numel(), ops._stream()),
               "usc_program_run_lane")
     except BaseException:
         lib.usc_wgrad_lane_hold(-1, 0, 0, None)
         raise
-    handle.early = state
+    handle.early = early
     EARLY_RUNS += 1
     units.queue_lane_join(key)
 
@@ -608,17 +626,9 @@ def _take_early(holder):
     if early is None:
         return None
     holder.early = None
-    if early["task"] >= 0 and early["task"] != ops._graph_task():      # (< 0: issued by a direct call, outside any pass)
+    if early.task >= 0 and early.task != ops._graph_task():      # (< 0: issued by a direct call, outside any pass)
         raise RuntimeError("step program: the last stage was issued ahead in another backward pass than this one")
     return early
-
-
-def _close_early(early, dev):
-    """The continuation has been issued: the stage's buffers go when the lane has been joined (the join was queued first)."""
-    _EARLY_OPEN.pop(early["key"], None)
-    kept = early["keep"]
-    if ops._graph_task() >= 0:
-        torch.autograd.Variable._execution_engine.queue_callback(kept.clear)
 
 
 def settle_abandoned(device=None):
@@ -633,8 +643,8 @@ def settle_abandoned(device=None):
     lib.usc_wgrad_lane_hold(-1, 0, 0, None)
     with torch.cuda.device(key):
         units.join_lane()
-    state["G"] = None
-    state["keep"].clear()
+    state.G = None
+    state.keep.clear()
     return True
 
 

@@ -10,6 +10,8 @@ input-gradient kernel itself (`dx_accumulate`) instead of a separate element-wis
 Same kernels, same kernel choice and the same arithmetic as the per-operator path; that path stays for odd cases
 (bias, non-default USC3D_CONV, an open profiler capture, CPU-side hooks on the parameters) and as the A/B
 reference of the tests (USC3D_NATIVE_UNITS=0).
+Parameter gradients go where ops._param_grads says; the lane's join and the grouped weight-gradient queue's last flush
+are queued once per backward pass by ops.at_end_of_backward.
 """
 from __future__ import annotations
 
@@ -51,7 +53,6 @@ SAME, DOWN, UP = 0, 1, 2
 # stride-16 level).  USC3D_GROUP_WGRAD=0 switches it off (A/B, and the bit-equality tests against the per-operator path).
 GROUP_WGRAD = os.environ.get("USC3D_GROUP_WGRAD", "1") == "1"
 _LANE = {}     # device index -> (stream, scratch tensor) handed to usc_set_wgrad_lane, or None
-_LANE_JOIN_QUEUED = {}     # device index -> id of the graph task whose end-of-backward lane join has been queued
 
 
 def _dev_key(device=None):
@@ -124,23 +125,13 @@ def lane_event(device=None, release=True):
     return ev
 
 
-def _join_lane_after_backward(key):
-    _LANE_JOIN_QUEUED.pop(key, None)
-    with torch.cuda.device(key):
-        join_lane()
-
-
 def queue_lane_join(key):
-    """Queue ONE lane join at the end of the running backward pass.  Keyed on the graph task (ops._graph_task): after a
-    backward pass that raised — the engine drops its callbacks then — the next pass queues its own join again."""
-    task = ops._graph_task()
-    if task < 0:                       # not inside a backward pass (a direct call of a backward function): join now
+    """ONE join of device `key`'s lane at the end of the running backward pass (ops.at_end_of_backward, keyed on the lane's
+    stream); outside a pass — a direct call of a backward function — the join happens now."""
+    def join():
         with torch.cuda.device(key):
             join_lane()
-        return
-    if _LANE_JOIN_QUEUED.get(key) != task:
-        _LANE_JOIN_QUEUED[key] = task
-        torch.autograd.Variable._execution_engine.queue_callback(lambda: _join_lane_after_backward(key))
+    ops.at_end_of_backward(_LANE[key][0], join, outside="run")
 
 
 def _lane_hold(device, n_in, n_out, in_place_dW, *tensors):
@@ -189,27 +180,21 @@ class _WgradQueue:
     """Deferred same-shape weight gradients of the running backward pass (one queue per device)."""
 
     def __init__(self):
-        self.key, self.items, self.task = None, [], None
+        self.key, self.items = None, []
 
     def push(self, key, kmap, x, dy, W_param, dW):
-        task = ops._graph_task()
-        if self.task is not None and task != self.task:
+        if self.items and not ops.queued_at_end_of_backward(self):
             # left behind by a backward pass that raised (the engine drops its callbacks then): those gradients belong
             # to a pass that never finished
-            self.items, self.key, self.task = [], None, None
+            self.items, self.key = [], None
         if self.key is not None and key != self.key:
             self.flush()
         self.key = key
         self.items.append((kmap, x, dy, W_param, dW))
-        if len(self.items) >= _group_max() or task < 0:
+        if len(self.items) >= _group_max():
             self.flush()
-        elif self.task is None:
-            self.task = task
-            torch.autograd.Variable._execution_engine.queue_callback(self._end_of_backward)
-
-    def _end_of_backward(self):
-        self.task = None
-        self.flush()
+        else:
+            ops.at_end_of_backward(self, self.flush, outside="run")     # (outside a pass: flushed now)
 
     def flush(self):
         items, key = self.items, self.key
@@ -381,21 +366,17 @@ def unit_backward(x, W3, bn, kmap, kind, y, stats, out_relu, dout, dy_buf, want_
     if need_dx and dx is None:
         dx = torch.empty((n_in, cin), dtype=torch.float32, device=dev)
         dx_accumulate = False
-    tW = ops._grad_target(W_param)
-    _lane_hold(dev, n_in, n_out, tW is not None, x, dy_buf)
-    tg, tb = ops._grad_target(g_param), ops._grad_target(b_param)
-    bn_in_place = tg is not None and tb is not None
-    dW = tW if tW is not None else torch.empty(W_param.shape, dtype=torch.float32, device=dev)
-    dg = tg if bn_in_place else torch.empty(cout, dtype=torch.float32, device=dev)
-    db = tb if bn_in_place else torch.empty(cout, dtype=torch.float32, device=dev)
+    (dW,), W_in_place, finish_W = ops._param_grads((W_param,))
+    _lane_hold(dev, n_in, n_out, W_in_place, x, dy_buf)
+    (dg, db), bn_in_place, finish_bn = ops._param_grads((g_param, b_param))
     _, bref = _bn_desc(bn, _training(bn))
     wsb = _split_ws_bytes(kmap, kind, cin, cout, planes) if planes else lib.usc_unit_ws_bytes(kmap.ref, kind, cin, cout)
     ws = workspace(wsb, dev)
-    defer = defer_ok and _defer_wgrad(kmap, kind, cin, cout, tW is not None)
+    defer = defer_ok and _defer_wgrad(kmap, kind, cin, cout, W_in_place)
     tail = (bref, y.data_ptr(), stats.data_ptr(), None if out_relu is None else out_relu.data_ptr(),
             dout.data_ptr(), dy_buf.data_ptr(), None if dres is None else dres.data_ptr(),
             dx.data_ptr() if need_dx else None, int(bool(dx_accumulate)), None if defer else dW.data_ptr(),
-            int(tW is not None), dg.data_ptr(), db.data_ptr(), int(bn_in_place), ws.data_ptr(), ws.numel(), ops._stream())
+            int(W_in_place), dg.data_ptr(), db.data_ptr(), int(bn_in_place), ws.data_ptr(), ws.numel(), ops._stream())
     if planes:
         check(lib.usc_conv_bn_act_backward_split(kmap.ref, kind, x.data_ptr(), cin, W3.data_ptr(), cout, planes, *tail),
               "usc_conv_bn_act_backward_split")
@@ -404,14 +385,11 @@ def unit_backward(x, W3, bn, kmap, kind, y, stats, out_relu, dout, dy_buf, want_
               "usc_conv_bn_act_backward")
     if defer:
         # queued: x and this unit's OWN dy stay referenced until the grouped launch; the write is reported then
-        _wgrad_queue(dev).push((id(kmap), cin, cout), kmap, x, dy_buf, W_param, tW)
+        _wgrad_queue(dev).push((id(kmap), cin, cout), kmap, x, dy_buf, W_param, dW)
         dW = None
-    elif tW is not None:
-        ops._grad_written(W_param)
-        dW = None
-    if bn_in_place:
-        ops._grad_written(g_param, b_param)
-        dg = db = None
+    else:
+        (dW,) = finish_W()
+    dg, db = finish_bn()
     return (dx if need_dx else None), dres, dW, dg, db
 
 
