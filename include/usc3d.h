@@ -1595,6 +1595,46 @@ int usc_mask_bits_to_columns(const uint64_t* bits, const int32_t* rows, int32_t 
 int usc_mask_bits_to_columns_u8(const uint64_t* bits, const int32_t* rows, int32_t m, int64_t n, uint8_t* out,
                                 int64_t ld, int32_t col0, usc_stream_t s);
 
+/* ------------------------------------------------------------------------
+ * general.separate_instances of the export step (csrc/separate.hip; reference
+ * trainer/trainer.py:609-650, utils/point_cloud_utils.py:82-121): a kept
+ * instance is cut into its connected parts on the segment adjacency.  Explicit
+ * stream, no allocation, no float, no read-modify-write atomics; every output
+ * element has one writer: two runs give the same bytes.
+ *
+ * usc_mask_columns_to_segment_bits (:626-629, np.unique of the masked ids per
+ *   instance): masks u8[n,k] row-major (non-zero = set); order i64[n], seg_off
+ *   i64[S+1] = the points sorted by segment index (usc_segment_csr).  bits
+ *   u64[k, ceil(S/64)] in the layout of usc_freemask_bits: bit s of row j = OR
+ *   of masks[p,j] over the points p of segment s; bits at positions >= S are
+ *   zero, every word is written.  The CALLER checks the CSR (seg_off rises
+ *   from 0 to n, order is a permutation); a broken one gives wrong bits but no
+ *   read outside the arrays: offsets are clamped to [0, n] and an entry of order
+ *   outside [0, n) is read as point 0.  k = 0 is valid.
+ * usc_mask_bits_components_wide (:632, separate_segments): the contract and
+ *   the labels of usc_mask_bits_components for S up to
+ *   USC_MASK_BITS_MAX_SEGMENTS_WIDE (= usc_mask_bits_max_segments_wide()): one
+ *   workgroup per row, the row of `label` is the work array (global memory).
+ *   The round loop stops after S + 1 rounds; a correct run is quiet after at
+ *   most S.  Reaching the bound sets *status (device i32[1], zeroed here), and
+ *   the call, which waits for the stream to read it, returns USC_ERR_RANGE.
+ *   Above the cap a round of one workgroup over a row is too long: refused.
+ * usc_segment_parts_to_columns (:639, np.isin per part): out u8[n, n_parts],
+ *   out[r * n_parts + p] = (label[src[p] * S + idx[r]] == root[p]); label
+ *   i32[n_rows, S], src in [0, n_rows), idx i32[n] in [0, S): the CALLER checks
+ *   both.  n = 0 and n_parts = 0 are valid.
+ * ---------------------------------------------------------------------- */
+#define USC_MASK_BITS_MAX_SEGMENTS_WIDE 65536
+int32_t usc_mask_bits_max_segments_wide(void);
+int usc_mask_columns_to_segment_bits(const uint8_t* masks, int64_t n, int32_t k, const int64_t* order,
+                                     const int64_t* seg_off, int32_t n_segments, uint64_t* bits, usc_stream_t s);
+int usc_mask_bits_components_wide(const uint64_t* bits, int64_t n_bits_rows, int32_t n_segments, const int32_t* rows,
+                                  int32_t n_rows, const int64_t* adj_off, const int32_t* adj, int32_t* label,
+                                  int32_t* n_comp, int32_t* status, usc_stream_t s);
+int usc_segment_parts_to_columns(const int32_t* label, int32_t n_rows, int32_t n_segments, const int32_t* src,
+                                 const int32_t* root, int32_t n_parts, const int32_t* idx, int64_t n, uint8_t* out,
+                                 usc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

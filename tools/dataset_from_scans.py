@@ -29,6 +29,9 @@ def main(argv=None):
     ap.add_argument("--val", default=None, metavar="FILE", help="scan names of the validation split")
     ap.add_argument("--oracle", action="store_true", help="one-hot ground-truth masks instead of pseudo masks")
     ap.add_argument("--segments-min-verts", type=int, default=20, help="over-segmentation when a scan has no segs.json")
+    ap.add_argument("--write-connectivity", action="store_true",
+                    help="also store the over-segmentation's segment pairs ({scene}_connectivity.npy) for the export "
+                         "step's general.separate_instances")
     args = ap.parse_args(argv)
     if not args.oracle and args.pseudo is None:
         ap.error("--pseudo is needed unless --oracle is given")
@@ -46,7 +49,7 @@ def main(argv=None):
         splits["train"] = sorted(e for e in os.listdir(args.scans) if os.path.isdir(os.path.join(args.scans, e)))
     device = torch.device("cuda", torch.cuda.current_device())
     databases = build_dataset(args.scans, splits, args.pseudo, args.out, oracle=args.oracle, device=device,
-                              segments_min_verts=args.segments_min_verts)
+                              segments_min_verts=args.segments_min_verts, write_connectivity=args.write_connectivity)
     print(json.dumps({"out": args.out, "scans": {mode: len(db) for mode, db in databases.items()}}))
     return 0
 

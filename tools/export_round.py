@@ -12,7 +12,10 @@ the weights of a `TrainLoop` checkpoint (tools/train.py --out RUN).  SELF_TRAIN/
 
 The model is built as tools/train.py --data-dir builds it (general.num_targets=3, loss.device_max_targets=128); --set
 takes `a.b=value` overrides of `default_config()`, e.g. the reference's export recipe
-`--set general.filter_out_instances=true general.scores_threshold=0.1 general.topk_per_image=100`."""
+`--set general.filter_out_instances=true general.scores_threshold=0.1 general.topk_per_image=100`.  With
+`general.separate_instances=true` (and filter_out_instances) the reader re-segments every scene's mesh, or reads the
+connectivity file tools/dataset_from_scans.py --write-connectivity stored, and every kept instance is exported as its
+connected parts on that segmentation."""
 import argparse
 import json
 import os
@@ -48,7 +51,9 @@ def main():
     stats = load_color_mean_std(os.path.join(a.data_dir, "color_mean_std.yaml"))
     entries = entries_from_database(os.path.join(a.data_dir, f"{a.split}_database.yaml"))
     scenes = FreeMaskSceneReader(entries, mode="validation", color_mean_std=stats, add_normals=False,
-                                 add_raw_coordinates=True, device=str(dev), device_tables=True)
+                                 add_raw_coordinates=True, device=str(dev), device_tables=True,
+                                 resegment_mesh=bool(cfg.data.resegment_mesh),
+                                 segment_min_vert_num=cfg.data.segment_min_vert_num)
     report = export_round(module, cfg, scenes, a.out, fmt=a.fmt, device=dev)
     torch.cuda.synchronize()
     from unscene3d_amd import _lib

@@ -163,7 +163,9 @@ def train_on_data_dir(a, cfg, module, dev, world, rank):
     val = val_ids = None
     val_db, gt_dir = os.path.join(d, "validation_database.yaml"), os.path.join(d, "instance_gt", "validation")
     if os.path.exists(val_db) and os.path.isdir(gt_dir):
-        val = FreeMaskSceneReader(entries_from_database(val_db), mode="validation", **common)
+        val = FreeMaskSceneReader(entries_from_database(val_db), mode="validation",
+                                  resegment_mesh=bool(getattr(cfg.data, "resegment_mesh", False)),
+                                  segment_min_vert_num=getattr(cfg.data, "segment_min_vert_num", 20), **common)
         names = [val._scene_name(i) for i in range(len(val))]
         val_ids = {n: load_gt_ids(os.path.join(gt_dir, f"{n}.txt")) for n in names}
     if a.out:

@@ -265,6 +265,10 @@ SIGNATURES = {
     "usc_selftrain_merge": (C.c_int, [_p, _p, _i32, _i64, _p, _i32, _p, _p, _p, _p]),
     "usc_mask_bits_to_columns": (C.c_int, [_p, _p, _i32, _i64, _p, _i64, _i32, _p]),
     "usc_mask_bits_to_columns_u8": (C.c_int, [_p, _p, _i32, _i64, _p, _i64, _i32, _p]),
+    "usc_mask_bits_max_segments_wide": (_i32, []),
+    "usc_mask_columns_to_segment_bits": (C.c_int, [_p, _i64, _i32, _p, _p, _i32, _p, _p]),
+    "usc_mask_bits_components_wide": (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _p, _p, _p]),
+    "usc_segment_parts_to_columns": (C.c_int, [_p, _i32, _i32, _p, _p, _i32, _p, _i64, _p, _p]),
 }
 
 

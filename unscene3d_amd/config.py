@@ -24,6 +24,9 @@ def default_config():
                     # export between self-training rounds (conf/config_base_instance_segmentation.yaml:12-44)
                     "filter_out_instances": False, "scores_threshold": 0.1, "iou_threshold": 0.66,
                     "topk_per_image": 100, "save_for_freemask": False, "save_dir": "saved",
+                    # cut every instance the overlap filter keeps into its connected parts on the mesh
+                    # over-segmentation's adjacency (trainer/separate.py; needs filter_out_instances)
+                    "separate_instances": False,
                     # mask files of save_for_freemask: "npy" (bool [N,K], the reference's), "bits" (u64 bit rows,
                     # `{name}_masks_bits.npy`, packed on the device) or "both"
                     "freemask_format": "npy",
@@ -35,7 +38,12 @@ def default_config():
                     "train_precision": "f32"},
         "data": {"voxel_size": 0.02, "in_channels": 3, "num_labels": 20, "add_raw_coordinates": True,
                  "add_colors": True, "add_normals": False, "ignore_label": 255, "batch_size": 8,
-                 "test_mode": "validation"},          # conf/data/indoor.yaml:9 ("test": eval_step skips the criterion)
+                 "test_mode": "validation",           # conf/data/indoor.yaml:9 ("test": eval_step skips the criterion)
+                 # the validation reader re-segments the scene's mesh and hands its connectivity on
+                 # (conf/data/indoor.yaml: resegment_mesh: ${general.separate_instances}: apply_overrides derives it
+                 # from that flag unless `data.resegment_mesh=...` is given; tools/train.py and tools/export_round.py
+                 # build their validation readers from this key)
+                 "resegment_mesh": False, "segment_min_vert_num": 20},
         "model": {"hidden_dim": 128, "dim_feedforward": 1024, "num_queries": 100, "num_heads": 8, "num_decoders": 3,
                   "dropout": 0.0, "pre_norm": False, "use_level_embed": False, "normalize_pos_enc": True,
                   "positional_encoding_type": "fourier", "gauss_scale": 1.0, "hlevels": [0, 1, 2, 3],
@@ -83,6 +91,9 @@ def apply_overrides(cfg, overrides):
     cfg.model.train_on_segments = cfg.general.train_on_segments
     cfg.loss.num_points = cfg.matcher.num_points
     cfg.model.voxel_size = cfg.data.voxel_size
+    # resegment_mesh: ${general.separate_instances} — like the YAML's interpolation, an explicit override of the key wins
+    if not any(ov.partition("=")[0] == "data.resegment_mesh" for ov in overrides):
+        cfg.data.resegment_mesh = bool(getattr(cfg.general, "separate_instances", False))
     return cfg
 
 

@@ -203,6 +203,8 @@ class FreeMaskSceneReader:
     """Validation-mode `SemanticSegmentationFreeDataset.__getitem__`: `{scene}.npy` ([N,12]: xyz, rgb, normal,
     segment id, 2 unused) + `{scene}_freemasks.npy` ([N,K] soft masks) -> the 9-tuple
     (coordinates, features, freemasks+segments, scene_name, raw_color, raw_normals, raw_coordinates, idx, []).
+    `resegment_mesh` (validation mode, both table paths): the segment column and the last field (int32[P,2] instead of
+    []) come from the over-segmentation of the entry's mesh, see `segment_mesh`.
     `device_tables`: item 2 is built by `mask_tables_device` and returned as a device int32 tensor (the collate takes
     it as it is); same values, same random draws (the table path draws none)."""
 
@@ -211,7 +213,7 @@ class FreeMaskSceneReader:
                  max_num_gt_instances=-1, load_self_train_data=False, self_train_data_dir=None, num_self_train_data=5,
                  device="cuda", mode="validation", volume_augmentations=None, image_augmentations=None,
                  is_elastic_distortion=True, flip_in_center=False, color_drop=0.0, point_per_cut=0, resample_points=0,
-                 noise_rate=0, device_tables=False):
+                 noise_rate=0, device_tables=False, resegment_mesh=False, segment_min_vert_num=20):
         self.data = list(entries)                      # dicts with "filepath" and "raw_filepath" (the database yaml)
         self.color_mean = np.asarray(color_mean_std[0], np.float32) * 255.0
         self.color_den = np.reciprocal(np.asarray(color_mean_std[1], np.float32) * 255.0)
@@ -223,6 +225,7 @@ class FreeMaskSceneReader:
         self.self_train_data_dir = self_train_data_dir
         self.num_self_train_data = num_self_train_data
         self.device, self.device_tables = device, bool(device_tables)
+        self.resegment_mesh, self.segment_min_vert_num = bool(resegment_mesh), int(segment_min_vert_num)
         self.mode, self.is_elastic_distortion, self.color_drop = mode, is_elastic_distortion, color_drop
         # objects with a `transforms` attribute, called like the reference's (volumentations / albumentations Compose);
         # datasets.augment.VolumeAugmentations() / ColorAugmentations() are the shipped YAML pipelines
@@ -265,8 +268,11 @@ class FreeMaskSceneReader:
         if self.max_num_gt_instances > 0:
             freemasks = freemasks[:, :self.max_num_gt_instances]
         coordinates, color, normals, segments = points[:, :3], points[:, 3:6], points[:, 6:9], points[:, 9]
+        connectivity = []
+        if self.resegment_mesh and "train" not in self.mode:        # freemask_semseg.py:302-303
+            segments, connectivity = self.segment_mesh(idx, coordinates, segments)
         if self.device_tables:
-            return self._item_device_tables(idx, path, coordinates, color, normals, segments, freemasks)
+            return self._item_device_tables(idx, path, coordinates, color, normals, segments, freemasks, connectivity)
         keep = filter_by_extent(coordinates, freemasks, self.freemask_hard_threshold, self.freemask_extent_max_ratio,
                                 self.device)
         if not keep:
@@ -289,9 +295,41 @@ class FreeMaskSceneReader:
         freemasks = np.hstack((freemasks, segments[..., None].astype(freemasks.dtype))).astype(np.int32)
         raw = self.data[idx]["raw_filepath"]
         scene_name = f"scene{raw.split('/')[-1].split('_')[0]}" if "arkit" in raw.lower() else raw.split("/")[-2]
-        return coordinates, features, freemasks, scene_name, raw_color, raw_normals, raw_coordinates, idx, []
+        return coordinates, features, freemasks, scene_name, raw_color, raw_normals, raw_coordinates, idx, connectivity
 
-    def _item_device_tables(self, idx, path, coordinates, color, normals, segments, freemasks):
+    def segment_mesh(self, idx, coordinates, segments):
+        """`resegment_mesh` (freemask_semseg.py:192-221): -> (segment id per point, connectivity int32[P,2]) from
+        `felzenszwalb_cpp.segment_mesh(vertices, faces, colors, 0.005, segment_min_vert_num)` on the entry's
+        `raw_filepath` mesh (numpy PLY reader); the ids go to the points through their exact nearest vertex when the
+        counts differ.  An entry that names a `connectivity_filepath` written with the same `segments_min_verts`
+        (datasets/preprocessing.py, write_connectivity) has that segmentation in its segment column already: the file
+        is used and nothing is segmented.  An empty or unreadable mesh keeps the stored ids and gives [] with a message
+        (the reference prints the same message and then fails on unpacking None)."""
+        from .. import felzenszwalb_cpp
+        from ..pseudo_masks import scans
+
+        entry = self.data[idx]
+        stored = entry.get("connectivity_filepath")
+        if stored and int(entry.get("segments_min_verts", -1)) == self.segment_min_vert_num and os.path.exists(stored):
+            return segments, np.load(stored).astype(np.int32).reshape(-1, 2)
+        mesh_path = entry["raw_filepath"]
+        try:
+            vertices, colors, faces = scans.read_ply_mesh(mesh_path)
+        except (OSError, ValueError) as e:
+            print(f"Can't segment mesh at {mesh_path}: {e}")
+            return segments, []
+        if len(vertices) == 0:
+            print(f"Can't segment mesh as it is empty at {mesh_path}")
+            return segments, []
+        dev = torch.device(self.device)
+        seg, conn = felzenszwalb_cpp.segment_mesh(vertices, faces, colors, 0.005, self.segment_min_vert_num, device=dev)
+        if coordinates.shape[0] != vertices.shape[0]:
+            _, ind = ops.knn1(torch.as_tensor(np.ascontiguousarray(coordinates, dtype=np.float32), device=dev),
+                              torch.as_tensor(np.ascontiguousarray(vertices, dtype=np.float32), device=dev))
+            seg = seg[ind.cpu().numpy().reshape(-1)]
+        return seg, conn
+
+    def _item_device_tables(self, idx, path, coordinates, color, normals, segments, freemasks, connectivity):
         """`__getitem__` from the extent filter on, with the mask table built on the device, segment column included."""
         table, keep = mask_tables_device(coordinates, freemasks, segments, self.freemask_hard_threshold,
                                          self.freemask_extent_max_ratio, self.device)
@@ -308,7 +346,8 @@ class FreeMaskSceneReader:
             features = np.hstack((features, normals))
         if self.add_raw_coordinates:
             features = np.hstack((features, coordinates))
-        return coordinates, features, table, self._scene_name(idx), raw_color, raw_normals, raw_coordinates, idx, []
+        return (coordinates, features, table, self._scene_name(idx), raw_color, raw_normals, raw_coordinates, idx,
+                connectivity)
 
     def _scene_name(self, idx):
         raw = self.data[idx]["raw_filepath"]

@@ -120,6 +120,8 @@ def build_scene_tables(scan_dir, pseudo_dir, oracle=False, device="cuda", foregr
     conf/data/indoor.yaml:47), label, instance (`scene_labels`; without ground-truth files 0 and -1).
     gt = label * 1000 + instance + 1.  color_mean / color_std: mean of c / 255 and of (c / 255)^2 per channel in f64
     (:162-171; "std" is the second moment, `color_mean_std` turns it into a deviation).
+    connectivity: int32[P,2], the over-segmentation's directed segment pairs, or None when the segment ids came from a
+    segs.json (which carries no adjacency).
     freemasks: the pseudo masks at the nearest cloud point of every vertex aligned with axisAlignment; `oracle=True`:
     one column per ground-truth instance i in range(number of instance ids), set where instance == i (:188-192)."""
     from .. import felzenszwalb_cpp
@@ -149,15 +151,15 @@ def build_scene_tables(scan_dir, pseudo_dir, oracle=False, device="cuda", foregr
     seg_path = _first(os.path.join(glob.escape(scan_dir), "*[0-9].segs.json"))
     agg_path = _first(os.path.join(glob.escape(scan_dir), "*.aggregation.json"))
     label_path = mesh_path.replace(".ply", ".labels.ply")
-    segments = None
+    segments = connectivity = None
     if seg_path is not None:
         segments = np.array(_read_json(seg_path)["segIndices"])
         if segments.shape != (vertices.shape[0],):
             raise ValueError(f"{seg_path}: {segments.shape[0]} segIndices for {vertices.shape[0]} vertices")
         segment_ids = np.unique(segments, return_inverse=True)[1].reshape(-1)
     else:
-        segment_ids, _ = felzenszwalb_cpp.segment_mesh(v_d, f_d, torch.from_numpy(colors01).to(dev), 0.005,
-                                                       int(segments_min_verts), device=dev)
+        segment_ids, connectivity = felzenszwalb_cpp.segment_mesh(v_d, f_d, torch.from_numpy(colors01).to(dev), 0.005,
+                                                                  int(segments_min_verts), device=dev)
     has_gt = agg_path is not None and os.path.exists(label_path)
     if has_gt:
         if segments is None:
@@ -184,7 +186,7 @@ def build_scene_tables(scan_dir, pseudo_dir, oracle=False, device="cuda", foregr
 
     mean, second = color_moments(features[:, :3])
     return {"points": points.astype(np.float32), "freemasks": freemasks, "gt": gt, "color_mean": mean, "color_std": second,
-            "raw_filepath": mesh_path, "raw_description_filepath": info_path, "raw_instance_filepath": agg_path,
+            "connectivity": connectivity, "raw_filepath": mesh_path, "raw_description_filepath": info_path, "raw_instance_filepath": agg_path,
             "raw_segmentation_filepath": seg_path, "raw_label_filepath": label_path if has_gt else None}
 
 
@@ -211,10 +213,14 @@ def save_yaml(path, obj):
 
 
 def build_dataset(scans_root, split_files, pseudo_dir, out_dir, oracle=False, device="cuda",
-                  foreground_ids=FOREGROUND_CLASS_IDS, segments_min_verts=20):
+                  foreground_ids=FOREGROUND_CLASS_IDS, segments_min_verts=20, write_connectivity=False):
     """`split_files`: {mode: text file with one scan name per line} (ScanNet's scannetv2_train.txt / _val.txt), or
     {mode: list of names}.  Every scan `scans_root/<name>` of a mode goes through `build_scene_tables`; scans without
     pseudo-mask files are skipped with a message.  Writes the files the module docstring lists.
+    `write_connectivity`: a scan whose segment ids come from the over-segmentation also gets
+    `{mode}/0000_00_connectivity.npy` (int32[P,2]) and the entry keys `connectivity_filepath` and
+    `segments_min_verts`, which spare `FreeMaskSceneReader(resegment_mesh=True)` its per-item segmentation; a scan
+    with a segs.json has no adjacency to store and says so.
     -> {mode: list of database entries}."""
     out_dir = os.fspath(out_dir)
     os.makedirs(out_dir, exist_ok=True)
@@ -247,6 +253,13 @@ def build_dataset(scans_root, split_files, pseudo_dir, out_dir, oracle=False, de
                         "raw_label_filepath"):
                 if t[key] is not None:
                     entry[key] = t[key]
+            if write_connectivity and t["connectivity"] is not None:
+                conn_path = path.replace(".npy", "_connectivity.npy")
+                np.save(conn_path, np.asarray(t["connectivity"], np.int32).reshape(-1, 2))
+                entry["connectivity_filepath"] = conn_path
+                entry["segments_min_verts"] = int(segments_min_verts)
+            elif write_connectivity:
+                print(f"{name}: segment ids come from {t['raw_segmentation_filepath']}, no connectivity to write")
             if t["gt"] is not None:
                 gt_path = os.path.join(out_dir, "instance_gt", mode, f"scene{scene:04}_{sub:02}.txt")
                 os.makedirs(os.path.dirname(gt_path), exist_ok=True)

@@ -1449,6 +1449,63 @@ def mask_bits_to_columns(bits: torch.Tensor, n: int, rows=None, out: torch.Tenso
     return ret
 
 
+# ------------------------------------------------------------------ separate_instances (csrc/separate.hip)
+def mask_columns_to_segment_bits(masks: torch.Tensor, csr: SegmentCSR, check_range: bool = True) -> torch.Tensor:
+    """masks bool / uint8 [N>=1, K] (non-zero = set), csr = `segment_csr(idx, S)` of the points' segment indices
+    -> bits i64[K, ceil(S/64)]: bit s of row j is set when any point of segment s has column j set.
+    The CSR's values are checked here before the launch (seg_off rises from 0 to N, order within [0, N): host reads);
+    `check_range=False`: the caller vouches for them (a CSR that `segment_csr` just built)."""
+    require_device()
+    if isinstance(masks, torch.Tensor) and masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    _chk(masks, torch.uint8, "masks")
+    if masks.dim() != 2 or masks.shape[0] < 1:
+        raise RuntimeError("mask_columns_to_segment_bits: masks must be bool or uint8 [N>=1, K]")
+    N, K = masks.shape
+    S = int(csr.S)
+    _chk(csr.order, torch.int64, "csr.order")
+    _chk(csr.seg_off, torch.int64, "csr.seg_off")
+    if csr.order.shape != (N,) or csr.seg_off.shape != (S + 1,):
+        raise RuntimeError(f"mask_columns_to_segment_bits: the CSR must cover the {N} rows of masks (order i64[{N}], "
+                           f"seg_off i64[{S + 1}])")
+    if check_range:
+        off = csr.seg_off.cpu()
+        if int(off[0]) != 0 or int(off[-1]) != N or bool((off[1:] < off[:-1]).any()):
+            raise RuntimeError(f"mask_columns_to_segment_bits: csr.seg_off must rise from 0 to {N}")
+        lo, hi = torch.aminmax(csr.order)
+        if int(lo) < 0 or int(hi) >= N:
+            raise RuntimeError(f"mask_columns_to_segment_bits: csr.order outside [0, {N})")
+    bits = torch.empty((K, _bit_words(S)), dtype=torch.int64, device=masks.device)
+    if K:
+        check(lib.usc_mask_columns_to_segment_bits(_ptr(masks), N, K, _ptr(csr.order), _ptr(csr.seg_off), S,
+                                                   _ptr(bits), _stream()), "usc_mask_columns_to_segment_bits")
+    return bits
+
+
+def segment_parts_to_columns(label: torch.Tensor, src: torch.Tensor, root: torch.Tensor, idx: torch.Tensor,
+                             check_range: bool = True) -> torch.Tensor:
+    """label i32[n, S] (`mask_components`), parts (src i32[R] in [0, n), root i32[R]), idx i32[N] in [0, S)
+    -> bool[N, R]: out[r, p] = (label[src[p], idx[r]] == root[p]).  src and idx are checked here (host reads;
+    `check_range=False`: the caller vouches for them)."""
+    require_device()
+    for t, name in ((label, "label"), (src, "src"), (root, "root"), (idx, "idx")):
+        _chk(t, torch.int32, name)
+    if label.dim() != 2 or label.shape[1] < 1 or src.dim() != 1 or root.shape != src.shape or idx.dim() != 1:
+        raise RuntimeError("segment_parts_to_columns: needs label i32[n, S>=1], src i32[R], root i32[R], idx i32[N]")
+    n, S = label.shape
+    R, N = src.shape[0], idx.shape[0]
+    if check_range:
+        if R and (int(src.min()) < 0 or int(src.max()) >= n):
+            raise RuntimeError(f"segment_parts_to_columns: src outside [0, {n})")
+        if N and (int(idx.min()) < 0 or int(idx.max()) >= S):
+            raise RuntimeError(f"segment_parts_to_columns: idx outside [0, {S})")
+    out = torch.empty((N, R), dtype=torch.uint8, device=label.device)
+    if N and R:
+        check(lib.usc_segment_parts_to_columns(_ptr(label), n, S, _ptr(src), _ptr(root), R, _ptr(idx), N, _ptr(out),
+                                               _stream()), "usc_segment_parts_to_columns")
+    return out.view(torch.bool)
+
+
 def mesh_vertex_normals(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     """Area-weighted vertex normals of a triangle mesh (vertices f32[V,3], faces i32[F,3]) -> f32[V,3]: the sum of the
     unnormalised face normals (v1-v0)x(v2-v0) over a vertex's faces in ascending face order, in f64, normalised; a

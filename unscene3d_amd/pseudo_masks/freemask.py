@@ -306,10 +306,12 @@ class SplitRows(NamedTuple):
     soft_sums: torch.Tensor   # f32[R]  sum of the soft values over the part, ascending segment index
 
 
-def segment_adjacency(seg_connectivity, unique_segments):
+def segment_adjacency(seg_connectivity, unique_segments, mutual=False):
     """CSR (adj_off i64[S+1], adj i32[E]) of the undirected segment adjacency over the indices of the sorted ids
     `unique_segments` i64[S]: pairs mapped to indices, pairs naming an id that is not in `unique_segments` and self
-    pairs dropped, symmetrised, deduplicated, neighbours ascending (torch operators, once per scene)."""
+    pairs dropped, symmetrised, deduplicated, neighbours ascending (torch operators, once per scene).
+    mutual=True: a and b are neighbours only when BOTH (a, b) and (b, a) are listed (the intersection of out- and
+    in-neighbours of the export step, reference trainer/trainer.py:620-621)."""
     dev = unique_segments.device
     S = unique_segments.numel()
     conn = torch.as_tensor(seg_connectivity).to(device=dev, dtype=torch.int64).reshape(-1, 2)
@@ -319,8 +321,12 @@ def segment_adjacency(seg_connectivity, unique_segments):
     pos = torch.searchsorted(unique_segments, conn.reshape(-1)).clamp_(max=S - 1).reshape(-1, 2)
     known = (unique_segments[pos] == conn).all(1) & (pos[:, 0] != pos[:, 1])
     pos = pos[known]
-    both = torch.cat([pos, pos.flip(1)], 0)
-    key = torch.unique(both[:, 0] * S + both[:, 1])                               # sorted: by source, then neighbour
+    if mutual:
+        listed = torch.unique(pos[:, 0] * S + pos[:, 1])
+        key = listed[torch.isin(listed, pos[:, 1] * S + pos[:, 0])]               # still sorted, and symmetric
+    else:
+        both = torch.cat([pos, pos.flip(1)], 0)
+        key = torch.unique(both[:, 0] * S + both[:, 1])                           # sorted: by source, then neighbour
     src, dst = key // S, key % S
     off[1:] = torch.cumsum(torch.bincount(src, minlength=S), 0)
     return off, dst.to(torch.int32).contiguous()
@@ -348,21 +354,39 @@ def _check_rows(bits, rows, S, name):
     return rows
 
 
-def mask_components(bits, rows, adj_off, adj, n_segments=None):
+def mask_components(bits, rows, adj_off, adj, n_segments=None, kernel="lds"):
     """Connected parts of the masks bits[rows] on the adjacency (adj_off, adj) -> (label i32[n, S]: -1 outside the mask,
     else the smallest segment index of the part; n_comp i32[n]).  The adjacency is checked on the host first: a bad
-    index raises, nothing is launched."""
+    index raises, nothing is launched.
+
+    kernel="lds" (the default, FreeMask segment mode's call): the LDS kernel, S up to usc_mask_bits_max_segments()
+    (8 192), refused above.  "wide": the kernel that keeps a row's labels in global memory (csrc/separate.hip), S up to
+    usc_mask_bits_max_segments_wide() (65 536); same labels.  "auto" (the export step's choice): the LDS kernel up to
+    its cap, the wide one above."""
     require_device()
+    if kernel not in ("lds", "wide", "auto"):
+        raise ValueError(f"mask_components: kernel must be 'lds', 'wide' or 'auto', not {kernel!r}")
     S = adj_off.numel() - 1 if n_segments is None else int(n_segments)
     cap = lib.usc_mask_bits_max_segments()
-    if not 1 <= S <= cap:
+    wide = kernel == "wide" or (kernel == "auto" and S > cap)
+    if wide:
+        cap_wide = lib.usc_mask_bits_max_segments_wide()
+        if not 1 <= S <= cap_wide:
+            raise RuntimeError(f"mask_components: S = {S} segments outside [1, {cap_wide}] (one workgroup walks a row's "
+                               "labels in global memory; above this count one round is too long for one workgroup)")
+    elif not 1 <= S <= cap:
         raise RuntimeError(f"mask_components: S = {S} segments outside [1, {cap}] (a row's labels live in LDS)")
     _check_adjacency(adj_off, adj, S)
     rows = _check_rows(bits, rows, S, "mask_components")
     n = rows.numel()
     label = torch.empty((n, S), dtype=torch.int32, device=bits.device)
     ncomp = torch.empty(n, dtype=torch.int32, device=bits.device)
-    if n:
+    if n and wide:
+        status = torch.empty(1, dtype=torch.int32, device=bits.device)
+        check(lib.usc_mask_bits_components_wide(_ptr(bits), bits.shape[0], S, _ptr(rows), n, _ptr(adj_off), _ptr(adj),
+                                                _ptr(label), _ptr(ncomp), _ptr(status), _stream()),
+              "usc_mask_bits_components_wide")
+    elif n:
         check(lib.usc_mask_bits_components(_ptr(bits), bits.shape[0], S, _ptr(rows), n, _ptr(adj_off), _ptr(adj),
                                            _ptr(label), _ptr(ncomp), _stream()), "usc_mask_bits_components")
     return label, ncomp

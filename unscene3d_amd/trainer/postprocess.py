@@ -7,11 +7,14 @@ tools/export_bench.py, and the route of the CPU stand-ins of the host-logic test
 from __future__ import annotations
 
 import os
+import warnings
 
 import numpy as np
 import torch
 
 from .. import ops
+
+_warned_separate = False
 
 
 def dbscan_split(masks: torch.Tensor, logits: torch.Tensor, coords: torch.Tensor, eps: float = 0.95):
@@ -106,14 +109,28 @@ def filter_instances(sorted_masks, sorted_scores, scores_threshold, iou_threshol
 
 def export_instances(output, target_low_res, target_full_res, inverse_maps, raw_coords, general, num_classes,
                      decoder_id=-1, train_on_segments=True, eval_on_segments=True, label_offset=0,
-                     full_res_coords=None):
+                     full_res_coords=None, segment_connectivity=None):
     """Device version of the prediction half of `eval_instance_step` (trainer.py:479-651, :668-683).
 
     output: model output dict (`pred_logits` [B,Q,C+1], `pred_masks` list of [S_b or N_b, Q], `aux_outputs`);
     target_*[b]['point2segment']; inverse_maps[b] i64[N_full_b]; raw_coords f32[sum N_b, 3] (DBSCAN only);
     general: config node with use_dbscan, dbscan_eps, dbscan_min_points (optional, 1), topk_per_image,
     filter_out_instances, scores_threshold, iou_threshold.  -> list of dicts {pred_masks bool[N_full,K], pred_scores f32[K], pred_classes i64[K]
-    (+ label_offset), pred_boxes f64[K',8] = class, centre, extent, score of the non-empty masks}."""
+    (+ label_offset), pred_boxes f64[K',8] = class, centre, extent, score of the non-empty masks}.
+
+    segment_connectivity: per scene, int[P,2] pairs of full-resolution segment ids, or [] / None.  With
+    `general.separate_instances` (optional, off) and `filter_out_instances`, the kept instances of a scene with a
+    non-empty connectivity are cut into their connected parts (trainer/separate.py, :609-650): one column per part,
+    score and class repeated, boxes from the new columns.  Without `filter_out_instances` the flag does nothing (as in
+    the reference) and says so once."""
+    global _warned_separate
+    separate = bool(getattr(general, "separate_instances", False))
+    if separate and not general.filter_out_instances:
+        if not _warned_separate:
+            warnings.warn("general.separate_instances has no effect without general.filter_out_instances "
+                          "(the split is part of the overlap filter's branch)")
+            _warned_separate = True
+        separate = False
     preds = list(output["aux_outputs"]) + [{"pred_logits": output["pred_logits"], "pred_masks": output["pred_masks"]}]
     pred = preds[decoder_id]
     logits = torch.softmax(pred["pred_logits"], dim=-1)[..., :-1]
@@ -154,7 +171,15 @@ def export_instances(output, target_low_res, target_full_res, inverse_maps, raw_
             keep = filter_instances(sorted_masks, sorted_scores, general.scores_threshold, general.iou_threshold)
             sorted_masks = sorted_masks.index_select(1, torch.as_tensor(keep, dtype=torch.int64, device=dev))
             sorted_scores, sorted_classes = sorted_scores[keep], sorted_classes[keep]
-        res = {"pred_masks": sorted_masks > 0, "pred_scores": sorted_scores, "pred_classes": sorted_classes + label_offset}
+        pred_masks = sorted_masks > 0
+        if separate:
+            conn = segment_connectivity[bid] if segment_connectivity is not None and bid < len(segment_connectivity) else []
+            if conn is not None and len(conn) > 0 and len(keep) > 0:     # :611; no kept instance: the unsplit, empty result
+                from .separate import separate_instances
+                pred_masks, src = separate_instances(pred_masks, seg_full, conn)
+                src = src.cpu()
+                sorted_scores, sorted_classes = sorted_scores[src.numpy()], sorted_classes[src]   # :635-636
+        res = {"pred_masks": pred_masks, "pred_scores": sorted_scores, "pred_classes": sorted_classes + label_offset}
         if full_res_coords is not None:
             res["pred_boxes"] = mask_boxes(res["pred_masks"], torch.as_tensor(full_res_coords[bid], device=dev),
                                            res["pred_classes"], sorted_scores)

@@ -238,7 +238,8 @@ class InstanceSegmentation(nn.Module):
                                      num_classes=self.model.num_classes, decoder_id=g.decoder_id,
                                      train_on_segments=self.model.train_on_segments,
                                      eval_on_segments=g.eval_on_segments, label_offset=label_offset,
-                                     full_res_coords=data.full_res_coords)
+                                     full_res_coords=data.full_res_coords,
+                                     segment_connectivity=getattr(data, "segment_connectivity", None))
         if getattr(g, "save_for_freemask", False):
             for name, coords, inst in zip(file_names, data.full_res_coords, instances):
                 save_for_freemask(g.save_dir, name, coords, inst["pred_masks"], getattr(g, "freemask_format", "npy"))
