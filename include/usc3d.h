@@ -1108,6 +1108,31 @@ int usc_knn1(const float* query, int64_t nq, const float* ref, int64_t nr,
              int64_t* idx, float* dist2, usc_stream_t s);
 
 /* ------------------------------------------------------------------------
+ * N6b the same search through a uniform grid — scipy.spatial.KDTree(ref)
+ * .query(query, k=1) of pseudo_masks/unscene3d_pseudo_main.py:339-343 in O(N)
+ * (csrc/knn.hip).  Returns exactly what usc_knn1 returns: f64 distances on the
+ * f32 inputs, the lowest reference index among equidistant points, dist2 the
+ * same f32 bits.  Inputs are finite.
+ * The grid is the caller's: origin f64[3], cell > 0 and dims i32[3] are HOST
+ * values (cell (i,j,k) covers origin + (i..i+1, j..j+1, k..k+1) * cell; at most
+ * 2^27 cells, 1 <= nr < 2^31).  Any grid gives the right answer — points and
+ * queries outside it are clamped into its boundary cells — a grid that fits
+ * the reference points with a few points per occupied cell gives it fast.
+ * Reference points are binned (histogram, scan, scatter in ascending index per
+ * cell); a query searches cubes of cells of Chebyshev radius 1, 2, .. 4 around
+ * its cell until its best distance is strictly below the distance of the
+ * nearest wall of the cube (less a rounding allowance), else streams all
+ * reference points like usc_knn1.  ws holds usc_knn1_grid_ws_bytes(nr, dims)
+ * bytes (-1 for sizes out of range); nq = 0 bins the points and searches
+ * nothing.  No allocation, no host synchronisation.
+ * ---------------------------------------------------------------------- */
+int64_t usc_knn1_grid_ws_bytes(int64_t nr, const int32_t* dims);
+int usc_knn1_grid(const float* query, int64_t nq, const float* ref, int64_t nr,
+                  const double* origin, double cell, const int32_t* dims,
+                  int64_t* idx, float* dist2, void* ws, int64_t ws_bytes,
+                  usc_stream_t s);
+
+/* ------------------------------------------------------------------------
  * E1  eps-ball connected components — replaces
  * sklearn.cluster.DBSCAN(eps, min_samples=1).fit(xyz).labels_
  * (trainer/trainer.py:521-523): min-label propagation with pointer jumping; the

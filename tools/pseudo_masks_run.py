@@ -11,6 +11,12 @@ Replicas only: rank r of W takes the scenes r, r+W, ... and nev
     python tools/pseudo_masks_run.py --synthetic 6 --out /tmp/pm                   # self-contained demo scenes
     python tools/pseudo_masks_run.py --scenes DIR --out OUT --method freemask      # the FreeMask baseline instead of NCut
     python tools/pseudo_masks_run.py --scenes DIR --out OUT --method freemask --freemask-mode segment   # on segments
+    python tools/pseudo_masks_run.py --scenes DIR --out OUT --modality both         # needs feats_2d and feats_3d
+
+--modality (the reference's config.freemask.modality) names the per-voxel features to use: `color` = feats_2d, `geom` =
+feats_3d, `both` = the pair (NCut averages the two affinities, unscene3d_pseudo_main.py:510-511; FreeMask takes one
+modality); `auto`, the default, is whatever the file holds for NCut and feats_2d for FreeMask.  `2d` and `3d` are the
+older spellings of `color` and `geom`.  A scene file without a named array stops the run with the file and the key.
 
 --method ncut (default) writes `{scene}_masks.npy` as bool[N_full, K] NCut masks; --method freemask (reference
 pseudo_masks/freemask_main.py, voxel mode; unscene3d_amd.pseudo_masks.freemask) writes it as f32[N_full, M] soft masks,
@@ -20,10 +26,9 @@ segment mode instead (keys and queries are the scene file's segments, masks spli
 
 Scene files (`DIR/*.npz`, one per scene; the encoders' per-voxel outputs are an input here.
 tools/scene_files_from_scans.py writes these files from ScanNet-style scan directories — colour frames, poses, the info
-file and the mesh — with `feats_2d` from the DINO ViT-S/8 image encoder (unscene3d_amd.pseudo_masks.scans.build_scene).
-`feats_3d` is the user's to add: the CSC Res16UNet is in the package as models.res16unet, and
-unscene3d_amd.pseudo_masks.pipeline.encode_scene_feats_3d produces the array from a backbone.  The encoders' published
-weights are files the user brings):
+file and the mesh — with `feats_2d` from the DINO ViT-S/8 image encoder and, given `--csc-weights`, `feats_3d` from the CSC
+Res16UNet34C (unscene3d_amd.pseudo_masks.scans.build_scene; `--no-images` writes `feats_3d` alone).  The encoders'
+published weights are files the user brings):
     coords            int[N,3] or [N,4]   voxel coordinates (b,x,y,z or x,y,z)
     feats_2d, feats_3d f32[N,d]            per-voxel features of one or both modalities (all-zero rows = not seen)
     segment_ids       int[N]              over-segmentation id per voxel (felzenszwalb_cpp.segment_mesh + 1-NN)
@@ -89,7 +94,24 @@ def write_scene(out_dir, name, cloud_file, all_masks, full):
     np.save(cloud_file, full.astype(np.single))                     # written last: its presence marks "done"
 
 
-def process_scene(path, out_dir, device, ncut_args):
+MODALITY_KEYS = {"color": ("feats_2d",), "2d": ("feats_2d",), "geom": ("feats_3d",), "3d": ("feats_3d",),
+                 "both": ("feats_2d", "feats_3d")}
+
+
+def modality_keys(path, files, modality):
+    """The feature arrays of scene file `path` (holding `files`) that --modality names; a missing one is an error."""
+    if modality == "auto":
+        keys = tuple(k for k in ("feats_2d", "feats_3d") if k in files)
+        if not keys:
+            raise RuntimeError(f"{path}: needs feats_2d and/or feats_3d")
+        return keys
+    for k in MODALITY_KEYS[modality]:
+        if k not in files:
+            raise RuntimeError(f"{path}: needs {k} for --modality {modality}")
+    return MODALITY_KEYS[modality]
+
+
+def process_scene(path, out_dir, device, ncut_args, modality="auto"):
     """-> (scene name, number of masks, seconds) or None when the scene was already processed."""
     from unscene3d_amd.pseudo_masks import ncut, pipeline
     todo = pending_scene(path, out_dir)
@@ -102,9 +124,7 @@ def process_scene(path, out_dir, device, ncut_args):
     segment_ids = torch.from_numpy(z["segment_ids"].astype(np.int64)).to(device)
     conn = torch.from_numpy(z["seg_connectivity"].astype(np.int64))
     voxel_size = float(z["voxel_size"]) if "voxel_size" in z.files else 0.02
-    mods = [torch.from_numpy(z[k]).to(device) for k in ("feats_2d", "feats_3d") if k in z.files]
-    if not mods:
-        raise RuntimeError(f"{path}: needs feats_2d and/or feats_3d")
+    mods = [torch.from_numpy(z[k]).to(device) for k in modality_keys(path, z.files, modality)]
     agg, unique_segments = [], None
     for f in mods:                                                  # reference :350-402, per modality
         a, unique_segments = ncut.aggregate_features(f, segment_ids, conn, aggregation_mode="mean")
@@ -120,7 +140,7 @@ def process_scene(path, out_dir, device, ncut_args):
     return name, int(all_masks.shape[1]), time.perf_counter() - t0
 
 
-def process_scene_freemask(path, out_dir, device, fm_args, modality="2d", resolution_scale=2, mode="voxel"):
+def process_scene_freemask(path, out_dir, device, fm_args, modality="color", resolution_scale=2, mode="voxel"):
     """FreeMask (voxel or segment mode) on one scene file -> (scene name, number of masks, seconds); None when already
     processed.  A scene without instances writes nothing (the reference prints and skips it)."""
     from unscene3d_amd.pseudo_masks import freemask as fm
@@ -130,9 +150,7 @@ def process_scene_freemask(path, out_dir, device, fm_args, modality="2d", resolu
     name, cloud_file = todo
     t0 = time.perf_counter()
     z = np.load(path)
-    key = f"feats_{modality}"
-    if key not in z.files:
-        raise RuntimeError(f"{path}: needs {key} for --method freemask --modality {modality}")
+    key, = modality_keys(path, z.files, modality)
     coords = torch.from_numpy(z["coords"].astype(np.int32)).to(device)
     feats = torch.from_numpy(z[key].astype(np.float32)).to(device)
     voxel_size = float(z["voxel_size"]) if "voxel_size" in z.files else 0.02
@@ -166,7 +184,9 @@ def main(argv=None):
     ap.add_argument("--max-extent-ratio", type=float, default=0.8)
     ap.add_argument("--method", choices=("ncut", "freemask"), default="ncut")
     fm = ap.add_argument_group("--method freemask (freemask_main.py's config.freemask)")
-    fm.add_argument("--modality", choices=("2d", "3d"), default="2d", help="which per-voxel features of the scene file")
+    ap.add_argument("--modality", choices=("auto", "color", "geom", "both", "2d", "3d"), default="auto",
+                    help="which per-voxel features of the scene file: color = feats_2d, geom = feats_3d, both; auto = "
+                         "what the file holds (--method freemask: feats_2d)")
     fm.add_argument("--freemask-mode", choices=("voxel", "segment"), default="voxel",
                     help="segment: keys and queries are the scene file's segments (segment_ids, seg_connectivity), "
                          "masks split into connected parts (the reference's segments_as_grids default)")
@@ -179,6 +199,11 @@ def main(argv=None):
     fm.add_argument("--nms-maskness-threshold", type=float, default=0.6)
     fm.add_argument("--similarity-metric", default="cos")
     args = ap.parse_args(argv)
+    if args.method == "freemask":
+        if args.modality == "both":
+            ap.error("--method freemask takes one modality: --modality color or geom")
+        if args.modality == "auto":
+            args.modality = "color"
     from unscene3d_amd.pseudo_masks.driver import scene_shard
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -210,7 +235,7 @@ def main(argv=None):
             r = process_scene_freemask(files[i], args.out, device, fm_args, args.modality, args.resolution_scale,
                                        args.freemask_mode)
         else:
-            r = process_scene(files[i], args.out, device, ncut_args)
+            r = process_scene(files[i], args.out, device, ncut_args, args.modality)
         if r is None:
             print(f"[rank {rank}] scene already processed: {os.path.basename(files[i])}", flush=True)
         else:

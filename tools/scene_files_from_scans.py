@@ -10,11 +10,17 @@ Replicas only, like pseudo_masks_run.py: rank r of W takes the scenes r, r+W, ..
     python tools/scene_files_from_scans.py --scans SCANS --out SCENES --dino-weights dino_deitsmall8_pretrain.pth
     python -m torch.distributed.run --nproc-per-node 8 tools/scene_files_from_scans.py --scans SCANS --out SCENES ...
     python tools/pseudo_masks_run.py --scenes SCENES --out MASKS
+    python tools/scene_files_from_scans.py --scans SCANS --out SCENES --dino-weights DINO.pth --csc-weights CSC.pth
+    python tools/scene_files_from_scans.py --scans SCANS --out SCENES --no-images --csc-weights CSC.pth
 
 --dino-weights is the published DINO ViT-S/8 checkpoint (a state_dict; not part of this repository);
 --random-weights SEED initialises the encoder from a seed instead (smoke runs and benchmarks: the features mean nothing).
 --frame-batch K sends K frames per encoder pass and projection launch (pipeline.encode_scene_feats_2d); 0 is the
-per-frame path through the resized feature maps.  The default is what profiles/scene_encode_bench.txt measured fastest."""
+per-frame path through the resized feature maps.  The default is what profiles/scene_encode_bench.txt measured fastest.
+--csc-weights is the published CSC Res16UNet34C checkpoint (`{"state_dict": ...}`; models.weights.load_csc_backbone):
+with it, or with --csc-random-weights SEED, the voxels also go through the 3D backbone and the file gets `feats_3d`, the
+features of level res_{--resolution-scale} (reference unscene3d_pseudo_main.py:332-348; `modality: both`).  --no-images
+reads no frame and writes the geometry modality alone (`modality: geom`); the image encoder's weights are not needed then."""
 import argparse
 import os
 import sys
@@ -47,7 +53,19 @@ def make_encoder(args, device):
     return net.to(device).eval()
 
 
-def process_scan(scan_dir, out_dir, model, args):
+def make_backbone_3d(args, device):
+    """The 3D feature extractor, or None without --csc-weights / --csc-random-weights."""
+    from unscene3d_amd.models.weights import load_csc_backbone
+
+    if args.csc_weights:
+        return load_csc_backbone(args.csc_weights, device=device)
+    if args.csc_random_weights is None:
+        return None
+    torch.manual_seed(args.csc_random_weights)
+    return load_csc_backbone({}, device=device)
+
+
+def process_scan(scan_dir, out_dir, model, args, model_3d=None):
     """-> (scene name, voxels, frames used, frames dropped, seconds) or None when the scene file exists."""
     from unscene3d_amd.pseudo_masks import scans
 
@@ -59,21 +77,31 @@ def process_scan(scan_dir, out_dir, model, args):
     scene = scans.build_scene(scan_dir, model, voxel_size=args.voxel_size, image_hw=(args.height, args.width),
                               segments_min_verts=args.segments_min_verts, frame_batch=args.frame_batch or None,
                               attention=args.attention, every=args.every,
-                              device=next(model.parameters()).device)
+                              device=next((model_3d if model is None else model).parameters()).device, model_3d=model_3d,
+                              resolution_scale=args.resolution_scale, precision_3d=args.precision_3d,
+                              images=not args.no_images)
     os.makedirs(out_dir, exist_ok=True)
     tmp = path + ".tmp.npz"
     np.savez(tmp, **scene)
     os.replace(tmp, path)                                           # a killed run leaves no half-written scene file
-    return name, scene["coords"].shape[0], scene["frames_used"], scene["frames_dropped"], time.perf_counter() - t0
+    return (name, scene["coords"].shape[0], scene.get("frames_used", 0), scene.get("frames_dropped", 0),
+            time.perf_counter() - t0)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scans", required=True, help="directory with one sub-directory per scan")
     ap.add_argument("--out", required=True, help="directory for the .npz scene files")
-    w = ap.add_mutually_exclusive_group(required=True)
+    w = ap.add_mutually_exclusive_group()
     w.add_argument("--dino-weights", help="state_dict file of DINO ViT-S/8")
     w.add_argument("--random-weights", type=int, metavar="SEED")
+    w3 = ap.add_mutually_exclusive_group()
+    w3.add_argument("--csc-weights", metavar="FILE", help="checkpoint of the CSC Res16UNet34C: also write feats_3d")
+    w3.add_argument("--csc-random-weights", type=int, metavar="SEED")
+    ap.add_argument("--resolution-scale", type=int, default=2, choices=(1, 2, 4, 8, 16),
+                    help="level of the 3D backbone whose features become feats_3d")
+    ap.add_argument("--precision-3d", choices=("f32", "bf16"), default="f32")
+    ap.add_argument("--no-images", action="store_true", help="read no frame: a geometry-only scene file")
     ap.add_argument("--frame-batch", type=int, default=DEFAULT_FRAME_BATCH, metavar="K",
                     help="frames per encoder pass and projection launch; 0 = the per-frame map path")
     ap.add_argument("--every", type=int, default=1, metavar="K", help="use every K-th frame")
@@ -86,6 +114,12 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.frame_batch < 0 or args.every < 1:
         ap.error("--frame-batch needs K >= 0 and --every K >= 1")
+    has_2d = args.dino_weights is not None or args.random_weights is not None
+    has_3d = args.csc_weights is not None or args.csc_random_weights is not None
+    if args.no_images and not has_3d:
+        ap.error("--no-images needs --csc-weights or --csc-random-weights")
+    if not args.no_images and not has_2d:
+        ap.error("one of the arguments --dino-weights --random-weights is required (or --no-images)")
     from unscene3d_amd.pseudo_masks.driver import scene_shard
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -94,10 +128,11 @@ def main(argv=None):
     device = torch.device("cuda", local)
     dirs = sorted(d for d in (os.path.join(args.scans, e) for e in os.listdir(args.scans)) if os.path.isdir(d))
     mine = scene_shard(len(dirs), rank, world)
-    model = make_encoder(args, device)
+    model = make_encoder(args, device) if has_2d and not args.no_images else None
+    model_3d = make_backbone_3d(args, device)
     done = 0
     for i in mine:
-        r = process_scan(dirs[i], args.out, model, args)
+        r = process_scan(dirs[i], args.out, model, args, model_3d)
         if r is None:
             print(f"[rank {rank}] scene file exists: {os.path.basename(dirs[i])}", flush=True)
         else:

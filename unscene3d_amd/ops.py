@@ -1114,6 +1114,71 @@ def knn1(query: torch.Tensor, ref: torch.Tensor):
     return d2.sqrt(), idx
 
 
+KNN1_GRID_CELL_BUDGET = 1 << 22          # cells of a knn1_grid grid: 16 MiB of cell offsets at the most
+
+
+def knn1_grid_plan(lo, hi, nr: int, cell=None):
+    """Host arithmetic of `knn1_grid`: the grid over the box lo..hi (3 floats each) for nr reference points.
+    -> (origin f64[3], cell, dims i32[3]).
+
+    cell=None: sqrt(2 * (ex*ey + ey*ez + ez*ex) / nr) for a box of extents ex, ey, ez.  The clouds of this package are
+    surfaces (mesh vertices, surface voxels), and a surface of area A meets about A / cell^2 cells, so nr * cell^2 / A
+    points share an occupied cell; half the box's surface stands in for A, which is not known without a pass over the
+    points, and the 2 asks for two points per occupied cell.  A box with no area (points on a line, one point) takes its
+    longest extent / nr, or 1.  profiles/knn1_grid.txt has the occupancy this gives on the package's own shapes.
+    A cell that would need more than KNN1_GRID_CELL_BUDGET cells is doubled until the grid fits."""
+    import numpy as np
+    lo = np.asarray(lo, np.float64).reshape(3)
+    ext = np.maximum(np.asarray(hi, np.float64).reshape(3) - lo, 0.0)
+    if not (np.isfinite(lo).all() and np.isfinite(ext).all()):
+        raise RuntimeError("knn1_grid: the reference bounds are not finite")
+    if cell is None:
+        area = ext[0] * ext[1] + ext[1] * ext[2] + ext[2] * ext[0]
+        cell = float(np.sqrt(2.0 * area / nr)) if area > 0 else float(ext.max() / nr)
+        if not cell > 0:
+            cell = 1.0
+    cell = float(cell)
+    if not (cell > 0 and np.isfinite(cell)):
+        raise RuntimeError(f"knn1_grid: cell must be a positive finite number, got {cell!r}")
+    while True:
+        dims = np.floor(ext / cell) + 1.0
+        if dims.prod() <= KNN1_GRID_CELL_BUDGET:
+            return lo, cell, dims.astype(np.int32)
+        cell *= 2.0
+
+
+def knn1_grid(query: torch.Tensor, ref: torch.Tensor, cell=None, bounds=None):
+    """`knn1` through a uniform grid (usc_knn1_grid): the same (dist f32[nq], idx i64[nq]), bit for bit, in time
+    proportional to nq + nr instead of nq * nr when the points are spread over many cells.
+
+    cell: side of a grid cell; None picks one from the bounds and nr (`knn1_grid_plan`).  Too small a cell is enlarged
+    until the grid has at most KNN1_GRID_CELL_BUDGET cells; a cell larger than the cloud gives one cell, which works.
+    bounds: (lo, hi) of the reference points, 3 numbers each (anything np.asarray takes).  None reads them back from the
+    device — one `aminmax` and one host synchronisation per call; a caller that knows the box passes it.  Bounds that
+    miss points cost speed, never correctness: points outside are binned into the boundary cells."""
+    require_device()
+    _chk(query, torch.float32, "query")
+    _chk(ref, torch.float32, "ref")
+    nq, nr = query.shape[0], ref.shape[0]
+    if nr < 1:
+        raise RuntimeError("knn1_grid: needs at least one reference point")
+    if bounds is None:
+        lo, hi = torch.aminmax(ref, dim=0)
+        lo, hi = torch.stack([lo, hi]).cpu().numpy()
+    else:
+        lo, hi = bounds
+    origin, cell, dims = knn1_grid_plan(lo, hi, nr, cell)
+    nbytes = lib.usc_knn1_grid_ws_bytes(nr, dims.ctypes.data)
+    if nbytes < 0:
+        check(-1, "usc_knn1_grid_ws_bytes")
+    ws = _ws(nbytes, ref.device)
+    idx = torch.empty(nq, dtype=torch.int64, device=query.device)
+    d2 = torch.empty(nq, dtype=torch.float32, device=query.device)
+    check(lib.usc_knn1_grid(_ptr(query), nq, _ptr(ref), nr, origin.ctypes.data, cell, dims.ctypes.data, _ptr(idx),
+                            _ptr(d2), _ptr(ws), ws.numel(), _stream()), "usc_knn1_grid")
+    return d2.sqrt(), idx
+
+
 def mask_gt_overlap(masks: torch.Tensor, slot: torch.Tensor, nslots: int) -> torch.Tensor:
     """Point overlap of every mask column with every GT slot (the ScanNet instance evaluator's intersections):
     masks bool/u8 [N,K] (rows may be strided: stride(0) >= K, stride(1) == 1), slot i32 [N] in [0, nslots)

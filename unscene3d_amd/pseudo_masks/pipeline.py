@@ -12,15 +12,25 @@ from .. import ops
 from ..precision import inference_precision
 
 
-def encode_scene_feats_3d(model, sinput, resolution_scale=2, precision="f32"):
+def encode_scene_feats_3d(model, sinput, resolution_scale=2, precision="f32", nn="brute"):
     """Res16UNet34CMultiRes features of level `res_{resolution_scale}` for every input voxel.  precision: the trunk's
-    convolutions in "f32" or "bf16" (unscene3d_amd.inference_precision)."""
+    convolutions in "f32" or "bf16" (unscene3d_amd.inference_precision).
+    nn: the 1-NN search that carries the coarse rows to the input voxels — "brute" (ops.knn1, every pair) or "grid"
+    (ops.knn1_grid with cells of the coarse level's tensor stride, one coarse voxel per cell; the box comes from one
+    aminmax of the coarse coordinates).  Both return the same rows."""
+    if nn not in ("brute", "grid"):
+        raise ValueError(f"nn must be 'brute' or 'grid', got {nn!r}")
     with torch.no_grad(), inference_precision(precision):
         _, feature_maps = model(sinput)
         enc = feature_maps[f"res_{resolution_scale}"]
         lr_coords = enc.C[:, 1:].float().contiguous()
         hr_coords = sinput.C[:, 1:].float().contiguous()
-        _, match = ops.knn1(hr_coords, lr_coords)
+        if nn == "grid":
+            lo, hi = torch.aminmax(enc.C[:, 1:], dim=0)
+            lo, hi = torch.stack([lo, hi]).cpu().numpy()
+            _, match = ops.knn1_grid(hr_coords, lr_coords, cell=float(enc.tensor_stride[0]), bounds=(lo, hi))
+        else:
+            _, match = ops.knn1(hr_coords, lr_coords)
         return enc.F[match].detach()
 
 

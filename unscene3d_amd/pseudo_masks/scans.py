@@ -14,7 +14,13 @@ same files through open3d, plyfile and torchvision.  `build_scene` joins the rea
 voxelisation (ME.utils.sparse_quantize), the mesh over-segmentation (felzenszwalb_cpp.segment_mesh), the image encoder
 and the ray-cast projection (pipeline.encode_scene_feats_2d).
 
-Not covered: the 3D modality (`pipeline.encode_scene_feats_3d` exists; add `feats_3d` to the file), depth
+The 3D modality: with `model_3d` (a Res16UNet34CMultiRes, e.g. models.weights.load_csc_backbone on the published CSC
+checkpoint) `build_scene` runs the voxels through the backbone and carries the features of level `res_{resolution_scale}`
+to every voxel (`pipeline.encode_scene_feats_3d`; reference unscene3d_pseudo_main.py:332-348) as `feats_3d`.  With
+`images=False`, or for a scan directory that has neither `color/` nor `pose/`, no frame is read and the file holds the
+geometry modality alone (the reference's `modality: geom`).
+
+Not covered: depth
 images, label / instance columns (the training dataset's builder, datasets/preprocessing.py, reads them through
 `read_ply_vertex_properties`), chunked scenes, the other datasets' layouts."""
 from __future__ import annotations
@@ -28,6 +34,7 @@ PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": 
              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
              "double": "f8", "float64": "f8"}
 FRAME_SUFFIXES = (".jpg", ".png", ".npy")
+SCENE_NN_3D = "grid"     # the 1-NN of build_scene's 3D branch: what profiles/knn1_grid.txt measured faster
 
 
 # ---------------------------------------------------------------------------------------------------- info and poses
@@ -289,7 +296,8 @@ def load_frames(color_dir, pose_dir, shape_hw, every=1, axis_alignment=None):
 
 # ------------------------------------------------------------------------------------------------------------- scene
 def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_min_verts=50, frame_batch=None,
-                attention=False, every=1, align=True, device="cuda"):
+                attention=False, every=1, align=True, device="cuda", model_3d=None, resolution_scale=2,
+                precision_3d="f32", images=True):
     """One scan directory -> the arrays of a scene file (tools/pseudo_masks_run.py), as the reference's dataset and
     `encode_scene_feats` produce them at test time (no augmentation):
 
@@ -297,6 +305,8 @@ def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_
         colors            f32[N,3]   rgb / 255 - 0.5 of the kept vertices (scannet.py:281): the 3D backbone's input
         feats_2d          f32[N,C]   running mean of the image features over the frames; all-zero rows = not seen
         feats_2d_query    f32[N,C]   only with `attention`
+        feats_3d          f32[N,C3]  only with `model_3d`: its `res_{resolution_scale}` features (96 channels at res_2)
+        resolution_scale  int        only with `model_3d`
         segment_ids       i64[N]     felzenszwalb_cpp.segment_mesh(vertices, faces, colors, 0.005, segments_min_verts)
         seg_connectivity  i64[E,2]
         full_res_coords   f32[M,3]   the aligned mesh vertices, metres
@@ -311,13 +321,24 @@ def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_
     segment through a 1-NN search of the points against the mesh vertices (:186-191), which is the identity here since
     the points are those vertices; frames with a non-finite pose are dropped (`load_frames`).
     The camera translations are divided by the voxel size (:255-258; no rotation at test time), the frames run through
-    `pipeline.encode_scene_feats_2d(model, ..., frame_batch=frame_batch)` with `model` a models.encoders_2d.DinoNet."""
+    `pipeline.encode_scene_feats_2d(model, ..., frame_batch=frame_batch)` with `model` a models.encoders_2d.DinoNet.
+
+    model_3d: a Res16UNet34CMultiRes in eval mode.  The voxels go through it as SparseTensor(colors, coords) — the
+    arrays above — with the convolutions in `precision_3d` ("f32" or "bf16"), and `pipeline.encode_scene_feats_3d`
+    carries the level's features to the voxels by exact 1-NN through the grid kernel (ops.knn1_grid).
+    images=False, or a scan directory with neither `color/` nor `pose/`: no frame is read, `model` may be None, and
+    `feats_2d`, `frames_used` and `frames_dropped` are not written — a geometry-only scene file.  That needs `model_3d`;
+    `images=False` without it raises before anything is read.  A directory that has the frame folders but no usable
+    frame still gets `feats_2d` as zeros."""
     import torch
+
+    if not images and model_3d is None:
+        raise ValueError("build_scene(images=False) needs model_3d: the scene file would hold no features")
 
     from .. import MinkowskiEngine as ME
     from .. import felzenszwalb_cpp
     from ..project_features_cuda import Project2DFeaturesCUDA
-    from .pipeline import encode_scene_feats_2d
+    from .pipeline import encode_scene_feats_2d, encode_scene_feats_3d
 
     dev = torch.device(device)
     scene = os.path.basename(os.path.normpath(scan_dir))
@@ -336,27 +357,38 @@ def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_
                                               device=dev)
 
     H, W = image_hw
-    images, poses, dropped = load_frames(os.path.join(scan_dir, "color"), os.path.join(scan_dir, "pose"), image_hw,
-                                         every=every, axis_alignment=axis)
-    poses = poses.copy()
-    poses[:, :3, 3] /= voxel_size
+    color_dir, pose_dir = os.path.join(scan_dir, "color"), os.path.join(scan_dir, "pose")
+    if model_3d is not None and not os.path.isdir(color_dir) and not os.path.isdir(pose_dir):
+        images = False                                              # a scan without frames: geometry only
+    if images and model is None:
+        raise ValueError(f"{scan_dir}: has frames, so build_scene needs the image encoder `model` (or images=False)")
     out = {"coords": coords, "colors": (colors[kept] - np.float32(0.5)).astype(np.float32)}
     coords_d = torch.from_numpy(coords).to(dev)
-    feats = None
-    if images.shape[0]:
-        projecter = Project2DFeaturesCUDA(width=W, height=H, voxel_size=voxel_size)
-        intr = torch.from_numpy(color_intrinsics(info, image_hw).astype(np.float32)).to(dev).view(1, 4)
-        feats = encode_scene_feats_2d(model, torch.from_numpy(images).to(dev).unsqueeze(0),
-                                      torch.from_numpy(poses.astype(np.float32)).to(dev).unsqueeze(0), intr, coords_d,
-                                      projecter, attention=attention, frame_batch=frame_batch)
-    if feats is None:                                               # no usable frame: nothing was seen
-        zeros = torch.zeros((coords.shape[0], int(model.feature_dim)), dtype=torch.float32)
-        feats = (zeros, zeros.clone()) if attention else zeros
-    key, query = feats if attention else (feats, None)
-    out["feats_2d"] = key.cpu().numpy()
-    if attention:
-        out["feats_2d_query"] = query.cpu().numpy()
+    counts = {}
+    if images:
+        frames, poses, dropped = load_frames(color_dir, pose_dir, image_hw, every=every, axis_alignment=axis)
+        poses = poses.copy()
+        poses[:, :3, 3] /= voxel_size
+        feats = None
+        if frames.shape[0]:
+            projecter = Project2DFeaturesCUDA(width=W, height=H, voxel_size=voxel_size)
+            intr = torch.from_numpy(color_intrinsics(info, image_hw).astype(np.float32)).to(dev).view(1, 4)
+            feats = encode_scene_feats_2d(model, torch.from_numpy(frames).to(dev).unsqueeze(0),
+                                          torch.from_numpy(poses.astype(np.float32)).to(dev).unsqueeze(0), intr,
+                                          coords_d, projecter, attention=attention, frame_batch=frame_batch)
+        if feats is None:                                           # no usable frame: nothing was seen
+            zeros = torch.zeros((coords.shape[0], int(model.feature_dim)), dtype=torch.float32)
+            feats = (zeros, zeros.clone()) if attention else zeros
+        key, query = feats if attention else (feats, None)
+        out["feats_2d"] = key.cpu().numpy()
+        if attention:
+            out["feats_2d_query"] = query.cpu().numpy()
+        counts = dict(frames_used=int(frames.shape[0]), frames_dropped=int(dropped))
+    if model_3d is not None:
+        sinput = ME.SparseTensor(features=torch.from_numpy(out["colors"]).to(dev), coordinates=coords_d, device=dev)
+        out["feats_3d"] = encode_scene_feats_3d(model_3d, sinput, resolution_scale=int(resolution_scale),
+                                                precision=precision_3d, nn=SCENE_NN_3D).float().cpu().numpy()
+        out["resolution_scale"] = int(resolution_scale)
     out.update(segment_ids=seg[kept].astype(np.int64), seg_connectivity=np.asarray(conn, np.int64).reshape(-1, 2),
-               full_res_coords=xyz.astype(np.float32), voxel_size=float(voxel_size),
-               frames_used=int(images.shape[0]), frames_dropped=int(dropped))
+               full_res_coords=xyz.astype(np.float32), voxel_size=float(voxel_size), **counts)
     return out
