@@ -1133,6 +1133,47 @@ int usc_knn1_grid(const float* query, int64_t nq, const float* ref, int64_t nr,
                   usc_stream_t s);
 
 /* ------------------------------------------------------------------------
+ * N6c normals estimated from a point cloud — replaces open3d's
+ * pcd.estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))
+ * (datasets/preprocessing/arkit_preprocessing.py:98-101) (csrc/normals.hip).
+ *
+ * usc_knn_hybrid_grid: the k nearest reference points inside a radius.
+ * query f32[nq,3], ref f32[nr,3] -> idx i32[nq,k], count i32[nq].  The
+ * candidates of a query are the reference points with d2 < r2, STRICTLY, where
+ * d2 is usc_knn1's expression (f64 on the f32 inputs, x, y, z in that order)
+ * and r2 = (double)radius * radius.  They are ordered by (d2, index) ascending;
+ * the first count = min(k, candidates) indices are written, the rest of the
+ * row is -1.  1 <= k <= 64; radius is finite and > 0; anything else, or a
+ * workspace shorter than usc_knn_hybrid_grid_ws_bytes(nr, dims), is refused
+ * before any launch with nothing written.  origin, cell, dims: the caller's
+ * grid, with usc_knn1_grid's rules — any grid gives the right answer, points
+ * and queries are clamped into it; cell = radius makes a query read at most
+ * 27 cells; a query whose ball reaches more than 4 cells from its own cell
+ * along an axis reads every reference point.  nq = 0 bins the points only.
+ * UNPINNED: the strict `<` is this library's reading of open3d's SearchHybrid.
+ *
+ * usc_normals_pca: per query, with m = count and x_j = ref[idx_j] - query
+ * (exact in f64): mean and centred second moments of the x_j summed in f64 in
+ * list order and divided by m; normals f32[nq,3] = the unit eigenvector of the
+ * smallest eigenvalue (cyclic Jacobi in f64, fixed sweeps), rounded to f32.
+ * m < 3, a zero or non-finite covariance or vector, or an index outside
+ * [0, nr) gives (0, 0, 1).  Sign: of the stored f32 components the one of
+ * largest magnitude (the lowest axis among equals) is >= 0.  UNPINNED:
+ * open3d's sign is a by-product of its eigen routine.
+ * Both: explicit stream, no allocation, no host synchronisation, no float
+ * atomics; two calls write the same bytes.
+ * ---------------------------------------------------------------------- */
+int64_t usc_knn_hybrid_grid_ws_bytes(int64_t nr, const int32_t* dims);
+int usc_knn_hybrid_grid(const float* query, int64_t nq, const float* ref,
+                        int64_t nr, float radius, int32_t k,
+                        const double* origin, double cell, const int32_t* dims,
+                        int32_t* idx, int32_t* count, void* ws,
+                        int64_t ws_bytes, usc_stream_t s);
+int usc_normals_pca(const float* query, int64_t nq, const float* ref,
+                    int64_t nr, const int32_t* idx, const int32_t* count,
+                    int32_t k, float* normals, usc_stream_t s);
+
+/* ------------------------------------------------------------------------
  * E1  eps-ball connected components — replaces
  * sklearn.cluster.DBSCAN(eps, min_samples=1).fit(xyz).labels_
  * (trainer/trainer.py:521-523): min-label propagation with pointer jumping; the

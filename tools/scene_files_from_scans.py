@@ -12,6 +12,7 @@ Replicas only, like pseudo_masks_run.py: rank r of W takes the scenes r, r+W, ..
     python tools/pseudo_masks_run.py --scenes SCENES --out MASKS
     python tools/scene_files_from_scans.py --scans SCANS --out SCENES --dino-weights DINO.pth --csc-weights CSC.pth
     python tools/scene_files_from_scans.py --scans SCANS --out SCENES --no-images --csc-weights CSC.pth
+    python tools/scene_files_from_scans.py --scans SCANS --out SCENES --layout arkit --csc-weights CSC.pth
 
 --dino-weights is the published DINO ViT-S/8 checkpoint (a state_dict; not part of this repository);
 --random-weights SEED initialises the encoder from a seed instead (smoke runs and benchmarks: the features mean nothing).
@@ -20,7 +21,11 @@ per-frame path through the resized feature maps.  The default is what profiles/s
 --csc-weights is the published CSC Res16UNet34C checkpoint (`{"state_dict": ...}`; models.weights.load_csc_backbone):
 with it, or with --csc-random-weights SEED, the voxels also go through the 3D backbone and the file gets `feats_3d`, the
 features of level res_{--resolution-scale} (reference unscene3d_pseudo_main.py:332-348; `modality: both`).  --no-images
-reads no frame and writes the geometry modality alone (`modality: geom`); the image encoder's weights are not needed then."""
+reads no frame and writes the geometry modality alone (`modality: geom`); the image encoder's weights are not needed then.
+--layout arkit reads mesh-only scans (`SCANS/{scene}/{scene}_3dod_mesh.ply`, ARKitScenes' naming, or a flat
+`SCANS/{scene}.ply`; scans.load_mesh_only_scan, reference pseudo_masks/datasets/arkit.py): the mesh is cleaned,
+over-segmented at every size of --segments-min-verts (default 50 100 150 200), small segments are removed and the rest is
+shifted to the origin; the file is geometry-only and holds the segments of level --segment-dimension-order."""
 import argparse
 import os
 import sys
@@ -69,17 +74,18 @@ def process_scan(scan_dir, out_dir, model, args, model_3d=None):
     """-> (scene name, voxels, frames used, frames dropped, seconds) or None when the scene file exists."""
     from unscene3d_amd.pseudo_masks import scans
 
-    name = os.path.basename(os.path.normpath(scan_dir))
+    name = scans.mesh_only_scan_path(scan_dir)[0] if args.layout == "arkit" else os.path.basename(os.path.normpath(scan_dir))
     path = os.path.join(out_dir, f"{name}.npz")
     if os.path.exists(path):
         return None
     t0 = time.perf_counter()
     scene = scans.build_scene(scan_dir, model, voxel_size=args.voxel_size, image_hw=(args.height, args.width),
                               segments_min_verts=args.segments_min_verts, frame_batch=args.frame_batch or None,
+                              layout=args.layout, segment_dimension_order=args.segment_dimension_order,
                               attention=args.attention, every=args.every,
                               device=next((model_3d if model is None else model).parameters()).device, model_3d=model_3d,
                               resolution_scale=args.resolution_scale, precision_3d=args.precision_3d,
-                              images=not args.no_images)
+                              images=not args.no_images and args.layout != "arkit")
     os.makedirs(out_dir, exist_ok=True)
     tmp = path + ".tmp.npz"
     np.savez(tmp, **scene)
@@ -110,10 +116,22 @@ def main(argv=None):
     ap.add_argument("--voxel-size", type=float, default=0.02)
     ap.add_argument("--height", type=int, default=192)
     ap.add_argument("--width", type=int, default=256)
-    ap.add_argument("--segments-min-verts", type=int, default=50)
+    ap.add_argument("--segments-min-verts", type=int, nargs="+", default=None, metavar="N",
+                    help="smallest segment of the over-segmentation: one number (default 50); --layout arkit: one per "
+                         "level (default 50 100 150 200)")
+    ap.add_argument("--layout", choices=("scannet", "arkit"), default="scannet",
+                    help="arkit: mesh-only scans, geometry-only scene files")
+    ap.add_argument("--segment-dimension-order", type=int, default=0, metavar="L",
+                    help="--layout arkit: the level of --segments-min-verts whose segments are written")
     args = ap.parse_args(argv)
     if args.frame_batch < 0 or args.every < 1:
         ap.error("--frame-batch needs K >= 0 and --every K >= 1")
+    if args.layout == "arkit":
+        args.no_images = True
+    elif args.segments_min_verts is not None:
+        if len(args.segments_min_verts) != 1:
+            ap.error("--segments-min-verts takes one number unless --layout arkit is given")
+        args.segments_min_verts = args.segments_min_verts[0]
     has_2d = args.dino_weights is not None or args.random_weights is not None
     has_3d = args.csc_weights is not None or args.csc_random_weights is not None
     if args.no_images and not has_3d:
@@ -126,7 +144,11 @@ def main(argv=None):
     local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
-    dirs = sorted(d for d in (os.path.join(args.scans, e) for e in os.listdir(args.scans)) if os.path.isdir(d))
+    if args.layout == "arkit":
+        from unscene3d_amd.pseudo_masks.scans import mesh_only_scans
+        dirs = mesh_only_scans(args.scans)
+    else:
+        dirs = sorted(d for d in (os.path.join(args.scans, e) for e in os.listdir(args.scans)) if os.path.isdir(d))
     mine = scene_shard(len(dirs), rank, world)
     model = make_encoder(args, device) if has_2d and not args.no_images else None
     model_3d = make_backbone_3d(args, device)

@@ -169,6 +169,9 @@ SIGNATURES = {
     "usc_knn1": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p]),
     "usc_knn1_grid_ws_bytes": (_i64, [_i64, _p]),
     "usc_knn1_grid": (C.c_int, [_p, _i64, _p, _i64, _p, _f64, _p, _p, _p, _p, _i64, _p]),
+    "usc_knn_hybrid_grid_ws_bytes": (_i64, [_i64, _p]),
+    "usc_knn_hybrid_grid": (C.c_int, [_p, _i64, _p, _i64, _f32, _i32, _p, _f64, _p, _p, _p, _p, _i64, _p]),
+    "usc_normals_pca": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i32, _p, _p]),
     "usc_cc_eps_init": (C.c_int, [_p, _i64, _p]),
     "usc_cc_eps_step": (C.c_int, [_p, _i64, _f32, _p, _p, _p, _p]),
     "usc_cc_eps_finish": (C.c_int, [_p, _i64, _p, _p, _p]),

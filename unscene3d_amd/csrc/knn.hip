@@ -3,79 +3,17 @@
 // without visiting every (query, reference) pair.  Replaces scipy.spatial.KDTree(ref).query(query, k=1)
 // (pseudo_masks/unscene3d_pseudo_main.py:339-343).
 //
-// Build: cell of every reference point -> histogram -> exclusive scan (scan.h) -> scatter -> rank inside the cell, so
+// Build (knn_grid.h): cell of every reference point -> histogram -> exclusive scan -> scatter -> rank inside the cell, so
 // that a cell's points lie in ascending reference index.  Query: one thread per query walks cubes of cells of Chebyshev
 // radius 1, 2, ... around its own cell and stops when its best distance is strictly below what any unsearched point can
 // have; a query that kKnnGridMaxRing rings do not settle is answered by streaming every reference point, block-wide,
 // exactly as knn1_kernel does.
-#include "common.h"
-#include "scan.h"
+#include "knn_grid.h"
 
 namespace usc {
 
 constexpr int kKnnGridMaxRing = 4;          // cubes of up to 9^3 cells; past that a query streams all points
 constexpr int kKnnGridTile = 1024;          // reference points per LDS tile of the streaming pass
-constexpr int64_t kKnnGridMaxCells = (int64_t)1 << 27;
-
-struct KnnGrid {
-  double ox, oy, oz, cell;
-  int nx, ny, nz;
-};
-
-struct __align__(16) KnnPoint {
-  float x, y, z;
-  int32_t i;
-};
-
-// Cell coordinate along one axis, in f64, clamped into [0, n): NaN and anything outside the grid land in a boundary
-// cell, so the result is always a valid address.  Build and query share this function; the stopping rule below allows
-// for its rounding.
-__device__ inline int knn_cell(float v, double o, double cell, int n) {
-  const double t = floor(((double)v - o) / cell);
-  return (int)fmin(fmax(t, 0.0), (double)(n - 1));
-}
-
-__global__ __launch_bounds__(256) void knn_grid_hist_kernel(const float* __restrict__ r, int nr, KnnGrid g,
-                                                           int32_t* __restrict__ count, int32_t* __restrict__ cellid,
-                                                           int32_t* __restrict__ slot) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nr) return;
-  const int cx = knn_cell(r[(int64_t)i * 3 + 0], g.ox, g.cell, g.nx),
-            cy = knn_cell(r[(int64_t)i * 3 + 1], g.oy, g.cell, g.ny),
-            cz = knn_cell(r[(int64_t)i * 3 + 2], g.oz, g.cell, g.nz);
-  const int c = (cx * g.ny + cy) * g.nz + cz;
-  cellid[i] = c;
-  slot[i] = atomicAdd(&count[c], 1);        // arrival order inside the cell; knn_grid_rank_kernel puts it right
-}
-
-__global__ __launch_bounds__(256) void knn_grid_scatter_kernel(int nr, const int32_t* __restrict__ start,
-                                                              const int32_t* __restrict__ cellid,
-                                                              const int32_t* __restrict__ slot,
-                                                              int32_t* __restrict__ arrived) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < nr) arrived[start[cellid[i]] + slot[i]] = i;
-}
-
-// The stable place of a point inside its cell = the number of points of that cell with a lower reference index.
-__global__ __launch_bounds__(256) void knn_grid_rank_kernel(const float* __restrict__ r, int nr,
-                                                           const int32_t* __restrict__ start,
-                                                           const int32_t* __restrict__ cellid,
-                                                           const int32_t* __restrict__ arrived,
-                                                           KnnPoint* __restrict__ pts) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= nr) return;
-  const int i = arrived[j];
-  const int c = cellid[i];
-  const int s = start[c], e = start[c + 1];
-  int rank = 0;
-  for (int k = s; k < e; ++k) rank += arrived[k] < i ? 1 : 0;
-  KnnPoint p;
-  p.x = r[(int64_t)i * 3 + 0];
-  p.y = r[(int64_t)i * 3 + 1];
-  p.z = r[(int64_t)i * 3 + 2];
-  p.i = i;
-  pts[s + rank] = p;
-}
 
 __global__ __launch_bounds__(256) void knn_grid_query_kernel(const float* __restrict__ q, int64_t nq,
                                                             const float* __restrict__ r, int nr, KnnGrid g,
@@ -172,35 +110,6 @@ __global__ __launch_bounds__(256) void knn_grid_query_kernel(const float* __rest
   }
 }
 
-struct KnnCountVal {
-  const int32_t* count;
-  int64_t n;
-  __device__ int operator()(int64_t i) const { return i < n ? count[i] : 0; }
-};
-struct KnnStartEmit {
-  int32_t* start;
-  __device__ void operator()(int64_t i, int64_t prefix, int) const { start[i] = (int32_t)prefix; }
-};
-
-// workspace: start i32[cells + 1] | cellid i32[nr] | slot i32[nr] | arrived i32[nr] | pts KnnPoint[nr] | scan
-struct KnnGridWs {
-  int64_t start, cellid, slot, arrived, pts, scan, total;
-};
-static bool knn_grid_layout(int64_t nr, const int32_t* dims, KnnGridWs* w) {
-  if (!dims || nr < 1 || nr > 0x7fffffff || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return false;
-  const int64_t cells = (int64_t)dims[0] * dims[1] * dims[2];
-  if ((int64_t)dims[0] * dims[1] > kKnnGridMaxCells || cells > kKnnGridMaxCells) return false;
-  int64_t o = 0;
-  w->start = o;   o += align_up((cells + 1) * 4, 256);
-  w->cellid = o;  o += align_up(nr * 4, 256);
-  w->slot = o;    o += align_up(nr * 4, 256);
-  w->arrived = o; o += align_up(nr * 4, 256);
-  w->pts = o;     o += align_up(nr * (int64_t)sizeof(KnnPoint), 256);
-  w->scan = o;    o += align_up(scan_ws_bytes(cells + 1), 256);
-  w->total = o;
-  return true;
-}
-
 }  // namespace usc
 
 using namespace usc;
@@ -227,26 +136,11 @@ int usc_knn1_grid(const float* query, int64_t nq, const float* ref, int64_t nr, 
               (long long)w.total);
   hipStream_t st = as_stream(s);
   const KnnGrid g{origin[0], origin[1], origin[2], cell, dims[0], dims[1], dims[2]};
-  const int64_t cells = (int64_t)dims[0] * dims[1] * dims[2];
   char* b = (char*)ws;
-  int32_t* start = (int32_t*)(b + w.start);
-  int32_t* cellid = (int32_t*)(b + w.cellid);
-  int32_t* slot = (int32_t*)(b + w.slot);
-  int32_t* arrived = (int32_t*)(b + w.arrived);
-  KnnPoint* pts = (KnnPoint*)(b + w.pts);
-  const dim3 gr((unsigned)ceil_div(nr, 256));
-  (void)hipMemsetAsync(start, 0, (size_t)((cells + 1) * 4), st);
-  hipLaunchKernelGGL(knn_grid_hist_kernel, gr, dim3(256), 0, st, ref, (int)nr, g, start, cellid, slot);
-  // counts -> first sorted position of every cell, in place (a thread reads its own items before it writes them);
-  // entry `cells` = nr
-  device_exclusive_scan(KnnCountVal{start, cells}, KnnStartEmit{start}, cells + 1, b + w.scan, st);
-  hipLaunchKernelGGL(knn_grid_scatter_kernel, gr, dim3(256), 0, st, (int)nr, (const int32_t*)start,
-                     (const int32_t*)cellid, (const int32_t*)slot, arrived);
-  hipLaunchKernelGGL(knn_grid_rank_kernel, gr, dim3(256), 0, st, ref, (int)nr, (const int32_t*)start,
-                     (const int32_t*)cellid, (const int32_t*)arrived, pts);
+  knn_grid_build(ref, nr, g, w, ws, st);
   if (nq > 0)
     hipLaunchKernelGGL(knn_grid_query_kernel, dim3((unsigned)ceil_div(nq, 256)), dim3(256), 0, st, query, nq, ref, (int)nr,
-                       g, (const int32_t*)start, (const KnnPoint*)pts, idx, dist2);
+                       g, (const int32_t*)(b + w.start), (const KnnPoint*)(b + w.pts), idx, dist2);
   USC_CHECK_LAUNCH("usc_knn1_grid");
   return USC_OK;
 }

@@ -27,7 +27,21 @@ computes them in that case, as here); the 1-NN search runs on f32 coordinates (t
 without ground-truth files is processed (label 0, instance -1), where the reference fails on the missing files;
 `color_mean_std.yaml` comes from the train database when one is written, else from the validation database (the
 reference's driver always passes the validation database, base_preprocessing.py:55-57).  Not built: the
-ARKit / S3DIS layouts, chunked scenes."""
+S3DIS layout, chunked scenes.
+
+Mesh-only scans (`layout="arkit"`; reference datasets/preprocessing/arkit_preprocessing.py `process_file`): a scan is
+`SCANS/{scene}/{scene}_3dod_mesh.ply` or `SCANS/{scene}.ply`, and `build_dataset` writes `{mode}/{scene}.npy`,
+`{mode}/{scene}_freemasks.npy` and database entries with the reference's placeholders (`scene_type: room`, empty raw
+description / instance / segmentation paths).  The normal columns are ESTIMATED FROM THE POINTS,
+`ops.estimate_normals(xyz, 0.1, 30)` (:98-101: open3d's estimate_normals with KDTreeSearchParamHybrid(0.1, 30)), since
+these meshes carry no usable normals at that stage.
+Deviation: the published reader indexes a 9-column cloud file (`cloud_np[:, 3:6]`, `[:, 7]`, `[:, 8]`, `[:, -1]`,
+:90-95), but its own pseudo-mask writer produces such a file only in a commented-out branch — whose columns disagree
+with those indices by one — and the live writer saves xyz only, as tools/pseudo_masks_run.py does.  So colours and
+segment ids come from the mesh: the builder re-runs the scan builder's deterministic mesh stages
+(`scans.load_mesh_only_scan`) and requires `{scene}_cloud.npy` to equal the kept, shifted vertices row for row, bit for
+bit in f32 (ValueError naming the scene otherwise); the masks are then taken row for row, with no 1-NN.  There is no
+ground truth: label 0, instance -1 and no `instance_gt` file, this builder's convention for scans without ground truth."""
 from __future__ import annotations
 
 import glob
@@ -190,6 +204,45 @@ def build_scene_tables(scan_dir, pseudo_dir, oracle=False, device="cuda", foregr
             "raw_segmentation_filepath": seg_path, "raw_label_filepath": label_path if has_gt else None}
 
 
+def mesh_only_points_table(xyz, rgb, normals, segment_ids):
+    """arkit_preprocessing.py:102-116 -> f32[N,12]: xyz, rgb 0..255, normal, segment id, label 0, instance -1, stacked
+    in f64 and rounded once."""
+    n = np.asarray(xyz).shape[0]
+    labels = np.stack([np.zeros(n, np.int64), np.full(n, -1, np.int64)], 1)
+    return np.hstack([np.asarray(xyz, np.float64), np.asarray(rgb, np.float64), np.asarray(normals, np.float64),
+                      np.asarray(segment_ids, np.int64)[:, None], labels]).astype(np.float32)
+
+
+def build_mesh_only_tables(scan, pseudo_dir, device="cuda", segments_min_verts=scans.ARKIT_SEGMENTS_MIN_VERTS,
+                           segment_dimension_order=0):
+    """One mesh-only scan -> the dict of `build_scene_tables` (gt None, connectivity of the written level), or None
+    (with a message) when its pseudo-mask files are missing — arkit_preprocessing.py `process_file`, with the module
+    docstring's deviation: xyz, colours and segment ids are `scans.load_mesh_only_scan`'s, the cloud file must equal xyz
+    bit for bit, the masks are taken row for row, the normals are `ops.estimate_normals(xyz, 0.1, 30)`."""
+    dev = torch.device(device)
+    scene, mesh_path = scans.mesh_only_scan_path(scan)
+    try:
+        cloud = np.load(os.path.join(pseudo_dir, f"{scene}_cloud.npy"))
+        masks = np.load(os.path.join(pseudo_dir, f"{scene}_masks.npy"))
+    except FileNotFoundError as e:
+        print(f"Could not load pseudo masks for {scene}: {e.filename}")
+        return None
+    m = scans.load_mesh_only_scan(scan, segments_min_verts, segment_dimension_order, device=dev)
+    xyz = m["xyz"].astype(np.float32)
+    if cloud.ndim != 2 or cloud.shape[1] < 3 or cloud.shape[0] != xyz.shape[0] or \
+            not np.array_equal(np.ascontiguousarray(cloud[:, :3], dtype=np.float32).view(np.uint32), xyz.view(np.uint32)):
+        raise ValueError(f"{scene}: {scene}_cloud.npy {list(cloud.shape)} is not the scan's {xyz.shape[0]} kept vertices "
+                         f"row for row (was it written from a scene file of this scan with the same --segments-min-verts?)")
+    if masks.ndim != 2 or masks.shape[0] != xyz.shape[0]:
+        raise ValueError(f"{scene}: pseudo masks {list(masks.shape)} do not match the cloud's {xyz.shape[0]} points")
+    normals = ops.estimate_normals(torch.from_numpy(xyz).to(dev), 0.1, 30).cpu().numpy()
+    mean, second = color_moments(m["rgb"])
+    return {"points": mesh_only_points_table(xyz, m["rgb"], normals, m["segment_ids"]),
+            "freemasks": masks.astype(np.float32), "gt": None, "color_mean": mean, "color_std": second, "connectivity": m["seg_connectivity"], "raw_filepath": mesh_path,
+            "raw_description_filepath": "", "raw_instance_filepath": "", "raw_segmentation_filepath": "",
+            "raw_label_filepath": None, "scene": scene}
+
+
 def color_moments(rgb):
     """A scene's database entries `color_mean` / `color_std` (:162-171) from its colours 0..255 (f64 [N,3]): per channel
     the mean of c / 255 and the mean of (c / 255)^2 — the second moment, under the reference's name."""
@@ -213,7 +266,8 @@ def save_yaml(path, obj):
 
 
 def build_dataset(scans_root, split_files, pseudo_dir, out_dir, oracle=False, device="cuda",
-                  foreground_ids=FOREGROUND_CLASS_IDS, segments_min_verts=20, write_connectivity=False):
+                  foreground_ids=FOREGROUND_CLASS_IDS, segments_min_verts=None, write_connectivity=False,
+                  layout="scannet", segment_dimension_order=0):
     """`split_files`: {mode: text file with one scan name per line} (ScanNet's scannetv2_train.txt / _val.txt), or
     {mode: list of names}.  Every scan `scans_root/<name>` of a mode goes through `build_scene_tables`; scans without
     pseudo-mask files are skipped with a message.  Writes the files the module docstring lists.
@@ -221,7 +275,18 @@ def build_dataset(scans_root, split_files, pseudo_dir, out_dir, oracle=False, de
     `{mode}/0000_00_connectivity.npy` (int32[P,2]) and the entry keys `connectivity_filepath` and
     `segments_min_verts`, which spare `FreeMaskSceneReader(resegment_mesh=True)` its per-item segmentation; a scan
     with a segs.json has no adjacency to store and says so.
+    `segments_min_verts`: None is 20 (layout="scannet") or scans.ARKIT_SEGMENTS_MIN_VERTS (layout="arkit").
+    layout="arkit": mesh-only scans through `build_mesh_only_tables` (module docstring); names are ARKitScenes' scene
+    ids (a sub-directory or a .ply file of `scans_root`), files are `{mode}/{scene}.npy`, entries carry
+    `scene_type: room` and empty raw description / instance / segmentation paths; `oracle` is refused.
     -> {mode: list of database entries}."""
+    if layout not in ("scannet", "arkit"):
+        raise ValueError(f"build_dataset: layout must be 'scannet' or 'arkit', got {layout!r}")
+    arkit = layout == "arkit"
+    if arkit and oracle:
+        raise ValueError("build_dataset(layout='arkit'): mesh-only scans have no ground truth for oracle masks")
+    if segments_min_verts is None:
+        segments_min_verts = scans.ARKIT_SEGMENTS_MIN_VERTS if arkit else 20
     out_dir = os.fspath(out_dir)
     os.makedirs(out_dir, exist_ok=True)
     save_yaml(os.path.join(out_dir, "label_database.yaml"), LABEL_DATABASE)
@@ -232,23 +297,34 @@ def build_dataset(scans_root, split_files, pseudo_dir, out_dir, oracle=False, de
                 split = [line.strip() for line in f if line.strip()]
         names = sorted(split)
         for name in names:
-            parse_scene_dir(name)                     # a bad name fails before anything is written for the mode
+            if not arkit:
+                parse_scene_dir(name)                 # a bad name fails before anything is written for the mode
         os.makedirs(os.path.join(out_dir, mode), exist_ok=True)
         database = []
         for name in names:
             scan_dir = os.path.join(os.fspath(scans_root), name)
-            t = build_scene_tables(scan_dir, pseudo_dir, oracle=oracle, device=device, foreground_ids=foreground_ids,
-                                   segments_min_verts=segments_min_verts)
+            if arkit:
+                t = build_mesh_only_tables(scan_dir, pseudo_dir, device=device, segments_min_verts=segments_min_verts,
+                                           segment_dimension_order=segment_dimension_order)
+            else:
+                t = build_scene_tables(scan_dir, pseudo_dir, oracle=oracle, device=device, foreground_ids=foreground_ids,
+                                       segments_min_verts=segments_min_verts)
             if t is None:
                 continue
-            _, scene, sub = parse_scene_dir(scan_dir)
-            path = os.path.join(out_dir, mode, f"{scene:04}_{sub:02}.npy")
+            if arkit:
+                scene, sub = t["scene"], 0            # arkit_preprocessing.py:168-169
+                path = os.path.join(out_dir, mode, f"{scene}.npy")
+            else:
+                _, scene, sub = parse_scene_dir(scan_dir)
+                path = os.path.join(out_dir, mode, f"{scene:04}_{sub:02}.npy")
             np.save(path, t["points"])
             mask_path = path.replace(".npy", "_freemasks.npy")
             np.save(mask_path, t["freemasks"])
             entry = {"filepath": path, "scene": scene, "sub_scene": sub, "raw_filepath": t["raw_filepath"],
                      "file_len": int(t["points"].shape[0]), "color_mean": t["color_mean"], "color_std": t["color_std"],
                      "freemask_filepath": mask_path}
+            if arkit:
+                entry["scene_type"] = "room"          # the reference's placeholders for what ARKit has not (:107-111)
             for key in ("raw_description_filepath", "raw_instance_filepath", "raw_segmentation_filepath",
                         "raw_label_filepath"):
                 if t[key] is not None:
@@ -257,7 +333,7 @@ def build_dataset(scans_root, split_files, pseudo_dir, out_dir, oracle=False, de
                 conn_path = path.replace(".npy", "_connectivity.npy")
                 np.save(conn_path, np.asarray(t["connectivity"], np.int32).reshape(-1, 2))
                 entry["connectivity_filepath"] = conn_path
-                entry["segments_min_verts"] = int(segments_min_verts)
+                entry["segments_min_verts"] = int(np.atleast_1d(segments_min_verts)[segment_dimension_order if arkit else 0])
             elif write_connectivity:
                 print(f"{name}: segment ids come from {t['raw_segmentation_filepath']}, no connectivity to write")
             if t["gt"] is not None:

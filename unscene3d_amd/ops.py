@@ -1179,6 +1179,65 @@ def knn1_grid(query: torch.Tensor, ref: torch.Tensor, cell=None, bounds=None):
     return d2.sqrt(), idx
 
 
+def knn_hybrid(query: torch.Tensor, ref: torch.Tensor, k: int, radius: float, cell=None, bounds=None):
+    """The k nearest reference points strictly inside `radius` of every query (usc_knn_hybrid_grid; open3d's
+    KDTreeSearchParamHybrid(radius, max_nn=k)) -> (idx i32[nq,k], count i32[nq]).
+
+    Candidates have d2 < r2 with d2 in f64 on the f32 inputs and r2 = float64(float32(radius)) ** 2; they are ordered
+    by (d2, index); row i holds its first count[i] = min(k, candidates) indices, then -1.  1 <= k <= 64.
+    cell: None means the radius (a query then reads at most 27 cells), doubled until the grid has at most
+    KNN1_GRID_CELL_BUDGET cells.  cell and bounds are as in `knn1_grid`: they change the time, never the answer."""
+    require_device()
+    _chk(query, torch.float32, "query")
+    _chk(ref, torch.float32, "ref")
+    nq, nr = query.shape[0], ref.shape[0]
+    if nr < 1:
+        raise RuntimeError("knn_hybrid: needs at least one reference point")
+    k, radius = int(k), float(radius)
+    if not 1 <= k <= 64:                                      # the library refuses it too; idx needs a valid shape
+        raise RuntimeError(f"knn_hybrid: k must be 1 .. 64, got {k}")
+    if bounds is None:
+        lo, hi = torch.aminmax(ref, dim=0)
+        lo, hi = torch.stack([lo, hi]).cpu().numpy()
+    else:
+        lo, hi = bounds
+    origin, cell, dims = knn1_grid_plan(lo, hi, nr, radius if cell is None else cell)
+    nbytes = lib.usc_knn_hybrid_grid_ws_bytes(nr, dims.ctypes.data)
+    if nbytes < 0:
+        check(-1, "usc_knn_hybrid_grid_ws_bytes")
+    ws = _ws(nbytes, ref.device)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=query.device)
+    count = torch.empty(nq, dtype=torch.int32, device=query.device)
+    check(lib.usc_knn_hybrid_grid(_ptr(query), nq, _ptr(ref), nr, radius, k, origin.ctypes.data, cell, dims.ctypes.data,
+                                  _ptr(idx), _ptr(count), _ptr(ws), ws.numel(), _stream()), "usc_knn_hybrid_grid")
+    return idx, count
+
+
+def normals_pca(query: torch.Tensor, ref: torch.Tensor, idx: torch.Tensor, count: torch.Tensor) -> torch.Tensor:
+    """Normal of every query from its neighbour list (usc_normals_pca): the unit eigenvector of the smallest eigenvalue
+    of the neighbours' covariance, f32[nq,3]; (0, 0, 1) with fewer than 3 neighbours or a degenerate covariance; the
+    component of largest magnitude is >= 0."""
+    require_device()
+    _chk(query, torch.float32, "query")
+    _chk(ref, torch.float32, "ref")
+    _chk(idx, torch.int32, "idx")
+    _chk(count, torch.int32, "count")
+    nq = query.shape[0]
+    if idx.dim() != 2 or idx.shape[0] != nq or count.shape != (nq,):
+        raise RuntimeError("normals_pca: idx must be [nq,k] and count [nq]")
+    out = torch.empty((nq, 3), dtype=torch.float32, device=query.device)
+    check(lib.usc_normals_pca(_ptr(query), nq, _ptr(ref), ref.shape[0], _ptr(idx), _ptr(count), idx.shape[1], _ptr(out),
+                              _stream()), "usc_normals_pca")
+    return out
+
+
+def estimate_normals(points: torch.Tensor, radius: float = 0.1, max_nn: int = 30) -> torch.Tensor:
+    """open3d's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) of a cloud f32[N,3] -> f32[N,3]:
+    `knn_hybrid` of the cloud against itself, then `normals_pca`.  The sign is this package's (see `normals_pca`)."""
+    idx, count = knn_hybrid(points, points, max_nn, radius)
+    return normals_pca(points, points, idx, count)
+
+
 def mask_gt_overlap(masks: torch.Tensor, slot: torch.Tensor, nslots: int) -> torch.Tensor:
     """Point overlap of every mask column with every GT slot (the ScanNet instance evaluator's intersections):
     masks bool/u8 [N,K] (rows may be strided: stride(0) >= K, stride(1) == 1), slot i32 [N] in [0, nslots)

@@ -20,9 +20,15 @@ to every voxel (`pipeline.encode_scene_feats_3d`; reference unscene3d_pseudo_mai
 `images=False`, or for a scan directory that has neither `color/` nor `pose/`, no frame is read and the file holds the
 geometry modality alone (the reference's `modality: geom`).
 
+Mesh-only scans (`layout="arkit"`; reference pseudo_masks/datasets/arkit.py:61-144): a scan is
+`DIR/{scene}/{scene}_3dod_mesh.ply` (ARKitScenes' naming) or a flat `DIR/{scene}.ply`, with no info file, no axis
+alignment and no frames.  `load_mesh_only_scan` cleans the mesh, over-segments it at several sizes, drops the vertices
+of too-small segments and shifts the rest to the origin; `build_scene` then runs the same voxelisation and 3D backbone
+and writes a geometry-only scene file.
+
 Not covered: depth
 images, label / instance columns (the training dataset's builder, datasets/preprocessing.py, reads them through
-`read_ply_vertex_properties`), chunked scenes, the other datasets' layouts."""
+`read_ply_vertex_properties`), chunked scenes, the S3DIS layout."""
 from __future__ import annotations
 
 import glob
@@ -34,6 +40,8 @@ PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": 
              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
              "double": "f8", "float64": "f8"}
 FRAME_SUFFIXES = (".jpg", ".png", ".npy")
+ARKIT_SEGMENTS_MIN_VERTS = (50, 100, 150, 200)     # segments_min_vert_nums of the reference's ARKit configuration
+ARKIT_MESH_SUFFIX = "_3dod_mesh.ply"
 SCENE_NN_3D = "grid"     # the 1-NN of build_scene's 3D branch: what profiles/knn1_grid.txt measured faster
 
 
@@ -294,10 +302,108 @@ def load_frames(color_dir, pose_dir, shape_hw, every=1, axis_alignment=None):
     return np.stack(images), np.stack(poses), dropped
 
 
+# ---------------------------------------------------------------------------------------------------- mesh-only scans
+def clean_mesh(vertices, colors, faces):
+    """arkit.py:61-87: drop the vertices no face references and re-index the faces.
+    -> (vertices[kept], colors[kept], faces i32[F,3] into the kept rows, kept i64[V'] ascending)."""
+    vertices, colors, faces = np.asarray(vertices), np.asarray(colors), np.asarray(faces, np.int32).reshape(-1, 3)
+    kept = np.unique(faces)
+    removed = np.ones(vertices.shape[0], np.int64)
+    removed[kept] = 0
+    shift = np.cumsum(removed)                         # unreferenced vertices in front of, or at, each vertex
+    return vertices[kept], colors[kept], (faces - shift[faces]).astype(np.int32), kept.astype(np.int64)
+
+
+def clean_segments(comps, min_vert_num=500):
+    """arkit.py:89-93: -> (comps[valid], valid bool[V]) with valid = the vertex's segment has at least `min_vert_num`
+    vertices."""
+    comps = np.asarray(comps)
+    ids, counts = np.unique(comps, return_counts=True)
+    valid = ~np.isin(comps, ids[counts < min_vert_num])
+    return comps[valid], valid
+
+
+def mesh_only_scan_path(scan):
+    """-> (scene name, mesh file) of a mesh-only scan: the directory `DIR/{scene}` holding `{scene}_3dod_mesh.ply`, or
+    the flat file `DIR/{scene}.ply`."""
+    scan = os.path.normpath(os.fspath(scan))
+    if os.path.isdir(scan):
+        scene = os.path.basename(scan)
+        return scene, os.path.join(scan, scene + ARKIT_MESH_SUFFIX)
+    if scan.endswith(".ply"):
+        return os.path.basename(scan)[:-4], scan
+    return os.path.basename(scan), scan + ".ply"
+
+
+def mesh_only_scans(root):
+    """The scans of a directory in the mesh-only layout, sorted by scene name: sub-directories and *.ply files."""
+    found = {}
+    for e in os.listdir(root):
+        p = os.path.join(root, e)
+        if os.path.isdir(p) or e.endswith(".ply"):
+            found[mesh_only_scan_path(p)[0]] = p
+    return [found[k] for k in sorted(found)]
+
+
+def load_mesh_only_scan(scan, segments_min_verts=ARKIT_SEGMENTS_MIN_VERTS, segment_dimension_order=0, device="cuda"):
+    """`ARKit_Dataset.load_mesh` + `load_scene_data` (arkit.py:95-144), the deterministic mesh stages of a mesh-only
+    scan -> dict:
+
+        scene             str
+        mesh_path         str
+        xyz               f64[N,3]   kept vertices minus their minimum (:142)
+        rgb               f64[N,3]   colours * 255 (:104); integer colours of the file are exact
+        segments          i64[N,L]   the over-segmentation at every level, kept rows
+        segment_ids       i64[N]     column `segment_dimension_order`
+        seg_connectivity  i64[E,2]   that level's directed segment pairs
+        kept              i64[N]     rows of the file's vertex element
+
+    The mesh is cleaned (`clean_mesh`), then `felzenszwalb_cpp.segment_mesh(vertices, faces, colours * 255, 0.005, n)`
+    runs for every n of `segments_min_verts` on the whole cleaned mesh (the edge weights are computed and sorted once;
+    each level is one host merge).  As the reference is written, `clean_segments` runs at every level but only the
+    vertex mask of the LAST level decides which vertices stay: a vertex stays when its segment at the last level has at
+    least segments_min_verts[-1] vertices.  Deviation: connectivity pairs that name a segment left without vertices are
+    dropped (the reference keeps them; nothing refers to such a segment)."""
+    import torch
+
+    from .. import felzenszwalb_cpp as felz
+
+    levels = tuple(int(n) for n in np.atleast_1d(segments_min_verts))
+    if not levels or not 0 <= int(segment_dimension_order) < len(levels):
+        raise ValueError(f"segment_dimension_order {segment_dimension_order} is no level of segments_min_verts {levels}")
+    scene, mesh_path = mesh_only_scan_path(scan)
+    vertices, colors, faces = read_ply_mesh(mesh_path)
+    vertices, colors, faces, kept = clean_mesh(vertices, colors, faces)
+    if vertices.shape[0] == 0:
+        raise ValueError(f"{mesh_path}: no vertex is referenced by a face")
+    rgb = colors.astype(np.float64) * 255.0
+    whole = np.rint(rgb)                               # integer colours come back as 199.99999: undo the trip through
+    rgb = np.where(np.abs(rgb - whole) < 1e-3, whole, rgb)          # f32 [0, 1], which the dataset's uint8 cast would cut
+    dev = torch.device(device)
+    to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dev, dt).contiguous()
+    ea, eb, w, _ = felz.edge_weights(to(vertices, torch.float32), to(faces, torch.int32), to(rgb, torch.float32))
+    order = torch.sort(w, stable=True).indices                      # as felzenszwalb_cpp.segment_mesh orders them
+    sa, sb, sw = ea[order].cpu().numpy(), eb[order].cpu().numpy(), w[order].cpu().numpy()
+    segments, connectivity, valid = [], [], None
+    for n in levels:
+        seg, conn = felz.relabel(felz.merge_host(sa, sb, sw, vertices.shape[0], 0.005, n), sa, sb)
+        segments.append(seg)
+        connectivity.append(conn)
+        _, valid = clean_segments(seg, min_vert_num=n)              # the last level's mask is the one that is used
+    segments = np.stack(segments, -1).astype(np.int64)[valid]
+    xyz = vertices[valid].astype(np.float64)
+    xyz -= xyz.min(0)
+    level = int(segment_dimension_order)
+    conn = np.asarray(connectivity[level], np.int64).reshape(-1, 2)
+    conn = conn[np.isin(conn, np.unique(segments[:, level])).all(1)]
+    return {"scene": scene, "mesh_path": mesh_path, "xyz": xyz, "rgb": rgb[valid], "segments": segments,
+            "segment_ids": np.ascontiguousarray(segments[:, level]), "seg_connectivity": conn, "kept": kept[valid]}
+
+
 # ------------------------------------------------------------------------------------------------------------- scene
-def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_min_verts=50, frame_batch=None,
+def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_min_verts=None, frame_batch=None,
                 attention=False, every=1, align=True, device="cuda", model_3d=None, resolution_scale=2,
-                precision_3d="f32", images=True):
+                precision_3d="f32", images=True, layout="scannet", segment_dimension_order=0):
     """One scan directory -> the arrays of a scene file (tools/pseudo_masks_run.py), as the reference's dataset and
     `encode_scene_feats` produce them at test time (no augmentation):
 
@@ -307,7 +413,7 @@ def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_
         feats_2d_query    f32[N,C]   only with `attention`
         feats_3d          f32[N,C3]  only with `model_3d`: its `res_{resolution_scale}` features (96 channels at res_2)
         resolution_scale  int        only with `model_3d`
-        segment_ids       i64[N]     felzenszwalb_cpp.segment_mesh(vertices, faces, colors, 0.005, segments_min_verts)
+        segment_ids       i64[N]     felzenszwalb_cpp.segment_mesh(vertices, faces, colors, 0.005, segments_min_verts or 50)
         seg_connectivity  i64[E,2]
         full_res_coords   f32[M,3]   the aligned mesh vertices, metres
         voxel_size        float
@@ -329,9 +435,19 @@ def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_
     images=False, or a scan directory with neither `color/` nor `pose/`: no frame is read, `model` may be None, and
     `feats_2d`, `frames_used` and `frames_dropped` are not written — a geometry-only scene file.  That needs `model_3d`;
     `images=False` without it raises before anything is read.  A directory that has the frame folders but no usable
-    frame still gets `feats_2d` as zeros."""
+    frame still gets `feats_2d` as zeros.
+
+    layout="arkit": `scan_dir` is a mesh-only scan (`load_mesh_only_scan`; `segments_min_verts` is then the tuple of
+    levels, None meaning ARKIT_SEGMENTS_MIN_VERTS, and `segment_dimension_order` picks the level that is written).  There is no
+    info file, no alignment and no frame: it needs `model_3d`, the file is geometry-only (no `feats_2d`), the points
+    are the kept vertices shifted to the origin, `colors` is rgb / 255 - 0.5 of the kept voxels as above and
+    `full_res_coords` is the kept, shifted vertices in f32.  layout="scannet", the default, is everything above."""
     import torch
 
+    if layout not in ("scannet", "arkit"):
+        raise ValueError(f"build_scene: layout must be 'scannet' or 'arkit', got {layout!r}")
+    if layout == "arkit":
+        images = False
     if not images and model_3d is None:
         raise ValueError("build_scene(images=False) needs model_3d: the scene file would hold no features")
 
@@ -341,20 +457,27 @@ def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_
     from .pipeline import encode_scene_feats_2d, encode_scene_feats_3d
 
     dev = torch.device(device)
-    scene = os.path.basename(os.path.normpath(scan_dir))
-    info = read_scan_info(os.path.join(scan_dir, f"{scene}.txt"), align=align)
-    axis = info["axisAlignment"]
-    vertices, colors, faces = read_ply_mesh(os.path.join(scan_dir, f"{scene}_vh_clean_2.ply"))       # scannet.py:163
-    homo = np.hstack([vertices.astype(np.float64), np.ones((vertices.shape[0], 1))])
-    xyz = homo @ axis.T[:, :3]
+    if layout == "arkit":
+        levels = ARKIT_SEGMENTS_MIN_VERTS if segments_min_verts is None else segments_min_verts
+        m = load_mesh_only_scan(scan_dir, levels, segment_dimension_order, device=dev)
+        xyz, colors = m["xyz"], (m["rgb"] / 255.0).astype(np.float32)
+        seg, conn, info, axis = m["segment_ids"], m["seg_connectivity"], None, None
+    else:
+        scene = os.path.basename(os.path.normpath(scan_dir))
+        info = read_scan_info(os.path.join(scan_dir, f"{scene}.txt"), align=align)
+        axis = info["axisAlignment"]
+        vertices, colors, faces = read_ply_mesh(os.path.join(scan_dir, f"{scene}_vh_clean_2.ply"))   # scannet.py:163
+        homo = np.hstack([vertices.astype(np.float64), np.ones((vertices.shape[0], 1))])
+        xyz = homo @ axis.T[:, :3]
 
     grid = np.floor(xyz * (1.0 / voxel_size)).astype(np.int32)
     _, kept = ME.utils.sparse_quantize(grid, return_index=True, device=dev)
     kept = kept.cpu().numpy()
     coords = np.concatenate([np.zeros((kept.shape[0], 1), np.int32), grid[kept]], 1)
 
-    seg, conn = felzenszwalb_cpp.segment_mesh(xyz.astype(np.float32), faces, colors, 0.005, int(segments_min_verts),
-                                              device=dev)
+    if layout == "scannet":
+        seg, conn = felzenszwalb_cpp.segment_mesh(xyz.astype(np.float32), faces, colors, 0.005,
+                                                  50 if segments_min_verts is None else int(segments_min_verts), device=dev)
 
     H, W = image_hw
     color_dir, pose_dir = os.path.join(scan_dir, "color"), os.path.join(scan_dir, "pose")
