@@ -764,6 +764,22 @@ int usc_sample_keys(const float* feats, int32_t c, const uint8_t* mask, int32_t 
                     const int64_t* idx, int32_t n_scenes, int32_t K, const int32_t* n_valid, float* out_feats,
                     uint8_t* out_mask, float* out_pos, void* ws, int64_t ws_bytes, usc_stream_t s);
 
+/* The attention-mask rows of one decoder pass for the SAMPLED keys only, straight from the [segments, q] logits: the
+ * bytes that d calls of usc_avgpool_down2_ex (the last one with mask_out) followed by the mask-only usc_sample_keys
+ * give, in one launch plus the all-masked-column launch of usc_sample_keys (skip_fix != 0: left out; the rows are
+ * then the gathered bits with the padding rows masked).
+ *   in      f32 logits, leading dimension ld (a multiple of 4, >= q; `in` 16-byte aligned); q % 4 == 0, q <= 128
+ *   tabs    HOST array of d (1..4) device child tables i32[8, n_rows[j]], -1 where a child is absent: tabs[0] holds
+ *           rows of `in` (point2segment folded into the finest map's k2/s2 child table), tabs[j] rows of table j-1
+ *   idx     i64[n_scenes*K], batch-wide rows of table d-1; n_valid: HOST i32[n_scenes] (n_scenes <= 16), as for
+ *           usc_sample_keys; ws: usc_attn_mask_rows_ws_bytes() (-1: sizes out of range), 4-byte aligned
+ * Every mean is summed in child-slot order and rounded to f32 before its parent adds it, like the separate launches. */
+int64_t usc_attn_mask_rows_ws_bytes(int32_t n_scenes, int32_t K, int32_t q, int32_t d);
+int usc_attn_mask_rows(const float* in, int32_t ld, int32_t q, int32_t d, const int32_t* const* tabs,
+                       const int64_t* n_rows, const int64_t* idx, int32_t n_scenes, int32_t K,
+                       const int32_t* n_valid, uint8_t* out_mask, void* ws, int64_t ws_bytes, int32_t skip_fix,
+                       usc_stream_t s);
+
 /* ------------------------------------------------------------------------
  * Q3  segment mean — replaces torch_scatter.scatter_mean(src, index, dim=0)
  * (models/mask3d.py:12,223; trainer/trainer.py:449) forward + backward.

@@ -152,6 +152,8 @@ SIGNATURES = {
     "usc_scatter_rows_unique_add": (C.c_int, [_p, _i32, _p, _i64, _p, _p]),
     "usc_sample_keys_ws_bytes": (_i64, [_i32, _i32, _i32]),
     "usc_sample_keys": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _i64, _p]),
+    "usc_attn_mask_rows_ws_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "usc_attn_mask_rows": (C.c_int, [_p, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p, _p, _p, _i64, _i32, _p]),
     "usc_segment_csr_ws_bytes": (_i64, [_i64, _i64]),
     "usc_segment_csr": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _i64, _p]),
     "usc_segment_mean_fwd": (C.c_int, [_p, _i32, _p, _p, _i64, _p, _p]),

@@ -628,6 +628,207 @@ __global__ __launch_bounds__(256) void avgpool_down2_kernel(const float* __restr
   }
 }
 
+// ---------------------------------------------------------------------------
+// The thresholded attention-mask rows of ONE decoder pass for the sampled keys only: what D avgpool_down2 launches (the
+// last one with mask_out) followed by the mask part of sample_keys_kernel give, without the pooled [n_level, q] tables
+// in between and without the rows nobody samples.  A key is the root of a tree of depth D: level j's node p has the
+// children tab[j-1][k * n[j-1] + p], k = 0..7 (-1: absent); the children of a level-1 node are rows of `in`.
+// Bits: every node is acc = 0; acc += child for the present slots in ascending k; mean = acc * (1.f / (float)cnt),
+// ROUNDED to f32 before the parent adds it (the chain rounds it by storing it) — contraction is off in this code, a
+// mean never meets its parent's add in one expression, and the sum of a node is never split among lanes.
+// Work split: groups of 32 lanes (a lane owns 4 query columns).  The lowest L <= 2 levels below an "item" node are
+// summed by one group; the S = D - L levels above go through LDS, where one group adds the <= 8 child means of a node
+// in slot order.  D = 1, 2: a group per key.  D = 3: items = the keys' children.  D = 4: items = grandchildren.
+// Output as sample_keys_kernel's: mask bytes [B, K, q] (padding rows stored all-masked) and the per-workgroup AND of
+// the rows' real bits in part[b][blk][q], which sample_fix_kernel reads.
+constexpr int kMaskRowsMaxDepth = 4;
+struct MaskRowsArgs {
+  const float* in; const int64_t* idx; unsigned char* out_mask; unsigned char* part;
+  const int32_t* tab[kMaskRowsMaxDepth];
+  int64_t n[kMaskRowsMaxDepth];
+  int ld, q4, K, nblk;                 // q4: float4 columns of a row (q / 4)
+  int n_valid[kSampleMaxScenes];
+};
+// keys per workgroup at depth d: 200 partials at the decoder's 12 800 / 3 200 / 800 / 200 keys (sample_fix_kernel's
+// time grows with their number)
+static constexpr int mask_rows_keys(int d) { return d == 1 ? 64 : d == 2 ? 16 : d == 3 ? 4 : 1; }
+// threads per workgroup at depth d: a group of 32 lanes has 4 keys (d = 1), 1 key (d = 2), 1 item (d = 3) or 2 items
+// (d = 4) — the kernel's time is the number of dependent loads one group waits for, ~2 us each on cold tables
+static constexpr int mask_rows_threads(int d) { return d <= 2 ? 512 : 1024; }
+
+// mean of the rows ids[0..7] of `in` (-1: absent).  All eight rows are loaded (an absent one reads row 0 and is not
+// added): no load waits for a branch.
+__device__ __forceinline__ float4 mask_leaf_mean(const MaskRowsArgs& a, const int (&ids)[8], int c4) {
+#pragma clang fp contract(off)
+  float4 t[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    t[k] = *reinterpret_cast<const float4*>(a.in + (int64_t)(ids[k] >= 0 ? ids[k] : 0) * a.ld + c4 * 4);
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  int cnt = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (ids[k] >= 0) {
+      ++cnt;
+      acc.x += t[k].x; acc.y += t[k].y; acc.z += t[k].z; acc.w += t[k].w;
+    }
+  const float inv = 1.f / (float)(cnt > 0 ? cnt : 1);
+  float4 m;
+  m.x = acc.x * inv; m.y = acc.y * inv; m.z = acc.z * inv; m.w = acc.w * inv;
+  return m;
+}
+
+// mean of node p of level L (1 or 2).  Level 2: the 8 + 64 table entries are read before any row (an absent child
+// reads the entries of node 0 and is not added), so a node costs three dependent loads, not two per present child.
+template <int L>
+__device__ __forceinline__ float4 mask_node_mean(const MaskRowsArgs& a, int64_t p, int c4) {
+#pragma clang fp contract(off)
+  static_assert(L == 1 || L == 2, "one group walks at most two levels");
+  int ch[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) ch[k] = a.tab[L - 1][k * a.n[L - 1] + p];
+  if constexpr (L == 1) {
+    return mask_leaf_mean(a, ch, c4);
+  } else {
+    int leaf[8][8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) leaf[k][j] = a.tab[0][j * a.n[0] + (ch[k] >= 0 ? ch[k] : 0)];
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float4 m = mask_leaf_mean(a, leaf[k], c4);
+      if (ch[k] >= 0) {
+        ++cnt;
+        acc.x += m.x; acc.y += m.y; acc.z += m.z; acc.w += m.w;
+      }
+    }
+    const float inv = 1.f / (float)(cnt > 0 ? cnt : 1);
+    float4 m;
+    m.x = acc.x * inv; m.y = acc.y * inv; m.z = acc.z * inv; m.w = acc.w * inv;
+    return m;
+  }
+}
+
+__device__ __forceinline__ unsigned int mask_rows_bit(float mean) {
+  return (1.f / (1.f + expf(-mean))) < 0.5f ? 1u : 0u;       // avgpool_down2_kernel's expression
+}
+
+template <int D>
+__global__ __launch_bounds__(mask_rows_threads(D)) void attn_mask_rows_kernel(MaskRowsArgs a) {
+#pragma clang fp contract(off)
+  constexpr int NT = mask_rows_threads(D), NG = NT / 32;
+  constexpr int S = D <= 2 ? 0 : D - 2, L = D - S, R = mask_rows_keys(D);
+  constexpr int NI = S == 0 ? 1 : (S == 1 ? R * 8 : 64);
+  static_assert(S < 2 || R == 1, "two LDS levels: one key per workgroup");
+  static_assert(NI <= NT && NG >= 8, "one thread per item; one group per child of the key");
+  __shared__ int leaf[D == 1 ? R : 1][8];   // (D == 1) the keys' rows of `in`
+  __shared__ float4 val[NI][32];
+  __shared__ float4 val2[S == 2 ? 8 : 1][32];
+  __shared__ int node[NI];             // the item's level-L node, -1: absent
+  __shared__ int node2[8];             // (S == 2) the key's children
+  __shared__ unsigned int band[R][32];
+  const int t = threadIdx.x, c4 = t & 31, g = t >> 5;
+  const int b = blockIdx.y, k0 = blockIdx.x * R;
+  const bool col = c4 < a.q4;
+  const int64_t* __restrict__ idx = a.idx + (int64_t)b * a.K;
+
+  if constexpr (D == 1) {
+    for (int e = t; e < R * 8; e += NT) {
+      const int r = e >> 3, k = e & 7;
+      leaf[r][k] = k0 + r < a.K ? a.tab[0][k * a.n[0] + idx[k0 + r]] : -1;
+    }
+    __syncthreads();
+  }
+  if constexpr (S >= 1) {
+    if (t < NI) {
+      const int r = S == 1 ? t >> 3 : 0, k = S == 1 ? t & 7 : t >> 3;
+      int nd = -1;
+      if (k0 + r < a.K) {
+        nd = a.tab[D - 1][k * a.n[D - 1] + idx[k0 + r]];
+        if constexpr (S == 2) {
+          if ((t & 7) == 0) node2[k] = nd;
+          if (nd >= 0) nd = a.tab[D - 2][(t & 7) * a.n[D - 2] + nd];
+        }
+      }
+      node[t] = nd;
+    }
+    __syncthreads();
+    for (int it = g; it < NI; it += NG) {
+      const int nd = node[it];
+      if (nd >= 0 && col) val[it][c4] = mask_node_mean<L>(a, nd, c4);
+    }
+    __syncthreads();
+    if constexpr (S == 2) {
+      if (g < 8 && node2[g] >= 0 && col) {      // group g: the mean of the key's child g
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        int cnt = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+          if (node[g * 8 + k] >= 0) {
+            ++cnt;
+            const float4 v = val[g * 8 + k][c4];
+            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+          }
+        const float inv = 1.f / (float)(cnt > 0 ? cnt : 1);
+        float4 m;
+        m.x = acc.x * inv; m.y = acc.y * inv; m.z = acc.z * inv; m.w = acc.w * inv;
+        val2[g][c4] = m;
+      }
+      __syncthreads();
+    }
+  }
+
+#pragma unroll 4
+  for (int r = g; r < R; r += NG) {
+    const int kk = k0 + r;
+    unsigned int word = 0x01010101u;   // rows past K and columns past q leave the AND alone
+    if (kk < a.K && col) {
+      float4 m;
+      if constexpr (D == 1) {
+        m = mask_leaf_mean(a, leaf[r], c4);
+      } else if constexpr (S == 0) {
+        m = mask_node_mean<L>(a, idx[kk], c4);
+      } else {
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        int cnt = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          bool present;
+          float4 v;
+          if constexpr (S == 1) {
+            present = node[r * 8 + k] >= 0;
+            v = val[r * 8 + k][c4];
+          } else {
+            present = node2[k] >= 0;
+            v = val2[k][c4];
+          }
+          if (present) {
+            ++cnt;
+            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+          }
+        }
+        const float inv = 1.f / (float)(cnt > 0 ? cnt : 1);
+        m.x = acc.x * inv; m.y = acc.y * inv; m.z = acc.z * inv; m.w = acc.w * inv;
+      }
+      word = mask_rows_bit(m.x) | (mask_rows_bit(m.y) << 8) | (mask_rows_bit(m.z) << 16) | (mask_rows_bit(m.w) << 24);
+      // a padding row (it repeats a real row) enters the AND with its real bits and is stored all-masked
+      reinterpret_cast<unsigned int*>(a.out_mask + ((int64_t)b * a.K + kk) * (a.q4 * 4))[c4] =
+          kk >= a.n_valid[b] ? 0x01010101u : word;
+    }
+    band[r][c4] = word;
+  }
+  __syncthreads();
+  if (t < a.q4) {
+    unsigned int w = band[0][t];
+#pragma unroll
+    for (int r = 1; r < R; ++r) w &= band[r][t];
+    reinterpret_cast<unsigned int*>(a.part + ((int64_t)b * a.nblk + blockIdx.x) * (a.q4 * 4))[t] = w;
+  }
+}
+
 template <int VEC>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ src, int c,
                                                          const int64_t* __restrict__ idx, int64_t n,
@@ -1480,6 +1681,61 @@ int usc_sample_keys(const float* feats, int32_t c, const uint8_t* mask, int32_t 
     hipLaunchKernelGGL(usc::sample_fix_kernel<2>, grid, dim3(256), 0, as_stream(s), a);
   }
   USC_CHECK_LAUNCH("usc_sample_keys");
+  return USC_OK;
+}
+
+int64_t usc_attn_mask_rows_ws_bytes(int32_t n_scenes, int32_t K, int32_t q, int32_t d) {
+  if (d < 1 || d > usc::kMaskRowsMaxDepth || n_scenes < 1 || K < 1 || q < 0) return -1;
+  return (int64_t)n_scenes * ceil_div((int64_t)K, (int64_t)usc::mask_rows_keys(d)) * ((q + 3) / 4 * 4);
+}
+
+int usc_attn_mask_rows(const float* in, int32_t ld, int32_t q, int32_t d, const int32_t* const* tabs,
+                       const int64_t* n_rows, const int64_t* idx, int32_t n_scenes, int32_t K,
+                       const int32_t* n_valid, uint8_t* out_mask, void* ws, int64_t ws_bytes, int32_t skip_fix,
+                       usc_stream_t s) {
+  USC_REQUIRE(d >= 1 && d <= usc::kMaskRowsMaxDepth, "usc_attn_mask_rows: %d pooling steps (1..%d)", d,
+              usc::kMaskRowsMaxDepth);
+  USC_REQUIRE(q >= 4 && q % 4 == 0 && q <= 128, "usc_attn_mask_rows: %d queries (a multiple of 4, <= 128)", q);
+  USC_REQUIRE(n_scenes >= 1 && n_scenes <= usc::kSampleMaxScenes && K >= 1,
+              "usc_attn_mask_rows: unsupported sizes (1..16 scenes, K >= 1)");
+  USC_REQUIRE(ld >= q && ld % 4 == 0, "usc_attn_mask_rows: leading dimension %d (a multiple of 4, >= q)", ld);
+  USC_REQUIRE(in && tabs && n_rows && idx && n_valid && out_mask && ws, "usc_attn_mask_rows: null pointer");
+  USC_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)out_mask & 3) == 0 && ((uintptr_t)ws & 3) == 0,
+              "usc_attn_mask_rows: logits must be 16-byte aligned, mask rows and workspace 4-byte aligned");
+  usc::MaskRowsArgs a{};
+  for (int j = 0; j < d; ++j) {
+    USC_REQUIRE(tabs[j] != nullptr, "usc_attn_mask_rows: child table %d is null", j);
+    USC_REQUIRE(n_rows[j] >= 1 && n_rows[j] <= INT32_MAX, "usc_attn_mask_rows: child table %d has %lld rows", j,
+                (long long)n_rows[j]);
+    a.tab[j] = tabs[j];
+    a.n[j] = n_rows[j];
+  }
+  USC_REQUIRE(ws_bytes >= usc_attn_mask_rows_ws_bytes(n_scenes, K, q, d), "usc_attn_mask_rows: workspace too small");
+  for (int b = 0; b < n_scenes; ++b) {
+    USC_REQUIRE(n_valid[b] >= 1, "usc_attn_mask_rows: a scene without rows");
+    a.n_valid[b] = n_valid[b];
+  }
+  a.in = in; a.idx = idx; a.out_mask = out_mask; a.part = (unsigned char*)ws;
+  a.ld = ld; a.q4 = q / 4; a.K = K;
+  a.nblk = (int)ceil_div((int64_t)K, (int64_t)usc::mask_rows_keys(d));
+  const dim3 grid((unsigned)a.nblk, (unsigned)n_scenes);
+  switch (d) {
+    case 1: hipLaunchKernelGGL(usc::attn_mask_rows_kernel<1>, grid, dim3(usc::mask_rows_threads(1)), 0, as_stream(s), a); break;
+    case 2: hipLaunchKernelGGL(usc::attn_mask_rows_kernel<2>, grid, dim3(usc::mask_rows_threads(2)), 0, as_stream(s), a); break;
+    case 3: hipLaunchKernelGGL(usc::attn_mask_rows_kernel<3>, grid, dim3(usc::mask_rows_threads(3)), 0, as_stream(s), a); break;
+    default: hipLaunchKernelGGL(usc::attn_mask_rows_kernel<4>, grid, dim3(usc::mask_rows_threads(4)), 0, as_stream(s), a); break;
+  }
+  if (!skip_fix) {
+    // the all-masked-column rule over this launch's partials: sample_fix_kernel as usc_sample_keys launches it, its
+    // own 16 rows per workgroup, any number of partials per scene
+    usc::SampleArgs f{};
+    f.out_mask = out_mask; f.part = (unsigned char*)ws;
+    f.q = q; f.qs = q; f.K = K; f.nblk = a.nblk;
+    for (int b = 0; b < n_scenes; ++b) f.n_valid[b] = n_valid[b];
+    const dim3 fgrid((unsigned)ceil_div((int64_t)K, (int64_t)usc::kSampleRows), (unsigned)n_scenes);
+    hipLaunchKernelGGL(usc::sample_fix_kernel<1>, fgrid, dim3(256), 0, as_stream(s), f);
+  }
+  USC_CHECK_LAUNCH("usc_attn_mask_rows");
   return USC_OK;
 }
 

@@ -449,14 +449,18 @@ class Mask3D(nn.Module):
                 normed, queries = self._norm_queries(queries)
                 output_class, outputs_mask, attn_mask = self.mask_module(
                     queries, mask_features, mask_segments, len(aux) - hlevel - 1, ret_attn_mask=True,
-                    point2segment=p2s_arg, coords=coords, defer_class=True, normed=normed)
-                decomposed_attn = attn_mask.decomposed_features
-                if fused and attn_mask.F.dtype == torch.bool and attn_mask.F.shape[1] <= fused_attn_max_queries():
+                    point2segment=p2s_arg, coords=coords, defer_class=True, normed=normed, sampled_rows_only=fused)
+                if isinstance(attn_mask, _AttnMaskRows):
+                    # the mask rows of the sampled keys straight from the segment logits, then the two rules below
+                    batched_attn = ops.attn_mask_rows(attn_mask.logits, attn_mask.tables, plan["gidx"], n_scenes,
+                                                      curr_sample_size, n_valid, outs=None if bufs is None else bufs[4])
+                elif fused and attn_mask.F.dtype == torch.bool and attn_mask.F.shape[1] <= fused_attn_max_queries():
                     # the mask rows, the all-masked-query rule (reference :346) and the padding mask (:343): two launches
                     batched_attn = ops.sample_keys(None, attn_mask.F.contiguous(), None, plan["gidx"], n_scenes,
                                                    curr_sample_size, n_valid,
                                                    outs=None if bufs is None else (None, bufs[4], None))
                 else:
+                    decomposed_attn = attn_mask.decomposed_features
                     batched_attn = _stack([decomposed_attn[k][rand_idx[k], :] for k in range(n_scenes)])
                     # a query whose sampled keys are all masked attends to everything (reference :346)
                     batched_attn.permute(0, 2, 1)[batched_attn.sum(1) == curr_sample_size] = False
@@ -529,7 +533,9 @@ class Mask3D(nn.Module):
         return norm(queries), queries
 
     def mask_module(self, query_feat, mask_features, mask_segments, num_pooling_steps, ret_attn_mask=True,
-                    point2segment=None, coords=None, defer_class=False, normed=None):
+                    point2segment=None, coords=None, defer_class=False, normed=None, sampled_rows_only=False):
+        # sampled_rows_only: the caller can take an _AttnMaskRows (the logits and the child tables of the pooling steps)
+        # in place of the pooled and thresholded mask tensor, and hands it to ops.attn_mask_rows with its key sample
         query_feat = self.decoder_norm(query_feat) if normed is None else normed
         head = self.mask_embed_head
         Q = query_feat.shape[-2]
@@ -580,15 +586,15 @@ class Mask3D(nn.Module):
                         off += seg.shape[0]
                     rows = torch.cat(parts).contiguous()
                     cm._usc_p2s_batched = rows          # geometry only: built once per batch
-            for step in range(num_pooling_steps):
-                if step == 0:
-                    # child table -> segment rows, folded once per batch (geometry only): the kernel then reads
-                    # child -> logits row in two dependent loads instead of three, in all 12 calls of the step
-                    pooled = ops.avgpool_down2(pooled, _child_segment_table(cm, ts, rows),
-                                               threshold=num_pooling_steps == 1)
-                else:
-                    pooled = ops.avgpool_down2(pooled, cm.stride_map(ts)["nbr2"],
-                                               threshold=step == num_pooling_steps - 1)
+            # child table -> segment rows, folded once per batch (geometry only): the kernel then reads
+            # child -> logits row in two dependent loads instead of three, in all 12 calls of the step
+            tables = [_child_segment_table(cm, ts, rows)]
+            tables += [cm.stride_map(ts << step)["nbr2"] for step in range(1, num_pooling_steps)]
+            if sampled_rows_only and ops.attn_mask_rows_applies(pooled, tables, len(mask_segments)):
+                # the caller pools the rows of its sampled keys only, in one launch (ops.attn_mask_rows)
+                return outputs_class, output_segments, _AttnMaskRows(pooled, tables)
+            for step, table in enumerate(tables):
+                pooled = ops.avgpool_down2(pooled, table, threshold=step == num_pooling_steps - 1)
                 ts *= 2
             attn_mask = me.SparseTensor(features=pooled, coordinate_manager=cm,
                                         coordinate_map_key=ME.CoordinateMapKey(ts))
@@ -939,6 +945,15 @@ def _padded_index(n, size, device):
         midx[:n] = False
         hit = _PAD_CACHE[key] = (idx, midx)
     return hit
+
+
+class _AttnMaskRows:
+    """What mask_module hands back instead of the attention-mask tensor of a level when its caller samples the level's
+    rows anyway: the [segments, Q] logits (detached) and the child tables of the pooling steps, finest first."""
+    __slots__ = ("logits", "tables")
+
+    def __init__(self, logits, tables):
+        self.logits, self.tables = logits, tables
 
 
 def _child_segment_table(cm, ts, rows):

@@ -1016,6 +1016,55 @@ def sample_keys(feats, mask, pos, idx, n_scenes, K, n_valid, outs=None, unique=F
                              valid_unique)
 
 
+ATTN_MASK_ROWS_MAX_QUERIES = 128
+ATTN_MASK_ROWS_MAX_STEPS = 4
+
+
+def attn_mask_rows_applies(logits, tables, n_scenes) -> bool:
+    """Whether attn_mask_rows takes these logits and child tables (else: the avgpool_down2 chain and sample_keys)."""
+    q = logits.shape[1]
+    ld = logits.stride(0) if logits.shape[0] > 1 else q
+    return (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+            and q % 4 == 0 and 4 <= q <= ATTN_MASK_ROWS_MAX_QUERIES and ld % 4 == 0 and logits.data_ptr() % 16 == 0
+            and 1 <= len(tables) <= ATTN_MASK_ROWS_MAX_STEPS and 1 <= n_scenes <= 16)
+
+
+def attn_mask_rows(logits, tables, idx, n_scenes, K, n_valid, outs=None, fix=True):
+    """The thresholded attention-mask rows of the sampled keys of one decoder pass, bool[B, K, Q], in one launch (and
+    sample_keys' all-masked-column launch): the bytes of avgpool_down2 over `tables` in turn (the last step with
+    threshold=True) followed by sample_keys(None, mask, None, idx, ...), computed for the rows `idx` only.
+    logits: f32[segments, Q] (may be a column slice), Q a multiple of 4 up to 128; tables: 1 to 4 child tables
+    i32[8, n_j], the first one holding rows of `logits`; idx: i64[n_scenes*K] rows of the last table's level.
+    outs: the caller's bool[B, K, Q] buffer (an input of a captured pass).  fix=False leaves the all-masked-column rule
+    out (tests)."""
+    if not attn_mask_rows_applies(logits, tables, n_scenes):
+        raise RuntimeError("attn_mask_rows: f32 HIP logits with 4..128 queries (a multiple of 4), a leading dimension "
+                           "that is a multiple of 4, 1..4 child tables and <= 16 scenes")
+    _chk(idx, torch.int64, "idx")
+    q, d, dev = logits.shape[1], len(tables), logits.device
+    for t in tables:
+        _chk(t, torch.int32, "child table")
+        if t.dim() != 2 or t.shape[0] != 8 or t.shape[1] < 1:
+            raise RuntimeError("attn_mask_rows: a child table must be i32 [8, n]")
+    if idx.shape[0] != n_scenes * K or len(n_valid) != n_scenes:
+        raise RuntimeError("attn_mask_rows: inconsistent sizes")
+    if outs is None:
+        out = torch.empty((n_scenes, K, q), dtype=torch.bool, device=dev)
+    else:
+        out = outs.detach()
+        if tuple(out.shape) != (n_scenes, K, q) or out.dtype != torch.bool or not out.is_contiguous():
+            raise RuntimeError(f"attn_mask_rows: the mask buffer {tuple(out.shape)} {out.dtype} does not fit "
+                               f"{(n_scenes, K, q)} contiguous bool")
+    ld = logits.stride(0) if logits.shape[0] > 1 else q
+    tabs = (ctypes.c_void_p * d)(*[t.data_ptr() for t in tables])
+    rows = (ctypes.c_int64 * d)(*[t.shape[1] for t in tables])
+    nv = (ctypes.c_int32 * n_scenes)(*[int(v) for v in n_valid])
+    ws = _ws(lib.usc_attn_mask_rows_ws_bytes(n_scenes, K, q, d), dev)
+    check(lib.usc_attn_mask_rows(_ptr(logits), ld, q, d, tabs, rows, _ptr(idx), n_scenes, K, nv, _ptr(out), _ptr(ws),
+                                 ws.numel(), 0 if fix else 1, _stream()), "usc_attn_mask_rows")
+    return out
+
+
 def gather_rows_i32(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """Row gather of an int32 table (coordinates) through the same kernel (bit pattern copy)."""
     _chk(src, torch.int32, "src")
