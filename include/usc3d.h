@@ -1440,6 +1440,59 @@ int usc_felz_merge_host(const int32_t* edge_a, const int32_t* edge_b,
                         float kthr, int32_t seg_min_verts, int32_t* comps);
 
 /* ------------------------------------------------------------------------
+ * F2b the same over-segmentation for a point cloud without a mesh
+ * (csrc/felz_points.hip): the edge set is a symmetrised k-NN table instead of
+ * the triangles' sides.  The reference reconstructs a mesh for such clouds
+ * (pseudo_masks/datasets/preprocess/stanford.py:80-135, open3d Poisson) only
+ * to have edges; sort and merge are F2's.
+ *
+ * usc_felz_knn_edges: idx i32[n,k], count i32[n] as usc_knn_hybrid_grid writes
+ * them for query == ref (1 <= k <= 64, 0 <= n < 2^31).  PRECONDITION: the
+ * first count[i] entries of row i are distinct and lie in [0, n); an entry
+ * outside [0, n) is skipped, never dereferenced, and a count is clamped to
+ * [0, k].  For row i ascending and position p < count[i] ascending, with
+ * j = idx[i,p] != i, the edge (edge_a = i, edge_b = j) is emitted iff i < j,
+ * or i > j and i does not occur in idx[j, :count[j]].  So every undirected
+ * pair that appears in either list is emitted exactly once, oriented from the
+ * emitting row, in (i, p) order.  (A point need not be first in its own row:
+ * coincident points sort by index.)
+ * ONE call into WORST-CASE buffers, not a count/fill pair: edge_a and edge_b
+ * hold n * k entries each (a point that is missing from its own full row, as
+ * among more than k coincident points, emits k edges), the first *n_edges of
+ * them are written and the rest is left alone; n_edges i64[1] is DEVICE
+ * memory, written on the stream.  The caller reads it back when it needs the
+ * number on the host (the pipeline ends in the host merge anyway).  Steps: a
+ * per-row bit mask of the emitting positions, the device exclusive scan of
+ * their popcounts, and the write pass.  ws holds
+ * usc_felz_knn_edges_ws_bytes(n) bytes (-1 for n out of range).
+ *
+ * usc_felz_point_edge_weights: weights f32[n_edges] of an explicit edge list
+ * over points, colors, normals f32[n_points,3].
+ *   oriented = 1  usc_felz_edge_weights' arithmetic, operation for operation
+ *                 (one shared device function): for the same endpoints,
+ *                 normals and colours the bits are equal.
+ *   oriented = 0  for estimated normals, whose sign is arbitrary
+ *                 (usc_normals_pca), so the convexity test means nothing:
+ *                 normal_dist = 1 - |dot|, and no weight is squared.
+ * A zero-length edge (coincident points) has a NaN direction; `dot2 > 0` is
+ * then false and the weight is the finite normal_dist * color_dist.  An
+ * endpoint outside [0, n_points) reads nothing and gives +inf.
+ * Both: explicit stream, no allocation, no host synchronisation, no atomics;
+ * two calls write the same bytes; bad arguments are refused before any launch
+ * with nothing written.
+ * ---------------------------------------------------------------------- */
+int64_t usc_felz_knn_edges_ws_bytes(int64_t n_points);
+int usc_felz_knn_edges(const int32_t* idx, const int32_t* count, int64_t n_points,
+                       int32_t k, int32_t* edge_a, int32_t* edge_b,
+                       int64_t* n_edges, void* ws, int64_t ws_bytes,
+                       usc_stream_t s);
+int usc_felz_point_edge_weights(const float* points, const float* colors,
+                                const float* normals, int64_t n_points,
+                                const int32_t* edge_a, const int32_t* edge_b,
+                                int64_t n_edges, int32_t oriented,
+                                float* weights, usc_stream_t s);
+
+/* ------------------------------------------------------------------------
  * Validation AP — the mask / GT-instance overlap counts of the ScanNet instance
  * evaluator (benchmark/evaluate_semantic_instance.py, assign_instances_for_scan*).
  * masks u8[n, ld] row-major, nonzero = point in mask (np.not_equal(mask, 0));

@@ -13,6 +13,7 @@ Replicas only, like pseudo_masks_run.py: rank r of W takes the scenes r, r+W, ..
     python tools/scene_files_from_scans.py --scans SCANS --out SCENES --dino-weights DINO.pth --csc-weights CSC.pth
     python tools/scene_files_from_scans.py --scans SCANS --out SCENES --no-images --csc-weights CSC.pth
     python tools/scene_files_from_scans.py --scans SCANS --out SCENES --layout arkit --csc-weights CSC.pth
+    python tools/scene_files_from_scans.py --scans SCANS --out SCENES --layout points --csc-weights CSC.pth --graph-k 8 --graph-radius 0.1
 
 --dino-weights is the published DINO ViT-S/8 checkpoint (a state_dict; not part of this repository);
 --random-weights SEED initialises the encoder from a seed instead (smoke runs and benchmarks: the features mean nothing).
@@ -25,7 +26,12 @@ reads no frame and writes the geometry modality alone (`modality: geom`); the im
 --layout arkit reads mesh-only scans (`SCANS/{scene}/{scene}_3dod_mesh.ply`, ARKitScenes' naming, or a flat
 `SCANS/{scene}.ply`; scans.load_mesh_only_scan, reference pseudo_masks/datasets/arkit.py): the mesh is cleaned,
 over-segmented at every size of --segments-min-verts (default 50 100 150 200), small segments are removed and the rest is
-shifted to the origin; the file is geometry-only and holds the segments of level --segment-dimension-order."""
+shifted to the origin; the file is geometry-only and holds the segments of level --segment-dimension-order.
+--layout points reads coloured point clouds without a mesh (`SCANS/{scene}/{scene}.ply` or a flat `SCANS/{scene}.ply`, a
+vertex element with x y z red green blue and optionally nx ny nz; scans.load_point_cloud_scan): the cloud is
+over-segmented on its k-NN graph (--graph-k neighbours inside --graph-radius metres; unmeasured starting values, DESIGN.md
+§3.30) at every size of --segments-min-verts (default 50), --small-segments says what becomes of segments the graph left
+small or unconnected, and the file is geometry-only as for arkit."""
 import argparse
 import os
 import sys
@@ -74,7 +80,7 @@ def process_scan(scan_dir, out_dir, model, args, model_3d=None):
     """-> (scene name, voxels, frames used, frames dropped, seconds) or None when the scene file exists."""
     from unscene3d_amd.pseudo_masks import scans
 
-    name = scans.mesh_only_scan_path(scan_dir)[0] if args.layout == "arkit" else os.path.basename(os.path.normpath(scan_dir))
+    name = scans.mesh_only_scan_path(scan_dir)[0] if args.layout != "scannet" else os.path.basename(os.path.normpath(scan_dir))
     path = os.path.join(out_dir, f"{name}.npz")
     if os.path.exists(path):
         return None
@@ -85,7 +91,8 @@ def process_scan(scan_dir, out_dir, model, args, model_3d=None):
                               attention=args.attention, every=args.every,
                               device=next((model_3d if model is None else model).parameters()).device, model_3d=model_3d,
                               resolution_scale=args.resolution_scale, precision_3d=args.precision_3d,
-                              images=not args.no_images and args.layout != "arkit")
+                              images=not args.no_images and args.layout == "scannet", graph_k=args.graph_k,
+                              graph_radius=args.graph_radius, small_segments=args.small_segments)
     os.makedirs(out_dir, exist_ok=True)
     tmp = path + ".tmp.npz"
     np.savez(tmp, **scene)
@@ -117,20 +124,25 @@ def main(argv=None):
     ap.add_argument("--height", type=int, default=192)
     ap.add_argument("--width", type=int, default=256)
     ap.add_argument("--segments-min-verts", type=int, nargs="+", default=None, metavar="N",
-                    help="smallest segment of the over-segmentation: one number (default 50); --layout arkit: one per "
-                         "level (default 50 100 150 200)")
-    ap.add_argument("--layout", choices=("scannet", "arkit"), default="scannet",
-                    help="arkit: mesh-only scans, geometry-only scene files")
+                    help="smallest segment of the over-segmentation: one number (default 50); --layout arkit / points: "
+                         "one per level (default 50 100 150 200 / 50)")
+    ap.add_argument("--layout", choices=("scannet", "arkit", "points"), default="scannet",
+                    help="arkit: mesh-only scans; points: point clouds without a mesh; both give geometry-only scene files")
     ap.add_argument("--segment-dimension-order", type=int, default=0, metavar="L",
-                    help="--layout arkit: the level of --segments-min-verts whose segments are written")
+                    help="--layout arkit / points: the level of --segments-min-verts whose segments are written")
+    ap.add_argument("--graph-k", type=int, default=8, metavar="K", help="--layout points: neighbours per point of the graph")
+    ap.add_argument("--graph-radius", type=float, default=0.1, metavar="R",
+                    help="--layout points: neighbours lie strictly inside this radius")
+    ap.add_argument("--small-segments", choices=("merge", "drop", "keep"), default="merge",
+                    help="--layout points: small or unconnected segments join the nearest kept one, lose their points, or stay")
     args = ap.parse_args(argv)
     if args.frame_batch < 0 or args.every < 1:
         ap.error("--frame-batch needs K >= 0 and --every K >= 1")
-    if args.layout == "arkit":
+    if args.layout != "scannet":
         args.no_images = True
     elif args.segments_min_verts is not None:
         if len(args.segments_min_verts) != 1:
-            ap.error("--segments-min-verts takes one number unless --layout arkit is given")
+            ap.error("--segments-min-verts takes one number unless --layout arkit or points is given")
         args.segments_min_verts = args.segments_min_verts[0]
     has_2d = args.dino_weights is not None or args.random_weights is not None
     has_3d = args.csc_weights is not None or args.csc_random_weights is not None
@@ -144,9 +156,9 @@ def main(argv=None):
     local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
-    if args.layout == "arkit":
+    if args.layout != "scannet":
         from unscene3d_amd.pseudo_masks.scans import mesh_only_scans
-        dirs = mesh_only_scans(args.scans)
+        dirs = mesh_only_scans(args.scans)                          # the point-cloud layout lists its scans the same way
     else:
         dirs = sorted(d for d in (os.path.join(args.scans, e) for e in os.listdir(args.scans)) if os.path.isdir(d))
     mine = scene_shard(len(dirs), rank, world)

@@ -240,6 +240,9 @@ SIGNATURES = {
     "usc_felz_vertex_normals": (C.c_int, [_p, _p, _p, _i64, _p, _p]),
     "usc_felz_edge_weights": (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, _p, _p]),
     "usc_felz_merge_host": (C.c_int, [_p, _p, _p, _i64, _i32, _f32, _i32, _p]),
+    "usc_felz_knn_edges_ws_bytes": (_i64, [_i64]),
+    "usc_felz_knn_edges": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _i64, _p]),
+    "usc_felz_point_edge_weights": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, _i32, _p, _p]),
     "usc_furthest_point_sampling": (C.c_int, [_p, _i32, _i32, _i32, _p, _p, _p]),
     "usc_fourier_posenc": (C.c_int, [_p, _i64, _p, _p, _p, _i32, _p, _p]),
     "usc_mask_gt_overlap": (C.c_int, [_p, _i64, _i32, _i64, _p, _i32, _p, _p]),

@@ -19,14 +19,12 @@
 #include <vector>
 
 #include "common.h"
+#include "felz_weight.h"
 
 #pragma clang fp contract(off)
 
 namespace usc {
 namespace {
-
-struct V3 { float x, y, z; };
-__device__ inline V3 ld3(const float* p, int64_t i) { return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
 
 __global__ __launch_bounds__(256) void felz_face_normals_kernel(const float* __restrict__ P, const int32_t* __restrict__ faces,
                                                                 int64_t nf, float* __restrict__ fn) {
@@ -73,17 +71,8 @@ __global__ __launch_bounds__(256) void felz_edge_weights_kernel(const float* __r
   const int j = (int)(e - 3 * f);
   const int32_t i1 = faces[3 * f], i2 = faces[3 * f + 1], i3 = faces[3 * f + 2];
   const int32_t a = j == 2 ? i3 : i1, b = j == 1 ? i3 : i2;
-  const V3 n1 = ld3(N, a), n2 = ld3(N, b), p1 = ld3(P, a), p2 = ld3(P, b), c1 = ld3(C, a), c2 = ld3(C, b);
-  float dx = p2.x - p1.x, dy = p2.y - p1.y, dz = p2.z - p1.z;
-  const float dd = sqrtf(dx * dx + dy * dy + dz * dz);
-  dx /= dd; dy /= dd; dz /= dd;
-  const float dot = n1.x * n2.x + n1.y * n2.y + n1.z * n2.z;
-  const float normal_dist = 1.0f - dot;
-  const float color_dist = fabsf(c1.x - c2.x) + fabsf(c1.y - c2.y) + fabsf(c1.z - c2.z);
-  float dist = normal_dist * color_dist;
-  const float dot2 = n2.x * dx + n2.y * dy + n2.z * dz;
-  if (dot2 > 0 && (double)color_dist < 0.05) dist = dist * dist;     // the reference compares against a double literal
-  ea[e] = a; eb[e] = b; w[e] = dist;
+  ea[e] = a; eb[e] = b;
+  w[e] = felz_edge_weight<true>(ld3(P, a), ld3(P, b), ld3(C, a), ld3(C, b), ld3(N, a), ld3(N, b));
 }
 
 }  // namespace

@@ -41,7 +41,12 @@ with those indices by one — and the live writer saves xyz only, as tools/pseud
 segment ids come from the mesh: the builder re-runs the scan builder's deterministic mesh stages
 (`scans.load_mesh_only_scan`) and requires `{scene}_cloud.npy` to equal the kept, shifted vertices row for row, bit for
 bit in f32 (ValueError naming the scene otherwise); the masks are then taken row for row, with no 1-NN.  There is no
-ground truth: label 0, instance -1 and no `instance_gt` file, this builder's convention for scans without ground truth."""
+ground truth: label 0, instance -1 and no `instance_gt` file, this builder's convention for scans without ground truth.
+
+Point-cloud scans (`layout="points"`): `SCANS/{scene}/{scene}.ply` or `SCANS/{scene}.ply` with a vertex
+element only.  The same files and entries as for a mesh-only scan, through `build_point_cloud_tables`: xyz, colours and
+segment ids are `scans.load_point_cloud_scan`'s; the normal columns are the file's nx, ny, nz when it has them, else
+`ops.estimate_normals(xyz, 0.1, 30)`.  Ground-truth columns (S3DIS's annotation folders) are not read."""
 from __future__ import annotations
 
 import glob
@@ -213,6 +218,51 @@ def mesh_only_points_table(xyz, rgb, normals, segment_ids):
                       np.asarray(segment_ids, np.int64)[:, None], labels]).astype(np.float32)
 
 
+def _load_pseudo_files(scene, pseudo_dir):
+    """-> (cloud, masks) of a scene, or None with the reference's message when a file is missing."""
+    try:
+        return (np.load(os.path.join(pseudo_dir, f"{scene}_cloud.npy")),
+                np.load(os.path.join(pseudo_dir, f"{scene}_masks.npy")))
+    except FileNotFoundError as e:
+        print(f"Could not load pseudo masks for {scene}: {e.filename}")
+        return None
+
+
+def _frameless_tables(m, scene, raw_path, cloud, masks, dev, normals=None):
+    """The tables of a scan without frames or ground truth from its loaded dict `m` (`scans.load_mesh_only_scan` /
+    `load_point_cloud_scan`): the cloud file must equal m["xyz"] bit for bit in f32, the masks are taken row for row.
+    normals: f32[N,3] to store, None to estimate them from the points."""
+    xyz = m["xyz"].astype(np.float32)
+    if cloud.ndim != 2 or cloud.shape[1] < 3 or cloud.shape[0] != xyz.shape[0] or \
+            not np.array_equal(np.ascontiguousarray(cloud[:, :3], dtype=np.float32).view(np.uint32), xyz.view(np.uint32)):
+        raise ValueError(f"{scene}: {scene}_cloud.npy {list(cloud.shape)} is not the scan's {xyz.shape[0]} kept vertices "
+                         f"row for row (was it written from a scene file of this scan with the same --segments-min-verts?)")
+    if masks.ndim != 2 or masks.shape[0] != xyz.shape[0]:
+        raise ValueError(f"{scene}: pseudo masks {list(masks.shape)} do not match the cloud's {xyz.shape[0]} points")
+    if normals is None:
+        normals = ops.estimate_normals(torch.from_numpy(xyz).to(dev), 0.1, 30).cpu().numpy()
+    mean, second = color_moments(m["rgb"])
+    return {"points": mesh_only_points_table(xyz, m["rgb"], normals, m["segment_ids"]),
+            "freemasks": masks.astype(np.float32), "gt": None, "color_mean": mean, "color_std": second, "connectivity": m["seg_connectivity"], "raw_filepath": raw_path,
+            "raw_description_filepath": "", "raw_instance_filepath": "", "raw_segmentation_filepath": "",
+            "raw_label_filepath": None, "scene": scene}
+
+
+def build_point_cloud_tables(scan, pseudo_dir, device="cuda", segments_min_verts=scans.POINTS_SEGMENTS_MIN_VERTS,
+                             segment_dimension_order=0, graph_k=8, graph_radius=0.1, small_segments="merge"):
+    """One point-cloud scan -> the dict of `build_mesh_only_tables`, or None (with a message) when its pseudo-mask files
+    are missing.  xyz, colours and segment ids are `scans.load_point_cloud_scan`'s (same graph arguments as the scene
+    file was written with); the normals are the file's when it has them, else `ops.estimate_normals(xyz, 0.1, 30)`."""
+    dev = torch.device(device)
+    scene, cloud_path = scans.point_cloud_scan_path(scan)
+    files = _load_pseudo_files(scene, pseudo_dir)
+    if files is None:
+        return None
+    m = scans.load_point_cloud_scan(scan, segments_min_verts, segment_dimension_order, graph_k, graph_radius,
+                                    small_segments, device=dev)
+    return _frameless_tables(m, scene, cloud_path, *files, dev, m["normals"] if m["normals_from_file"] else None)
+
+
 def build_mesh_only_tables(scan, pseudo_dir, device="cuda", segments_min_verts=scans.ARKIT_SEGMENTS_MIN_VERTS,
                            segment_dimension_order=0):
     """One mesh-only scan -> the dict of `build_scene_tables` (gt None, connectivity of the written level), or None
@@ -221,26 +271,11 @@ def build_mesh_only_tables(scan, pseudo_dir, device="cuda", segments_min_verts=s
     bit for bit, the masks are taken row for row, the normals are `ops.estimate_normals(xyz, 0.1, 30)`."""
     dev = torch.device(device)
     scene, mesh_path = scans.mesh_only_scan_path(scan)
-    try:
-        cloud = np.load(os.path.join(pseudo_dir, f"{scene}_cloud.npy"))
-        masks = np.load(os.path.join(pseudo_dir, f"{scene}_masks.npy"))
-    except FileNotFoundError as e:
-        print(f"Could not load pseudo masks for {scene}: {e.filename}")
+    files = _load_pseudo_files(scene, pseudo_dir)
+    if files is None:
         return None
     m = scans.load_mesh_only_scan(scan, segments_min_verts, segment_dimension_order, device=dev)
-    xyz = m["xyz"].astype(np.float32)
-    if cloud.ndim != 2 or cloud.shape[1] < 3 or cloud.shape[0] != xyz.shape[0] or \
-            not np.array_equal(np.ascontiguousarray(cloud[:, :3], dtype=np.float32).view(np.uint32), xyz.view(np.uint32)):
-        raise ValueError(f"{scene}: {scene}_cloud.npy {list(cloud.shape)} is not the scan's {xyz.shape[0]} kept vertices "
-                         f"row for row (was it written from a scene file of this scan with the same --segments-min-verts?)")
-    if masks.ndim != 2 or masks.shape[0] != xyz.shape[0]:
-        raise ValueError(f"{scene}: pseudo masks {list(masks.shape)} do not match the cloud's {xyz.shape[0]} points")
-    normals = ops.estimate_normals(torch.from_numpy(xyz).to(dev), 0.1, 30).cpu().numpy()
-    mean, second = color_moments(m["rgb"])
-    return {"points": mesh_only_points_table(xyz, m["rgb"], normals, m["segment_ids"]),
-            "freemasks": masks.astype(np.float32), "gt": None, "color_mean": mean, "color_std": second, "connectivity": m["seg_connectivity"], "raw_filepath": mesh_path,
-            "raw_description_filepath": "", "raw_instance_filepath": "", "raw_segmentation_filepath": "",
-            "raw_label_filepath": None, "scene": scene}
+    return _frameless_tables(m, scene, mesh_path, *files, dev)
 
 
 def color_moments(rgb):
@@ -267,7 +302,7 @@ def save_yaml(path, obj):
 
 def build_dataset(scans_root, split_files, pseudo_dir, out_dir, oracle=False, device="cuda",
                   foreground_ids=FOREGROUND_CLASS_IDS, segments_min_verts=None, write_connectivity=False,
-                  layout="scannet", segment_dimension_order=0):
+                  layout="scannet", segment_dimension_order=0, graph_k=8, graph_radius=0.1, small_segments="merge"):
     """`split_files`: {mode: text file with one scan name per line} (ScanNet's scannetv2_train.txt / _val.txt), or
     {mode: list of names}.  Every scan `scans_root/<name>` of a mode goes through `build_scene_tables`; scans without
     pseudo-mask files are skipped with a message.  Writes the files the module docstring lists.
@@ -279,14 +314,17 @@ def build_dataset(scans_root, split_files, pseudo_dir, out_dir, oracle=False, de
     layout="arkit": mesh-only scans through `build_mesh_only_tables` (module docstring); names are ARKitScenes' scene
     ids (a sub-directory or a .ply file of `scans_root`), files are `{mode}/{scene}.npy`, entries carry
     `scene_type: room` and empty raw description / instance / segmentation paths; `oracle` is refused.
+    layout="points": point-cloud scans through `build_point_cloud_tables` with `graph_k`, `graph_radius` and
+    `small_segments` (`segments_min_verts` None is scans.POINTS_SEGMENTS_MIN_VERTS); everything else as for "arkit".
     -> {mode: list of database entries}."""
-    if layout not in ("scannet", "arkit"):
-        raise ValueError(f"build_dataset: layout must be 'scannet' or 'arkit', got {layout!r}")
-    arkit = layout == "arkit"
+    if layout not in scans.LAYOUTS:
+        raise ValueError(f"build_dataset: layout must be 'scannet', 'arkit' or 'points', got {layout!r}")
+    arkit = layout != "scannet"                       # frame-less scans without ground truth: "arkit" and "points"
     if arkit and oracle:
-        raise ValueError("build_dataset(layout='arkit'): mesh-only scans have no ground truth for oracle masks")
+        raise ValueError(f"build_dataset(layout={layout!r}): such scans have no ground truth for oracle masks")
     if segments_min_verts is None:
-        segments_min_verts = scans.ARKIT_SEGMENTS_MIN_VERTS if arkit else 20
+        segments_min_verts = {"scannet": 20, "arkit": scans.ARKIT_SEGMENTS_MIN_VERTS,
+                              "points": scans.POINTS_SEGMENTS_MIN_VERTS}[layout]
     out_dir = os.fspath(out_dir)
     os.makedirs(out_dir, exist_ok=True)
     save_yaml(os.path.join(out_dir, "label_database.yaml"), LABEL_DATABASE)
@@ -303,7 +341,11 @@ def build_dataset(scans_root, split_files, pseudo_dir, out_dir, oracle=False, de
         database = []
         for name in names:
             scan_dir = os.path.join(os.fspath(scans_root), name)
-            if arkit:
+            if layout == "points":
+                t = build_point_cloud_tables(scan_dir, pseudo_dir, device=device, segments_min_verts=segments_min_verts,
+                                             segment_dimension_order=segment_dimension_order, graph_k=graph_k,
+                                             graph_radius=graph_radius, small_segments=small_segments)
+            elif arkit:
                 t = build_mesh_only_tables(scan_dir, pseudo_dir, device=device, segments_min_verts=segments_min_verts,
                                            segment_dimension_order=segment_dimension_order)
             else:

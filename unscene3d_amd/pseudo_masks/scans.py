@@ -26,9 +26,15 @@ alignment and no frames.  `load_mesh_only_scan` cleans the mesh, over-segments i
 of too-small segments and shifts the rest to the origin; `build_scene` then runs the same voxelisation and 3D backbone
 and writes a geometry-only scene file.
 
+Point-cloud scans (`layout="points"`): a scan is `DIR/{scene}/{scene}.ply` or a flat `DIR/{scene}.ply`
+with a vertex element only (S3DIS rooms, laser scans, LiDAR).  `load_point_cloud_scan` over-segments the cloud on its
+k-NN graph (`felzenszwalb_cpp.segment_points`; the reference reconstructs a Poisson mesh first,
+pseudo_masks/datasets/preprocess/stanford.py:80-135), and `build_scene` writes a geometry-only scene file as for a
+mesh-only scan.
+
 Not covered: depth
 images, label / instance columns (the training dataset's builder, datasets/preprocessing.py, reads them through
-`read_ply_vertex_properties`), chunked scenes, the S3DIS layout."""
+`read_ply_vertex_properties`), chunked scenes, S3DIS's annotation folders and images for point-cloud scans."""
 from __future__ import annotations
 
 import glob
@@ -42,6 +48,9 @@ PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": 
 FRAME_SUFFIXES = (".jpg", ".png", ".npy")
 ARKIT_SEGMENTS_MIN_VERTS = (50, 100, 150, 200)     # segments_min_vert_nums of the reference's ARKit configuration
 ARKIT_MESH_SUFFIX = "_3dod_mesh.ply"
+POINTS_SEGMENTS_MIN_VERTS = (50,)                  # layout="points": one level unless the caller asks for more
+SMALL_SEGMENTS = ("merge", "drop", "keep")         # load_point_cloud_scan(small_segments=...)
+LAYOUTS = ("scannet", "arkit", "points")
 SCENE_NN_3D = "grid"     # the 1-NN of build_scene's 3D branch: what profiles/knn1_grid.txt measured faster
 
 
@@ -247,6 +256,27 @@ def read_ply_vertex_properties(path, names):
     raise ValueError(f"{path}: needs a vertex element")
 
 
+def read_ply_points(path):
+    """A coloured point cloud -> (points f32[N,3], colors f32[N,3] in [0,1], normals f32[N,3] or None).
+
+    Only the vertex element is needed, with x, y, z, red, green, blue (integer colours are divided by 255, as in
+    `read_ply_mesh`); nx, ny, nz are read when all three are there, else normals is None.  A face element, or any other
+    element behind the vertex element, is ignored — a mesh file is a valid point cloud.  Same formats and header rules
+    as `read_ply_vertex_properties`, which reads the records."""
+    path = os.fspath(path)
+    with open(path, "rb") as f:
+        _, elements = _ply_header(f, path)
+    have = [p[2] for name, _, props in elements if name == "vertex" for p in props if p[0] == "scalar"]
+    names = ["x", "y", "z", "red", "green", "blue"]
+    with_normals = all(n in have for n in ("nx", "ny", "nz"))
+    v = read_ply_vertex_properties(path, names + (["nx", "ny", "nz"] if with_normals else []))
+    points = np.stack([v["x"], v["y"], v["z"]], 1).astype(np.float32)
+    rgb = [v[n] for n in ("red", "green", "blue")]
+    colors = np.stack([c.astype(np.float64) / 255.0 if c.dtype.kind in "iu" else c.astype(np.float64) for c in rgb], 1)
+    normals = np.stack([v["nx"], v["ny"], v["nz"]], 1).astype(np.float32) if with_normals else None
+    return points, colors.astype(np.float32), normals
+
+
 # ------------------------------------------------------------------------------------------------------------ frames
 def frame_files(color_dir, pose_dir, every=1):
     """-> [(colour file, pose file)] in the reference's order: `sorted()` of the file names of each directory, paired by
@@ -323,13 +353,13 @@ def clean_segments(comps, min_vert_num=500):
     return comps[valid], valid
 
 
-def mesh_only_scan_path(scan):
+def mesh_only_scan_path(scan, suffix=ARKIT_MESH_SUFFIX):
     """-> (scene name, mesh file) of a mesh-only scan: the directory `DIR/{scene}` holding `{scene}_3dod_mesh.ply`, or
-    the flat file `DIR/{scene}.ply`."""
+    the flat file `DIR/{scene}.ply`.  `suffix`: what the file inside a directory is called after the scene name."""
     scan = os.path.normpath(os.fspath(scan))
     if os.path.isdir(scan):
         scene = os.path.basename(scan)
-        return scene, os.path.join(scan, scene + ARKIT_MESH_SUFFIX)
+        return scene, os.path.join(scan, scene + suffix)
     if scan.endswith(".ply"):
         return os.path.basename(scan)[:-4], scan
     return os.path.basename(scan), scan + ".ply"
@@ -400,10 +430,129 @@ def load_mesh_only_scan(scan, segments_min_verts=ARKIT_SEGMENTS_MIN_VERTS, segme
             "segment_ids": np.ascontiguousarray(segments[:, level]), "seg_connectivity": conn, "kept": kept[valid]}
 
 
+# -------------------------------------------------------------------------------------------------- point-cloud scans
+def point_cloud_scan_path(scan):
+    """-> (scene name, cloud file) of a point-cloud scan: `DIR/{scene}/{scene}.ply` or the flat file `DIR/{scene}.ply`."""
+    return mesh_only_scan_path(scan, ".ply")
+
+
+def point_cloud_scans(root):
+    """The scans of a directory in the point-cloud layout, sorted by scene name: sub-directories and *.ply files."""
+    return mesh_only_scans(root)
+
+
+def _check_point_cloud_args(segments_min_verts, segment_dimension_order, graph_k, graph_radius, small_segments):
+    levels = tuple(int(n) for n in np.atleast_1d(segments_min_verts))
+    if not levels or not 0 <= int(segment_dimension_order) < len(levels):
+        raise ValueError(f"segment_dimension_order {segment_dimension_order} is no level of segments_min_verts {levels}")
+    if small_segments not in SMALL_SEGMENTS:
+        raise ValueError(f"small_segments must be one of {SMALL_SEGMENTS}, got {small_segments!r}")
+    if not 0 <= int(graph_k) <= 63:
+        raise ValueError(f"graph_k must be 0 .. 63, got {graph_k}")
+    if not (float(graph_radius) > 0 and np.isfinite(float(graph_radius))):
+        raise ValueError(f"graph_radius must be a positive finite number, got {graph_radius!r}")
+    return levels
+
+
+def merge_floaters(labels, connectivity, min_verts, nearest):
+    """stanford.py:114-128 with the deviation below: a segment with fewer than `min_verts` points, or one that no
+    connectivity pair names, is a floater the graph never reached; it takes the segment of the nearest point of a KEPT
+    (non-floater) segment, measured from the floater's first row.  labels i[N]; connectivity i[P,2];
+    nearest(query_rows i64[Q], ref_rows i64[R]) -> i64[Q], positions in ref_rows.  -> labels i64[N], not renumbered.
+    Deviation: the reference takes the nearest point of ANY other segment, which can be another floater, so the result
+    depends on the order of the loop; here a floater always lands in a kept segment.  No kept segment: all 0."""
+    labels = np.asarray(labels, np.int64)
+    ids, first, counts = np.unique(labels, return_index=True, return_counts=True)
+    floater = (counts < int(min_verts)) | ~np.isin(ids, np.asarray(connectivity, np.int64).reshape(-1))
+    if not floater.any():
+        return labels.copy()
+    if floater.all():
+        return np.zeros_like(labels)
+    ref_rows = np.nonzero(np.isin(labels, ids[~floater]))[0]
+    target = labels[ref_rows[np.asarray(nearest(first[floater], ref_rows), np.int64)]]
+    table = np.arange(int(ids.max()) + 1, dtype=np.int64)
+    table[ids[floater]] = target
+    return table[labels]
+
+
+def load_point_cloud_scan(scan, segments_min_verts=POINTS_SEGMENTS_MIN_VERTS, segment_dimension_order=0, graph_k=8,
+                          graph_radius=0.1, small_segments="merge", device="cuda"):
+    """A coloured point cloud without a mesh (S3DIS rooms, laser scans, LiDAR) -> the dict of `load_mesh_only_scan`:
+
+        scene, cloud_path  str
+        xyz               f64[N,3]   kept points minus their minimum
+        rgb               f64[N,3]   colours * 255
+        segments          i64[N,L]   `felzenszwalb_cpp.segment_points` at every level of `segments_min_verts`, kept rows
+        segment_ids       i64[N]     column `segment_dimension_order`
+        seg_connectivity  i64[E,2]   that level's segment pairs, both directions
+        kept              i64[N]     rows of the file's vertex element
+        normals           f32[N,3]   kept rows: the file's nx, ny, nz, or `ops.estimate_normals` of the file's points
+        normals_from_file bool
+
+    The scan is `DIR/{scene}/{scene}.ply` or a flat `DIR/{scene}.ply` (`read_ply_points`).  The graph is
+    `felzenszwalb_cpp.point_graph(points, colours in [0, 1], normals of the file or None, graph_k, graph_radius)` — the
+    colour scale stanford.py:107-112 passes — built and sorted ONCE; every level is one host merge with kthr 0.005.
+    graph_k=8 and graph_radius=0.1 are unmeasured starting values.
+    small_segments, per level with its minimum n:
+        "merge"  `merge_floaters` (stanford.py:114-128 and its documented deviation), the nearest point through
+                 `ops.knn1_grid`; labels are renumbered and the connectivity recomputed from the edge list.  All rows stay.
+        "drop"   arkit's rule (`clean_segments`, `load_mesh_only_scan`): the rows of segments below the LAST level's
+                 minimum are removed, `kept` says which stay, pairs naming a removed segment are dropped.
+        "keep"   nothing; all rows stay.
+    The reference reconstructs a Poisson mesh and segments that (stanford.py:80-135); see DESIGN.md §3.30."""
+    import torch
+
+    from .. import felzenszwalb_cpp as felz
+    from .. import ops
+
+    levels = _check_point_cloud_args(segments_min_verts, segment_dimension_order, graph_k, graph_radius, small_segments)
+    scene, cloud_path = point_cloud_scan_path(scan)
+    points, colors, file_normals = read_ply_points(cloud_path)
+    n_points = points.shape[0]
+    if n_points == 0:
+        raise ValueError(f"{cloud_path}: the vertex element is empty")
+    rgb = colors.astype(np.float64) * 255.0
+    whole = np.rint(rgb)                               # as load_mesh_only_scan: integer colours come back exact
+    rgb = np.where(np.abs(rgb - whole) < 1e-3, whole, rgb)
+    dev = torch.device(device)
+    points_d = torch.from_numpy(points).to(dev)
+    normals_d = ops.estimate_normals(points_d) if file_normals is None else torch.from_numpy(file_normals).to(dev)
+    sa, sb, sw = felz.point_graph(points_d, colors, normals_d, graph_k, graph_radius, device=dev,
+                                  oriented=file_normals is not None)
+
+    def nearest(query_rows, ref_rows):
+        q = points_d[torch.from_numpy(query_rows).to(dev)].contiguous()
+        r = points_d[torch.from_numpy(ref_rows).to(dev)].contiguous()
+        return ops.knn1_grid(q, r)[1].cpu().numpy()
+
+    segments, connectivity, valid = [], [], np.ones(n_points, bool)
+    for n in levels:
+        seg, conn = felz.relabel_symmetric(felz.merge_host(sa, sb, sw, n_points, 0.005, n), sa, sb)
+        if small_segments == "merge":
+            seg, conn = felz.relabel_symmetric(merge_floaters(seg, conn, n, nearest), sa, sb)
+        elif small_segments == "drop":
+            _, valid = clean_segments(seg, min_vert_num=n)          # the last level's mask is the one that is used
+        segments.append(seg)
+        connectivity.append(conn)
+    if not valid.any():
+        raise ValueError(f"{cloud_path}: no segment has {levels[-1]} points; nothing is left with small_segments='drop'")
+    segments = np.stack(segments, -1).astype(np.int64)[valid]
+    xyz = points[valid].astype(np.float64)
+    xyz -= xyz.min(0)
+    level = int(segment_dimension_order)
+    conn = np.asarray(connectivity[level], np.int64).reshape(-1, 2)
+    conn = conn[np.isin(conn, np.unique(segments[:, level])).all(1)]
+    return {"scene": scene, "cloud_path": cloud_path, "xyz": xyz, "rgb": rgb[valid], "segments": segments,
+            "segment_ids": np.ascontiguousarray(segments[:, level]), "seg_connectivity": conn,
+            "kept": np.nonzero(valid)[0].astype(np.int64), "normals": normals_d.cpu().numpy()[valid],
+            "normals_from_file": file_normals is not None}
+
+
 # ------------------------------------------------------------------------------------------------------------- scene
 def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_min_verts=None, frame_batch=None,
                 attention=False, every=1, align=True, device="cuda", model_3d=None, resolution_scale=2,
-                precision_3d="f32", images=True, layout="scannet", segment_dimension_order=0):
+                precision_3d="f32", images=True, layout="scannet", segment_dimension_order=0, graph_k=8,
+                graph_radius=0.1, small_segments="merge"):
     """One scan directory -> the arrays of a scene file (tools/pseudo_masks_run.py), as the reference's dataset and
     `encode_scene_feats` produce them at test time (no augmentation):
 
@@ -441,12 +590,17 @@ def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_
     levels, None meaning ARKIT_SEGMENTS_MIN_VERTS, and `segment_dimension_order` picks the level that is written).  There is no
     info file, no alignment and no frame: it needs `model_3d`, the file is geometry-only (no `feats_2d`), the points
     are the kept vertices shifted to the origin, `colors` is rgb / 255 - 0.5 of the kept voxels as above and
-    `full_res_coords` is the kept, shifted vertices in f32.  layout="scannet", the default, is everything above."""
+    `full_res_coords` is the kept, shifted vertices in f32.  layout="scannet", the default, is everything above.
+
+    layout="points": `scan_dir` is a point-cloud scan (`load_point_cloud_scan` with `graph_k`, `graph_radius`,
+    `small_segments`; `segments_min_verts` None means POINTS_SEGMENTS_MIN_VERTS).  Frame-less like "arkit" in every
+    respect above: it needs `model_3d`, the file is geometry-only, the points are the kept points shifted to the
+    origin.  Images for point-cloud scans are not covered."""
     import torch
 
-    if layout not in ("scannet", "arkit"):
-        raise ValueError(f"build_scene: layout must be 'scannet' or 'arkit', got {layout!r}")
-    if layout == "arkit":
+    if layout not in LAYOUTS:
+        raise ValueError(f"build_scene: layout must be 'scannet', 'arkit' or 'points', got {layout!r}")
+    if layout != "scannet":
         images = False
     if not images and model_3d is None:
         raise ValueError("build_scene(images=False) needs model_3d: the scene file would hold no features")
@@ -460,6 +614,12 @@ def build_scene(scan_dir, model, voxel_size=0.02, image_hw=(192, 256), segments_
     if layout == "arkit":
         levels = ARKIT_SEGMENTS_MIN_VERTS if segments_min_verts is None else segments_min_verts
         m = load_mesh_only_scan(scan_dir, levels, segment_dimension_order, device=dev)
+        xyz, colors = m["xyz"], (m["rgb"] / 255.0).astype(np.float32)
+        seg, conn, info, axis = m["segment_ids"], m["seg_connectivity"], None, None
+    elif layout == "points":
+        levels = POINTS_SEGMENTS_MIN_VERTS if segments_min_verts is None else segments_min_verts
+        m = load_point_cloud_scan(scan_dir, levels, segment_dimension_order, graph_k, graph_radius, small_segments,
+                                  device=dev)
         xyz, colors = m["xyz"], (m["rgb"] / 255.0).astype(np.float32)
         seg, conn, info, axis = m["segment_ids"], m["seg_connectivity"], None, None
     else:
